@@ -16,9 +16,6 @@ import argparse, ctypes, json, os, socket, subprocess, sys, time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# hardware queues for the HIP runtime of this process (read once, when the runtime initialises -- before torch or the library touches the GPU): the pipeline's seven streams
-# on the default four queues run 5 % slower (csrc/zkc_api.hip zkc_runtime_defaults; profiles/r05_hw_queues_ab.json)
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')
 # the host side of a step is a few kilobytes of numpy / torch bookkeeping: one thread each.  Left alone, OpenBLAS starts 64 threads at import and torch's intra-op pool one per
 # schedulable core (256 on the GPU boxes) -- and eight ranks share 16 cores' worth of CPU time (profiles/r04_cpu_baseline_scaling.json); a parallel region that wakes 256 threads to add
 # up 1 024 status words costs more than the step's enqueueing.  (The CPU baseline leg and the batch verifier use their own threads, not these pools.)
@@ -41,6 +38,8 @@ def parse_args():
     ap.add_argument('--no-verify', action='store_true', help='skip the post-run verification of the timed proofs')
     ap.add_argument('--no-step-pipelining', action='store_true', help='one synchronous call per step (rounds 1-2) instead of begin(k + 1) before finish(k)')
     ap.add_argument('--no-extras', action='store_true', help='skip the extra legs after the timed region (host-to-host rate, unfolded / worst-case rates, isolated per-stage times)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned (proofs, public signals, status; gathered records with N > 1) '
+                                                           'as DIR/<name>.npy, float32, at most 64 MB in all')
     ap.add_argument('--dry-run-cpu', action='store_true',
                     help='launcher / rendezvous / gather rehearsal on the CPU (gloo, fabricated records, no prover): NOT a measurement')
     return ap.parse_args()
@@ -106,6 +105,37 @@ def draw_rs(rng, n):
         good = a[lt][:n - have]
         out[have:have + len(good)] = good; have += len(good)
     return out
+
+
+def test_artifacts(setup, nlevels):
+    """The seeded test key: in the package's build/artifacts when that holds it or can be written, else in a per-user directory under the system's
+    temporary directory (a checkout the benchmark may only read).  The key's bytes depend on the seed alone, so either place gives the same proofs."""
+    import errno, tempfile
+    try:
+        return setup.ensure_test_artifacts(nlevels)
+    except OSError as e:
+        if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS):
+            raise
+    return setup.ensure_test_artifacts(nlevels, directory=os.path.join(tempfile.gettempdir(), 'zkcensus_artifacts_%d' % os.getuid()))
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array is (rows, columns) of small integers (bytes, status codes), written as float32 (exact).  Past DUMP_LIMIT in all, the same fixed seeded
+    sample of rows is kept from every array of that row count, and its indices go beside them as <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    frac = (DUMP_LIMIT - 4096 * len(arrays)) / (total + 8 * sum(len(a) for a in arrays.values()))       # room for the .npy headers and the row indices
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, int(len(a) * frac))
+            rows = np.sort(np.random.default_rng(0x5A4B43).choice(len(a), keep, replace=False))
+            np.save(os.path.join(path, name + '_rows.npy'), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + '.npy'), a.astype(np.float32))
 
 
 def dry_run(args, rank, world):
@@ -455,10 +485,10 @@ def main():
     from zkcensus_amd import setup, census, parallel, groth16
     # ---- artifacts: test proving key (the reference's proving_key.zkey is a missing blob) ----
     if local == 0:
-        setup.ensure_test_artifacts(args.nlevels)
+        test_artifacts(setup, args.nlevels)
     if world > 1:
         dist.barrier()
-    _, zkey_path, vkey_path = setup.ensure_test_artifacts(args.nlevels)
+    _, zkey_path, vkey_path = test_artifacts(setup, args.nlevels)
     ctx = zkcensus_amd.Context(dev)
     zkey_bytes = open(zkey_path, 'rb').read()
     pk = zkcensus_amd.ProvingKey(ctx, zkey_bytes)
@@ -586,6 +616,12 @@ def main():
         cpu_per_rank = [round(float(t.item()), 3) for t in each]
     dt = float(tmax.item())
     assert all(int(t.abs().sum().item()) == 0 for t in d_status_s), 'a synthetic voter failed a circuit assert'
+    if args.dump_outputs and rank == 0:                  # what a caller of the timed path receives from its last step (proofs / public signals as 256 bytes per voter)
+        outs = {'proofs': np.frombuffer(out['proofs'], dtype=np.uint8).reshape(B, 256), 'public_signals': np.frombuffer(out['pubs'], dtype=np.uint8).reshape(B, 256),
+                'status': d_status.cpu().numpy().reshape(B, 1)}
+        if world > 1:
+            outs['records'] = out['records'].cpu().numpy().reshape(B * world, -1)
+        dump_outputs(args.dump_outputs, outs)
 
     # ---- per-category device time from HIP events on the library's stream ----
     prof = read_prof(ctx)

@@ -58,3 +58,52 @@ def test_eight_ranks_one_dies():
     t0 = time.time()
     r = subprocess.run([sys.executable, 'bench.py', '--gpus', '8', '--dry-run-cpu'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode != 0 and 'rank 5 exited with status 7' in r.stderr and time.time() - t0 < 120
+
+
+def test_dump_outputs_exact_and_bounded(tmp_path):
+    """--dump-outputs: byte arrays come back exactly as float32; past the size limit a fixed seeded sample of rows is kept (the same rows in every array
+    of that length, the same rows from run to run) and the files stay under the limit."""
+    import numpy as np
+    code = ("import importlib.util, sys, numpy as np\n"
+            "spec = importlib.util.spec_from_file_location('bench', 'bench.py'); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)\n"
+            "a = (np.arange(4096 * 256) * 7 % 256).astype(np.uint8).reshape(4096, 256); s = np.arange(4096, dtype=np.int32).reshape(4096, 1)\n"
+            "b.dump_outputs(sys.argv[1] + '/full', {'proofs': a[:64], 'status': s[:64]})\n"
+            "b.DUMP_LIMIT = 1 << 20\n"
+            "for d in ('cut1', 'cut2'):\n"
+            "    b.dump_outputs(sys.argv[1] + '/' + d, {'proofs': a, 'status': s})\n")
+    r = subprocess.run([sys.executable, '-c', code, str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    a = (np.arange(4096 * 256) * 7 % 256).astype(np.uint8).reshape(4096, 256)
+    full = {f[:-4]: np.load(tmp_path / 'full' / f) for f in os.listdir(tmp_path / 'full')}
+    assert sorted(full) == ['proofs', 'status'] and full['proofs'].dtype == np.float32
+    assert (full['proofs'] == a[:64]).all() and (full['status'][:, 0] == np.arange(64)).all()
+    cut = tmp_path / 'cut1'
+    assert sum(os.path.getsize(cut / f) for f in os.listdir(cut)) <= 1 << 20
+    rows = np.load(cut / 'proofs_rows.npy').astype(np.int64)
+    assert 0 < len(rows) < 4096 and (np.load(cut / 'status_rows.npy') == rows).all()
+    assert (np.load(cut / 'proofs.npy') == a[rows]).all() and (np.load(cut / 'status.npy')[:, 0] == rows).all()
+    for f in os.listdir(cut):
+        assert (np.load(cut / f) == np.load(tmp_path / 'cut2' / f)).all()
+
+
+def test_test_key_falls_back_when_the_package_cannot_be_written(tmp_path):
+    """bench.py on a checkout it may only read: the seeded test key goes to a per-user directory under the temporary directory instead of failing;
+    any other error is not swallowed."""
+    code = ("import errno, importlib.util, sys, tempfile\n"
+            "spec = importlib.util.spec_from_file_location('bench', 'bench.py'); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)\n"
+            "class S:\n"
+            "    def __init__(self, err): self.err, self.calls = err, []\n"
+            "    def ensure_test_artifacts(self, nl, directory=None):\n"
+            "        self.calls.append(directory)\n"
+            "        if directory is None: raise self.err\n"
+            "        return directory\n"
+            "s = S(PermissionError(errno.EACCES, 'denied')); d = b.test_artifacts(s, 10)\n"
+            "assert s.calls == [None, d] and d.startswith(tempfile.gettempdir()), s.calls\n"
+            "s = S(OSError(errno.ENOSPC, 'full'))\n"
+            "try:\n"
+            "    b.test_artifacts(s, 10); raise SystemExit('ENOSPC was swallowed')\n"
+            "except OSError as e:\n"
+            "    assert e.errno == errno.ENOSPC and s.calls == [None]\n"
+            "print('ok')\n")
+    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=120, env=dict(os.environ, TMPDIR=str(tmp_path)))
+    assert r.returncode == 0 and r.stdout.strip() == 'ok', r.stderr[-2000:]

@@ -52,13 +52,6 @@ def test_circuit_selection_by_wasm_hash():
     info = open(ol.golden('ref/circuits-info.md')).read()
     sha = [l.split()[0] for l in info.splitlines() if l.strip().endswith('circuit.wasm')][0]
     assert sha == '80a73567f6a4655d4332301efcff4bc5711bb48176d1c71fdb1e48df222ac139'
-    wasm = '/root/reference/artifacts/zkCensus/dev/160/circuit.wasm'
-    if os.path.exists(wasm):                                      # only where the reference tree is present (not on the GPU box)
-        raw = open(wasm, 'rb').read()
-        assert lib.zkc_circuit_nlevels_from_wasm(raw, len(raw), hexbuf) == 160 and hexbuf.value.decode() == sha
-        assert groth16.circuit_nlevels(wasm) == 160
-        with pytest.raises(ValueError):
-            groth16.circuit_nlevels(wasm, 10)
 
 
 def test_verifier_strictness_and_return_codes():

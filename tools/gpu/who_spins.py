@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
 """Which host threads burn CPU while the batch pipeline runs?  Lists the threads each start-up stage creates, then samples every thread's state / syscall /
-CPU time while batch steps run, and finally lets rocgdb print the top frames of the busy ones."""
-import os, sys, time, threading, subprocess, ctypes
+CPU time while batch steps run."""
+import os, sys, time, threading
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')
 
 def tids():
     return set(os.listdir('/proc/self/task'))
@@ -57,15 +56,4 @@ dt = time.time() - w0
 busy = sorted(((cpu(t)[1] - c0.get(t, 0)) / dt, t) for t in tids())[-4:]
 for u, t in reversed(busy):
     s = samples.get(t, []); print('tid %s  %.2f cores  states %s' % (t, u, {k: s.count(k) for k in set(s)}))
-if os.environ.get('WHO_GDB') == '1':
-    libc = ctypes.CDLL(None); libc.prctl(0x59616d61, ctypes.c_ulong(-1 & 0xffffffffffffffff), 0, 0, 0)      # PR_SET_PTRACER, PR_SET_PTRACER_ANY
-    cmds = []
-    for u, t in reversed(busy[-3:]):
-        cmds += ['-ex', 'thread find %s' % t]
-    r = subprocess.run(['/opt/rocm/bin/rocgdb', '-p', str(os.getpid()), '-batch', '-ex', 'set pagination off', '-ex', 'thread apply all bt 6'], capture_output=True, text=True, timeout=240)
-    out = r.stdout
-    for u, t in reversed(busy[-3:]):
-        k = out.find('LWP %s)' % t)
-        print('---- tid %s (%.2f cores)\n%s' % (t, u, out[max(0, k - 60):k + 900] if k >= 0 else '(not found)'))
-    if r.returncode: print(r.stderr[-600:])
 stop = True; th.join(); pk.close(); ctx.close()

@@ -144,9 +144,8 @@ static void conv_consts(std::vector<Fr>& out, const unsigned long long (&src)[N]
 // [r5] Hardware queues.  ROCm maps a process' HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and a queue executes in order: a stream whose queue also
 // carries another stream's pending barrier packet (a hipStreamWaitEvent that has not fired) runs behind it.  This pipeline keeps seven to sixteen streams busy with cross-
 // stream waits; on four queues the batch path lost 5 % (3104 -> 3267 proofs/s with 8, same box) and the proving service's lanes ran one after another instead of side by
-// side (profiles/r05_service_hw_queues.txt).  The variable is read when the HIP runtime initialises, so it is set here, at library load, unless the host has set it; a host
-// that initialises HIP before loading this library (or wants another value) sets GPU_MAX_HW_QUEUES itself -- bench.py and the N-API addon do.
-__attribute__((constructor)) static void zkc_runtime_defaults() { setenv("GPU_MAX_HW_QUEUES", "24", 0); }
+// side (profiles/r05_service_hw_queues.txt).  The library does not set the variable: the queue count is the host's choice, and hosts that share a GPU
+// with other processes keep it low.
 
 extern "C" int zkc_ctx_create(int device, zkc_ctx** out) {
     if (!out) return zkc_fail(nullptr, ZKC_ERR_BAD_ARG, "out == NULL");
