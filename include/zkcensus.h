@@ -298,6 +298,54 @@ int zkc_smt_build(zkc_ctx* ctx, const void* keys, const void* values, size_t n, 
 int zkc_census_inputs(zkc_ctx* ctx, size_t n, int nLevels, const uint8_t election_id[64], const void* address, const void* password, const void* signature,
                       const void* available_weight, const void* vote_weight, const void* vote_hash, void* inputs_out, void* d_inputs_out, uint8_t* roots_out);
 
+/* ---- f1: a census tree that grows in place (arbo NewTree / Add / AddBatch / Update / Get / GenProof; internal/helpers.go:36-85).  Same semantics as zkc_smt_build: leaf =
+ * H(key, value, 1), node = H(left, right), path bit i = bit i of the key (LSB first), an empty subtree is 0, a single-leaf subtree is that leaf's hash; MaxLevels = nLevels
+ * (1..253), so a tree equals zkc_smt_build over its current (key, value) set, root and sibling lists byte for byte.  All keys and values 32-byte little-endian, standard form.
+ *
+ * A zkc_tree belongs to one zkc_ctx, which must outlive it (the rule of zkc_zkey).  The trie lives on the host as flat arrays (per inner node: left, right, depth; per leaf:
+ * key, value); the hashes live on the device in one array indexed by node reference (leaves and inner nodes share the references, 0 = empty; capacity doubles as it fills).
+ * A call uploads only what changed -- the new or updated leaves and the dirty inner nodes, deepest first -- and rehashes just those on ctx's stream: a 1 024-voter add into
+ * a 2^20-voter tree touches ~12 k nodes.  Memory: ~64 B of device memory and ~100 B of host memory per voter (10^7 voters: ~0.7 GB of HBM, ~1 GB of host memory).
+ *
+ * Batches: every entry gets a ZKC_TREE_* status; a batch has the effect of applying its entries one by one in order, and a rejected entry changes nothing (arbo AddBatch's
+ * "invalids").  Calls return ZKC_OK when they ran (whatever the statuses), ZKC_ERR_BAD_ARG for a bad handle or a missing pointer.  A HIP failure during a change marks the
+ * tree broken: every later call on it fails, no half-updated root is ever served.  Each tree has a mutex: calls on one tree from several threads are serialised.
+ * zkc_tree_add         : arbo Add / AddBatch.  status: OK, KEY_EXISTS (also a key repeated within the batch), COLLISION (shares its first nLevels path bits with a key of
+ *                        the tree), NOT_BELOW_R (key or value >= r).
+ * zkc_tree_update      : arbo Update.  status: OK, KEY_ABSENT, NOT_BELOW_R.
+ * zkc_tree_root        : the current root (0 for an empty tree).  zkc_tree_size: the number of leaves.
+ * zkc_tree_get         : values_out n x 32 B (zero where absent), exists n x int32 (1 / 0).
+ * zkc_tree_gen_proof   : root (32 B) and, per key, siblings (n x (nLevels + 1) x 32 B, zero-padded as zkc_smt_build pads them), depths (levels above the leaf) and exists
+ *                        (1 / 0; an absent key gets zero siblings and depth 0; non-membership proofs are not made).  The root is the one the siblings belong to.
+ *                        siblings, depths may be NULL.
+ * zkc_tree_census_inputs: zkc_census_inputs for n voters of two resident trees -- census: address -> available weight, sik: address -> SIK, same context, same nLevels --
+ *                        without touching either tree: the SIK H(address, password, signature) and the nullifier are hashed on the GPU, availableWeight is the census
+ *                        tree's stored value.  status n x int32: OK, NOT_IN_CENSUS, NOT_IN_SIK, SIK_MISMATCH (the SIK tree holds another value); a voter that is not OK
+ *                        gets a zeroed block.  inputs_out / d_inputs_out / roots_out as for zkc_census_inputs (roots_out may be NULL).
+ * zkc_tree_stats       : ms[0] = host trie time, ms[1] = device time (upload, kernels, synchronise) of the last add or update. ---- */
+typedef struct zkc_tree zkc_tree;
+enum {
+    ZKC_TREE_OK = 0,
+    ZKC_TREE_KEY_EXISTS = 1,          /* add: the key is in the tree, or earlier in the same batch */
+    ZKC_TREE_KEY_ABSENT = 2,          /* update */
+    ZKC_TREE_COLLISION = 3,           /* add: another key shares the first nLevels path bits */
+    ZKC_TREE_NOT_BELOW_R = 4,         /* key or value >= r */
+    ZKC_TREE_NOT_IN_CENSUS = 5,       /* census_inputs: the address is not in the census tree */
+    ZKC_TREE_NOT_IN_SIK = 6,          /* census_inputs: the address is not in the SIK tree */
+    ZKC_TREE_SIK_MISMATCH = 7         /* census_inputs: the SIK tree holds another SIK for the address */
+};
+int  zkc_tree_create(zkc_ctx* ctx, int nLevels, zkc_tree** out);
+void zkc_tree_free(zkc_tree* tree);
+int  zkc_tree_add(zkc_tree* tree, const void* keys, const void* values, size_t n, int32_t* status);
+int  zkc_tree_update(zkc_tree* tree, const void* keys, const void* values, size_t n, int32_t* status);
+int  zkc_tree_root(zkc_tree* tree, uint8_t root[32]);
+int  zkc_tree_size(zkc_tree* tree, size_t* leaves);
+int  zkc_tree_get(zkc_tree* tree, const void* keys, size_t n, void* values_out, int32_t* exists);
+int  zkc_tree_gen_proof(zkc_tree* tree, const void* keys, size_t n, uint8_t root[32], void* siblings, int32_t* depths, int32_t* exists);
+int  zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n, const uint8_t election_id[64], const void* address, const void* password, const void* signature,
+                            const void* vote_weight, const void* vote_hash, void* inputs_out, void* d_inputs_out, uint8_t roots_out[64], int32_t* status);
+int  zkc_tree_stats(zkc_tree* tree, double ms[2]);
+
 /* ---- measurement: HIP-event timing per kernel category on zkc_ctx_stream (bit i of mask enables category i) ----
  * 0 witness, 1 buildABC mat-vec, 2 NTT+joinABC, 3 MSM digits+sort+offsets, 4 MSM bucket accumulation G1, 5 same G2,
  * 6 MSM heavy+reduce+final, 7 (no timing) bytes = (scalar, base) pairs x 96 B that entered the G1 MSMs after constant folding and

@@ -63,6 +63,17 @@ def load():
     L.zkc_poseidon_batch.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
     L.zkc_smt_build.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, i32p]
     L.zkc_census_inputs.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_char_p]
+    sz = ctypes.c_size_t
+    L.zkc_tree_create.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp)]
+    L.zkc_tree_free.argtypes = [vp]; L.zkc_tree_free.restype = None
+    L.zkc_tree_add.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, i32p]
+    L.zkc_tree_update.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, i32p]
+    L.zkc_tree_root.argtypes = [vp, ctypes.c_char_p]
+    L.zkc_tree_size.argtypes = [vp, ctypes.POINTER(sz)]
+    L.zkc_tree_get.argtypes = [vp, ctypes.c_char_p, sz, vp, i32p]
+    L.zkc_tree_gen_proof.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp, i32p, i32p]
+    L.zkc_tree_census_inputs.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_char_p, i32p]
+    L.zkc_tree_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.zkc_profile_enable.argtypes = [vp, ctypes.c_uint32]
     L.zkc_ntt_dev.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.zkc_g1_mul_batch_dev.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint32, vp]

@@ -197,3 +197,112 @@ def deep_voters(ctx, n_voters, nLevels=160, depth=None, seed=160):
     return [{'electionId': list(eid), 'nullifier': str(nullifier[i]), 'availableWeight': str(avail[i]), 'voteHash': ['1', '2'], 'sikRoot': str(sroot[i]),
              'censusRoot': str(croot[i]), 'address': str(address[i]), 'password': str(password[i]), 'signature': str(signature[i]), 'voteWeight': '1',
              'censusSiblings': pad(csib[i]), 'sikSiblings': pad(ssib[i])} for i in range(n_voters)]
+
+
+def _le(xs):
+    """ints -> concatenated 32-byte little-endian words (bytes pass through unchanged)"""
+    return bytes(xs) if isinstance(xs, (bytes, bytearray)) else b''.join(int(x).to_bytes(32, 'little') for x in xs)
+
+
+def smt_build(ctx, keys, values, nLevels=160, siblings=True):
+    """One static tree over (key, value) pairs (zkc_smt_build): (root, siblings bytes n x (nLevels + 1) x 32 or None, depths)."""
+    kb, vb = _le(keys), _le(values)
+    n = len(kb) // 32
+    root = ctypes.create_string_buffer(32); dep = (ctypes.c_int32 * n)()
+    sib = ctypes.create_string_buffer(32 * n * (nLevels + 1)) if siblings else None
+    ctx._check(ctx._lib.zkc_smt_build(ctx._h, kb, vb, n, nLevels, root, sib, dep))
+    return int.from_bytes(root.raw, 'little'), (sib.raw if siblings else None), list(dep)
+
+
+class CensusTree:
+    """A census tree that grows in place (zkc_tree_*, csrc/zkc_tree.hip): arbo Add / Update / Get / GenProof on a resident tree, the trie on the host, the hashes on the
+    GPU, each call rehashing only the nodes it changed.  Keys and values: lists of ints, or bytes of n x 32-byte little-endian words.  Statuses: ZKC_TREE_* (STATUS below).
+    Closed with its context at the latest (a context outlives its trees)."""
+
+    OK, KEY_EXISTS, KEY_ABSENT, COLLISION, NOT_BELOW_R, NOT_IN_CENSUS, NOT_IN_SIK, SIK_MISMATCH = range(8)
+
+    def __init__(self, ctx, nLevels=160):
+        self.ctx, self.nLevels, self._lib = ctx, nLevels, ctx._lib
+        h = ctypes.c_void_p()
+        ctx._check(self._lib.zkc_tree_create(ctx._h, int(nLevels), ctypes.byref(h)))
+        self._h = h
+        ctx._keys.append(self)            # the context closes what lives on it before itself
+
+    def close(self):
+        if getattr(self, '_h', None):
+            if getattr(self.ctx, '_h', None):
+                self._lib.zkc_tree_free(self._h)
+            self._h = None
+            if self in self.ctx._keys:
+                self.ctx._keys.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _change(self, fn, keys, values):
+        kb, vb = _le(keys), _le(values)
+        n = len(kb) // 32
+        assert len(vb) == len(kb), 'keys and values differ in length'
+        st = (ctypes.c_int32 * n)()
+        self.ctx._check(fn(self._h, kb, vb, n, st))
+        return list(st)
+
+    def add(self, keys, values):
+        """arbo Add / AddBatch: per-entry statuses; the rejected entries change nothing."""
+        return self._change(self._lib.zkc_tree_add, keys, values)
+
+    def update(self, keys, values):
+        return self._change(self._lib.zkc_tree_update, keys, values)
+
+    @property
+    def root(self):
+        r = ctypes.create_string_buffer(32)
+        self.ctx._check(self._lib.zkc_tree_root(self._h, r))
+        return int.from_bytes(r.raw, 'little')
+
+    def __len__(self):
+        n = ctypes.c_size_t()
+        self.ctx._check(self._lib.zkc_tree_size(self._h, ctypes.byref(n)))
+        return n.value
+
+    def stats(self):
+        """(host trie ms, device ms) of the last add or update"""
+        ms = (ctypes.c_double * 2)()
+        self.ctx._check(self._lib.zkc_tree_stats(self._h, ms))
+        return ms[0], ms[1]
+
+    def get(self, keys):
+        """(values, exists): the stored value of every key (0 where absent)"""
+        kb = _le(keys); n = len(kb) // 32
+        out = ctypes.create_string_buffer(32 * n + 1); ex = (ctypes.c_int32 * n)()
+        self.ctx._check(self._lib.zkc_tree_get(self._h, kb, n, ctypes.cast(out, ctypes.c_void_p), ex))
+        raw = out.raw
+        return [int.from_bytes(raw[32 * i:32 * i + 32], 'little') for i in range(n)], [bool(x) for x in ex]
+
+    def gen_proof(self, keys):
+        """(root, siblings, depths, exists): siblings as bytes, n x (nLevels + 1) x 32, zero-padded like zkc_smt_build; the root they belong to"""
+        kb = _le(keys); n = len(kb) // 32
+        r = ctypes.create_string_buffer(32); sib = ctypes.create_string_buffer(32 * n * (self.nLevels + 1) + 1)
+        dep = (ctypes.c_int32 * n)(); ex = (ctypes.c_int32 * n)()
+        self.ctx._check(self._lib.zkc_tree_gen_proof(self._h, kb, n, r, ctypes.cast(sib, ctypes.c_void_p), dep, ex))
+        return int.from_bytes(r.raw, 'little'), sib.raw[:32 * n * (self.nLevels + 1)], list(dep), [bool(x) for x in ex]
+
+
+def census_inputs_from_trees(ctx, census_tree, sik_tree, election_id, address, password, signature, vote_weight, vote_hash, d_out_ptr=None):
+    """census_inputs for n voters of two resident trees (zkc_tree_census_inputs): census_tree maps address -> available weight, sik_tree address -> SIK.  Returns
+    (flat bytes, census root, sik root, statuses); a voter whose status is not CensusTree.OK gets a zeroed block.  vote_hash: pairs."""
+    address = _le(address); n = len(address) // 32
+    nIn = 12 + 2 * (census_tree.nLevels + 1)
+    out = ctypes.create_string_buffer(32 * nIn * n); roots = ctypes.create_string_buffer(64); st = (ctypes.c_int32 * n)()
+    ctx._check(ctx._lib.zkc_tree_census_inputs(census_tree._h, sik_tree._h, n, _le(election_id), _le(address), _le(password), _le(signature), _le(vote_weight),
+                                               _le(x for pair in vote_hash for x in pair), ctypes.cast(out, ctypes.c_void_p), d_out_ptr, roots, st))
+    return out.raw, int.from_bytes(roots.raw[:32], 'little'), int.from_bytes(roots.raw[32:], 'little'), list(st)

@@ -1,0 +1,424 @@
+// zkc_tree.hip -- f1: a census tree that grows in place (arbo NewTree / Add / AddBatch / Update / Get / GenProof; internal/helpers.go:36-85), beside the static builder of
+// zkc_census.hip.  A Vocdoni census gains voters as they register; rebuilding the whole trie and rehashing every node per change costs what zkc_smt_build costs.  Here:
+//
+// - The trie stays on the host as flat arrays indexed by node reference (no pointers): per inner node its two child references and its depth, per leaf its key and value.
+//   Leaves and inner nodes share one reference space; 0 is the empty subtree.  A leaf keeps its reference when a later key pushes it down a chain, so its hash stays valid.
+// - The hashes stay on the device in ONE array val[reference] (val[0] = 0), doubled in place when full.  The device holds no child table: per batch the host uploads the
+//   whole description of the work -- the changed leaves as (slot, key, value) and the dirty inner nodes as (node, left, right) triples grouped by depth, deepest first --
+//   and rehashes only those: zkc_tree_leaves, then one zkc_tree_level launch per depth with more than a wave of dirty nodes and one zkc_tree_narrow launch per maximal run
+//   of narrower depths (the top of the tree, and the one-child chains below two keys with a long common path prefix: up to nLevels levels in one launch instead of one
+//   launch each).  Kernels live in zkc_witness.hip beside poseidon_trace29.
+//
+// arbo semantics as zkc_smt_build pins them: leaf = H(key, value, 1), node = H(left, right), path bit i = bit i of the key (LSB first), an empty subtree is 0, a subtree
+// holding one leaf is that leaf's hash; inner nodes sit at depths 0 .. nLevels - 1.  Inserting walks from the root along the key bits: at an empty child the leaf goes
+// there; at a leaf with another key, a chain of inner nodes (one child each, except the last) runs down to the first bit where the two keys differ.
+#include "zkc_internal.h"
+#include "zkc_field.h"
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+using namespace zkc;
+
+extern "C" __global__ void zkc_tree_leaves(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*);
+extern "C" __global__ void zkc_tree_level(PoseidonTable, const uint32_t*, uint32_t, uint32_t*);
+extern "C" __global__ void zkc_tree_narrow(PoseidonTable, const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*);
+extern "C" __global__ void zkc_census_hash(PoseidonTable, int, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, size_t);
+extern "C" __global__ void zkc_census_scatter(const uint32_t*, const uint2*, size_t, uint32_t*);
+extern "C" __global__ void zkc_census_scalars(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
+                                              const uint32_t*, const uint32_t*, size_t, int, uint32_t*);
+
+struct zkc_tree {
+    zkc_ctx* ctx = nullptr;
+    int nLevels = 0;
+    std::mutex mu;
+    bool broken = false;                     // a HIP call failed while the tree changed: host trie and device values may disagree
+    // host trie by reference: inner node -> a = left, b = right, depth 0 .. nLevels - 1; leaf -> a = leaf index, depth = LEAF.  Reference 0 (empty) is a placeholder.
+    std::vector<uint32_t> a{0}, b{0};
+    std::vector<uint8_t> depth{0}, dirty{0};
+    std::vector<uint8_t> keys, vals;         // per leaf index, 32 B each
+    uint32_t root = 0;
+    std::vector<uint32_t> dirty_nodes, dirty_leaves, path;
+    // device
+    uint32_t* d_val = nullptr; size_t cap = 0;              // val capacity, in references
+    void* d_stage = nullptr; size_t d_stage_sz = 0;         // a call's uploads
+    uint8_t* h_stage = nullptr; size_t h_stage_sz = 0;      // their pinned host copy
+    void* d_out = nullptr; size_t d_out_sz = 0;             // gen_proof / census_inputs output blocks
+    double ms[2] = {0, 0};
+};
+
+namespace {
+constexpr uint8_t LEAF = 0xff;
+constexpr uint32_t WAVE = 64;                // a depth with at most this many dirty nodes is narrow
+constexpr uint64_t MAX_REFS = 0xfffffff0ull;
+
+inline int key_bit(const uint8_t* key, int d) { return (key[d >> 3] >> (d & 7)) & 1; }
+inline bool below_r(const uint8_t* v) { uint32_t t[8]; memcpy(t, v, 32); return fp_std_lt_p<FrParams>(t); }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using clk = std::chrono::steady_clock;
+inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
+
+inline const uint8_t* leaf_key(const zkc_tree* t, uint32_t r) { return t->keys.data() + 32 * (size_t)t->a[r]; }
+inline uint8_t* leaf_val(zkc_tree* t, uint32_t r) { return t->vals.data() + 32 * (size_t)t->a[r]; }
+inline uint32_t child(const zkc_tree* t, uint32_t node, int side) { return side ? t->b[node] : t->a[node]; }
+inline void set_child(zkc_tree* t, uint32_t node, int side, uint32_t r) { if (!node) t->root = r; else (side ? t->b[node] : t->a[node]) = r; }
+uint32_t new_ref(zkc_tree* t, uint32_t a, uint32_t b, uint8_t depth) {
+    t->a.push_back(a); t->b.push_back(b); t->depth.push_back(depth); t->dirty.push_back(0);
+    return (uint32_t)(t->a.size() - 1);
+}
+uint32_t new_leaf(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
+    const uint32_t li = (uint32_t)(t->keys.size() / 32);
+    t->keys.insert(t->keys.end(), key, key + 32); t->vals.insert(t->vals.end(), val, val + 32);
+    return new_ref(t, li, 0, LEAF);
+}
+inline void mark(zkc_tree* t, uint32_t r, std::vector<uint32_t>& list) { if (!t->dirty[r]) { t->dirty[r] = 1; list.push_back(r); } }
+void mark_path(zkc_tree* t) { for (uint32_t r : t->path) mark(t, r, t->dirty_nodes); }
+
+// the leaf reference of `key` (0: absent); t->path = the inner nodes from the root down to where the walk ended
+uint32_t find(zkc_tree* t, const uint8_t* key) {
+    t->path.clear();
+    uint32_t r = t->root;
+    for (int d = 0; r; d++) {
+        if (t->depth[r] == LEAF) return memcmp(leaf_key(t, r), key, 32) == 0 ? r : 0;
+        t->path.push_back(r);
+        r = child(t, r, key_bit(key, d));
+    }
+    return 0;
+}
+int32_t add_one(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
+    if (!below_r(key) || !below_r(val)) return ZKC_TREE_NOT_BELOW_R;
+    t->path.clear();
+    uint32_t parent = 0; int side = 0;
+    for (int d = 0;; d++) {
+        const uint32_t r = parent ? child(t, parent, side) : t->root;
+        if (r == 0) {                                                              // an empty child: the leaf goes here
+            const uint32_t l = new_leaf(t, key, val);
+            set_child(t, parent, side, l); mark_path(t); mark(t, l, t->dirty_leaves);
+            return ZKC_TREE_OK;
+        }
+        if (t->depth[r] != LEAF) { t->path.push_back(r); parent = r; side = key_bit(key, d); continue; }
+        const uint8_t* other = leaf_key(t, r);
+        if (memcmp(other, key, 32) == 0) return ZKC_TREE_KEY_EXISTS;
+        int e = d; while (e < t->nLevels && key_bit(key, e) == key_bit(other, e)) e++;
+        if (e >= t->nLevels) return ZKC_TREE_COLLISION;
+        // a chain of inner nodes at depths d .. e: one child each down to e, where the old leaf r and the new one part
+        const uint32_t l = new_leaf(t, key, val);
+        uint32_t up = parent; int up_side = side;
+        for (int c = d; c <= e; c++) {
+            const uint32_t nd = new_ref(t, 0, 0, (uint8_t)c);
+            set_child(t, up, up_side, nd); t->path.push_back(nd);
+            up = nd; up_side = key_bit(key, c);
+        }
+        set_child(t, up, up_side, l); set_child(t, up, !up_side, r);
+        mark_path(t); mark(t, l, t->dirty_leaves);
+        return ZKC_TREE_OK;
+    }
+}
+int32_t update_one(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
+    if (!below_r(key) || !below_r(val)) return ZKC_TREE_NOT_BELOW_R;
+    const uint32_t l = find(t, key);
+    if (!l) return ZKC_TREE_KEY_ABSENT;
+    memcpy(leaf_val(t, l), val, 32);
+    mark_path(t); mark(t, l, t->dirty_leaves);
+    return ZKC_TREE_OK;
+}
+
+// room for `bytes` of uploads: device buffer and its pinned host copy (nothing of an earlier call is in flight: every call ends synchronised)
+int stage(zkc_tree* t, size_t bytes) {
+    zkc_ctx* ctx = t->ctx; int rc;
+    if ((rc = zkc_ensure(ctx, &t->d_stage, &t->d_stage_sz, bytes))) return rc;
+    if (t->h_stage_sz < bytes) {
+        if (t->h_stage) { ZKC_HIP_CHECK(ctx, hipHostFree(t->h_stage)); t->h_stage = nullptr; t->h_stage_sz = 0; }
+        const size_t sz = std::max(bytes, (size_t)1 << 20);
+        ZKC_HIP_CHECK(ctx, hipHostMalloc((void**)&t->h_stage, sz));
+        t->h_stage_sz = sz;
+    }
+    return ZKC_OK;
+}
+// val holds at least `need` references: double it, copying the old values on the stream
+int grow(zkc_tree* t, size_t need) {
+    if (need <= t->cap) return ZKC_OK;
+    zkc_ctx* ctx = t->ctx;
+    size_t cap = std::max<size_t>(t->cap, 1024); while (cap < need) cap *= 2;
+    uint32_t* nv = nullptr;
+    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&nv, 32 * cap));
+    if (t->d_val) {
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(nv, t->d_val, 32 * t->cap, hipMemcpyDeviceToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipFree(t->d_val));
+    } else {
+        ZKC_HIP_CHECK(ctx, hipMemsetAsync(nv, 0, 32, ctx->stream));                    // val[0]: the empty subtree
+    }
+    t->d_val = nv; t->cap = cap;
+    return ZKC_OK;
+}
+
+// hash what the entries of this call changed: the dirty leaves, then the dirty inner nodes deepest first.  Clears the dirty lists.
+int commit(zkc_tree* t, clk::time_point t0) {
+    zkc_ctx* ctx = t->ctx;
+    const size_t K = t->dirty_leaves.size(), M = t->dirty_nodes.size();
+    for (uint32_t r : t->dirty_leaves) t->dirty[r] = 0;
+    for (uint32_t r : t->dirty_nodes) t->dirty[r] = 0;
+    if (!K && !M) { t->ms[0] = ms_since(t0); t->ms[1] = 0; return ZKC_OK; }
+    // the dirty nodes by depth, deepest first: position of depth d's first triple = pos[d]
+    int D = 0; for (uint32_t r : t->dirty_nodes) D = std::max(D, t->depth[r] + 1);
+    std::vector<uint32_t> cnt(D, 0), pos(D + 1, 0);
+    for (uint32_t r : t->dirty_nodes) cnt[t->depth[r]]++;
+    { uint32_t p = 0; for (int d = D - 1; d >= 0; d--) { pos[d] = p; p += cnt[d]; } pos[D] = 0; }
+    // one upload: [slots K][keys K x 32 B][values K x 32 B][triples M x 3][offsets: position of the k-th deepest depth, D + 1]
+    const size_t o_keys = align256(4 * K), o_vals = o_keys + align256(32 * K), o_trip = o_vals + align256(32 * K), o_off = o_trip + align256(12 * M), total = o_off + 4 * ((size_t)D + 1);
+    int rc;
+    if ((rc = stage(t, total))) return rc;
+    uint8_t* h = t->h_stage;
+    uint32_t* hs = (uint32_t*)h; uint32_t* ht = (uint32_t*)(h + o_trip); uint32_t* ho = (uint32_t*)(h + o_off);
+    const uint64_t nref = t->a.size();
+    for (size_t i = 0; i < K; i++) {
+        const uint32_t r = t->dirty_leaves[i];
+        hs[i] = r; memcpy(h + o_keys + 32 * i, leaf_key(t, r), 32); memcpy(h + o_vals + 32 * i, leaf_val(t, r), 32);
+    }
+    { std::vector<uint32_t> fill(pos.begin(), pos.end() - 1);
+      for (uint32_t r : t->dirty_nodes) { uint32_t* q = ht + 3 * (size_t)fill[t->depth[r]]++; q[0] = r; q[1] = t->a[r]; q[2] = t->b[r]; } }
+    for (int k = 0; k < D; k++) ho[k] = pos[D - 1 - k];
+    ho[D] = (uint32_t)M;
+    // every reference a kernel will follow is below the number of references (and so below val's capacity, grown to it next)
+    for (size_t i = 0; i < K; i++) if (hs[i] == 0 || hs[i] >= nref) return zkc_fail(ctx, ZKC_ERR_GENERIC, "zkc_tree: leaf slot out of range");
+    for (size_t i = 0; i < 3 * M; i++) if (ht[i] >= nref || (i % 3 == 0 && ht[i] == 0)) return zkc_fail(ctx, ZKC_ERR_GENERIC, "zkc_tree: node reference out of range");
+    t->dirty_leaves.clear(); t->dirty_nodes.clear();
+    t->ms[0] = ms_since(t0);
+    const clk::time_point t1 = clk::now();
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if ((rc = grow(t, nref))) return rc;
+    uint8_t* dst = (uint8_t*)t->d_stage;
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(dst, h, total, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t* dt = (const uint32_t*)(dst + o_trip); const uint32_t* dof = (const uint32_t*)(dst + o_off);
+    if (K) hipLaunchKernelGGL(zkc_tree_leaves, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, ctx->stream, ctx->ptab, (const uint32_t*)dst, (const uint32_t*)(dst + o_keys),
+                              (const uint32_t*)(dst + o_vals), (uint32_t)K, t->d_val);
+    for (int k = 0; k < D;) {                        // k-th deepest depth
+        const uint32_t c = ho[k + 1] - ho[k];
+        if (c > WAVE) {
+            hipLaunchKernelGGL(zkc_tree_level, dim3((c + 63) / 64), dim3(64), 0, ctx->stream, ctx->ptab, dt + 3 * (size_t)ho[k], c, t->d_val);
+            k++;
+        } else {
+            int j = k; while (j < D && ho[j + 1] - ho[j] <= WAVE) j++;
+            hipLaunchKernelGGL(zkc_tree_narrow, dim3(1), dim3(64), 0, ctx->stream, ctx->ptab, dt, dof + k, (uint32_t)(j - k), (uint32_t)M, t->d_val);
+            k = j;
+        }
+    }
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    t->ms[1] = ms_since(t1);
+    return ZKC_OK;
+}
+
+int change(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status, bool add) {
+    if (!t || (n && (!keys || !values || !status))) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_add / update: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    zkc_ctx* ctx = t->ctx;
+    ZKC_LOCK(ctx);
+    if (t->broken) return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_tree: the tree is broken by an earlier device failure");
+    if (add && t->a.size() + (uint64_t)n * (t->nLevels + 2) > MAX_REFS) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_add: the tree would exceed 2^32 nodes");
+    const clk::time_point t0 = clk::now();
+    const uint8_t* k = (const uint8_t*)keys; const uint8_t* v = (const uint8_t*)values;
+    for (size_t i = 0; i < n; i++) status[i] = add ? add_one(t, k + 32 * i, v + 32 * i) : update_one(t, k + 32 * i, v + 32 * i);
+    const int rc = commit(t, t0);
+    if (rc) t->broken = true;
+    return rc;
+}
+int read_root(zkc_tree* t, uint8_t root[32]) {
+    zkc_ctx* ctx = t->ctx;
+    if (!t->root) { memset(root, 0, 32); return ZKC_OK; }
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(root, t->d_val + 8 * (size_t)t->root, 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
+}
+// (dst, ref) pairs of the non-zero siblings on t->path for a key: dst = base + level
+void sibling_pairs(const zkc_tree* t, const uint8_t* key, size_t base, std::vector<uint2>& out) {
+    for (size_t l = 0; l < t->path.size(); l++) {
+        const uint32_t s = child(t, t->path[l], !key_bit(key, (int)l));
+        if (s) out.push_back(make_uint2((uint32_t)(base + l), s));
+    }
+}
+}  // namespace
+
+extern "C" int zkc_tree_create(zkc_ctx* ctx, int nLevels, zkc_tree** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || nLevels < 1 || nLevels > 253) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_create: bad argument");
+    ZKC_LOCK(ctx);
+    zkc_tree* t = new zkc_tree;
+    t->ctx = ctx; t->nLevels = nLevels;
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = grow(t, 1)) == ZKC_OK) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = zkc_fail(ctx, ZKC_ERR_HIP, std::string("zkc_tree_create: ") + hipGetErrorString(e));
+    }
+    if (rc) { zkc_tree_free(t); return rc; }
+    *out = t;
+    return ZKC_OK;
+}
+
+extern "C" void zkc_tree_free(zkc_tree* t) {
+    if (!t) return;
+    {
+        std::lock_guard<std::mutex> g(t->mu);
+        ZKC_LOCK(t->ctx);
+        (void)hipSetDevice(t->ctx->device);
+        (void)hipStreamSynchronize(t->ctx->stream);
+        if (t->d_val) (void)hipFree(t->d_val);
+        if (t->d_stage) (void)hipFree(t->d_stage);
+        if (t->d_out) (void)hipFree(t->d_out);
+        if (t->h_stage) (void)hipHostFree(t->h_stage);
+    }
+    delete t;
+}
+
+extern "C" int zkc_tree_add(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status) { return change(t, keys, values, n, status, true); }
+extern "C" int zkc_tree_update(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status) { return change(t, keys, values, n, status, false); }
+
+extern "C" int zkc_tree_root(zkc_tree* t, uint8_t root[32]) {
+    if (!t || !root) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_root: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    ZKC_LOCK(t->ctx);
+    if (t->broken) return zkc_fail(t->ctx, ZKC_ERR_HIP, "zkc_tree: the tree is broken by an earlier device failure");
+    return read_root(t, root);
+}
+
+extern "C" int zkc_tree_size(zkc_tree* t, size_t* leaves) {
+    if (!t || !leaves) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_size: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    *leaves = t->keys.size() / 32;
+    return ZKC_OK;
+}
+
+extern "C" int zkc_tree_stats(zkc_tree* t, double ms[2]) {
+    if (!t || !ms) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_stats: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    ms[0] = t->ms[0]; ms[1] = t->ms[1];
+    return ZKC_OK;
+}
+
+extern "C" int zkc_tree_get(zkc_tree* t, const void* keys, size_t n, void* values_out, int32_t* exists) {
+    if (!t || (n && (!keys || !values_out || !exists))) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_get: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->broken) return zkc_fail(t->ctx, ZKC_ERR_HIP, "zkc_tree: the tree is broken by an earlier device failure");
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t* key = (const uint8_t*)keys + 32 * i; uint8_t* v = (uint8_t*)values_out + 32 * i;
+        const uint32_t l = find(t, key);
+        exists[i] = l != 0;
+        if (l) memcpy(v, leaf_val(t, l), 32); else memset(v, 0, 32);
+    }
+    return ZKC_OK;
+}
+
+extern "C" int zkc_tree_gen_proof(zkc_tree* t, const void* keys, size_t n, uint8_t root[32], void* siblings, int32_t* depths, int32_t* exists) {
+    if (!t || !root || (n && (!keys || !exists))) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_gen_proof: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    zkc_ctx* ctx = t->ctx;
+    ZKC_LOCK(ctx);
+    if (t->broken) return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_tree: the tree is broken by an earlier device failure");
+    const size_t stride = (size_t)t->nLevels + 1;
+    if ((uint64_t)n * stride >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_gen_proof: too many keys for 32-bit slots");
+    std::vector<uint2> pairs;
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t* key = (const uint8_t*)keys + 32 * i;
+        const uint32_t l = find(t, key);
+        exists[i] = l != 0;
+        if (depths) depths[i] = l ? (int32_t)t->path.size() : 0;
+        if (l && siblings) sibling_pairs(t, key, i * stride, pairs);
+    }
+    int rc;
+    if ((rc = read_root(t, root))) return rc;
+    if (!siblings || !n) return ZKC_OK;
+    const size_t out_bytes = 32 * n * stride;
+    if ((rc = zkc_ensure(ctx, &t->d_out, &t->d_out_sz, out_bytes)) || (rc = stage(t, pairs.size() * sizeof(uint2) + 8))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(t->d_out, 0, out_bytes, ctx->stream));
+    if (!pairs.empty()) {
+        memcpy(t->h_stage, pairs.data(), pairs.size() * sizeof(uint2));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(t->d_stage, t->h_stage, pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((pairs.size() + 255) / 256)), dim3(256), 0, ctx->stream, t->d_val, (const uint2*)t->d_stage, pairs.size(),
+                           (uint32_t*)t->d_out);
+        ZKC_HIP_CHECK(ctx, hipGetLastError());
+    }
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(siblings, t->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
+}
+
+// zkc_census_inputs for n voters of two resident trees (include/zkcensus.h): the SIK and nullifier hashed on the GPU, availableWeight and both sibling lists from the trees.
+extern "C" int zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n, const uint8_t election_id[64], const void* address, const void* password, const void* signature,
+                                      const void* vote_weight, const void* vote_hash, void* inputs_out, void* d_inputs_out, uint8_t roots_out[64], int32_t* status) {
+    zkc_ctx* ctx = census ? census->ctx : sik ? sik->ctx : nullptr;
+    if (!census || !sik || census->ctx != sik->ctx || census->nLevels != sik->nLevels || census->nLevels < 3 || n == 0 || n > (1u << 24) || !election_id || !address ||
+        !password || !signature || !vote_weight || !vote_hash || (!inputs_out && !d_inputs_out) || !status)
+        return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: bad argument");
+    const uint8_t *addr = (const uint8_t*)address, *pw = (const uint8_t*)password, *sg = (const uint8_t*)signature, *vw = (const uint8_t*)vote_weight, *vh = (const uint8_t*)vote_hash;
+    for (size_t i = 0; i < 2 * n; i++)
+        if ((i < 2 && !below_r(election_id + 32 * i)) || !below_r(vh + 32 * i) || (i < n && (!below_r(addr + 32 * i) || !below_r(pw + 32 * i) || !below_r(sg + 32 * i) || !below_r(vw + 32 * i))))
+            return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: a value is not below the field order");
+    std::unique_lock<std::mutex> gc(census->mu, std::defer_lock), gs(sik->mu, std::defer_lock);
+    if (census == sik) gc.lock(); else std::lock(gc, gs);
+    ZKC_LOCK(ctx);
+    if (census->broken || sik->broken) return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_tree: the tree is broken by an earlier device failure");
+    const int nLevels = census->nLevels;
+    const size_t nIn = 12 + 2 * ((size_t)nLevels + 1);
+    if ((uint64_t)n * nIn >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: too many voters for 32-bit slots");
+    // the trees: per voter its stored weight and stored SIK, its two sibling lists (kept per voter until the SIK check says whether it goes out)
+    std::vector<uint8_t> avail(32 * n, 0), stored_sik(32 * n, 0);
+    std::vector<uint2> pc, ps; std::vector<size_t> pc_end(n), ps_end(n);
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t* key = addr + 32 * i;
+        status[i] = ZKC_TREE_OK;
+        const uint32_t lc = find(census, key);
+        if (!lc) status[i] = ZKC_TREE_NOT_IN_CENSUS;
+        else { memcpy(&avail[32 * i], leaf_val(census, lc), 32); sibling_pairs(census, key, i * nIn + 12, pc); }
+        const uint32_t ls = find(sik, key);
+        if (!ls) { if (!status[i]) status[i] = ZKC_TREE_NOT_IN_SIK; }
+        else { memcpy(&stored_sik[32 * i], leaf_val(sik, ls), 32); sibling_pairs(sik, key, i * nIn + 12 + (size_t)nLevels + 1, ps); }
+        pc_end[i] = pc.size(); ps_end[i] = ps.size();
+    }
+    // uploads: election id, address, password, signature, availableWeight, voteWeight, voteHash; then SIK and nullifier out; then the pairs (at most pc + ps + 12 n)
+    const size_t o_eid = 0, o_addr = 256, o_pw = o_addr + align256(32 * n), o_sig = o_pw + align256(32 * n), o_av = o_sig + align256(32 * n), o_vw = o_av + align256(32 * n),
+                 o_vh = o_vw + align256(32 * n), o_sik = o_vh + align256(64 * n), o_null = o_sik + align256(32 * n), o_pc = o_null + align256(32 * n),
+                 o_ps = o_pc + align256(8 * (pc.size() + 12 * n)), total = o_ps + 8 * ps.size() + 8;
+    int rc;
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if ((rc = stage(census, total))) return rc;
+    uint8_t* h = census->h_stage; uint8_t* d = (uint8_t*)census->d_stage;
+    memcpy(h + o_eid, election_id, 64); memcpy(h + o_addr, addr, 32 * n); memcpy(h + o_pw, pw, 32 * n); memcpy(h + o_sig, sg, 32 * n);
+    memcpy(h + o_av, avail.data(), 32 * n); memcpy(h + o_vw, vw, 32 * n); memcpy(h + o_vh, vh, 64 * n);
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d, h, o_sik, hipMemcpyHostToDevice, ctx->stream));
+    auto D = [&](size_t o) { return (uint32_t*)(d + o); };
+    const unsigned g64 = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(zkc_census_hash, dim3(g64), dim3(64), 0, ctx->stream, ctx->ptab, 1, D(o_addr), D(o_pw), D(o_sig), D(o_sik), n);        // census.circom:74-77
+    hipLaunchKernelGGL(zkc_census_hash, dim3(g64), dim3(64), 0, ctx->stream, ctx->ptab, 2, D(o_sig), D(o_pw), D(o_eid), D(o_null), n);        // :105-109
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h + o_sik, d + o_sik, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    // the voters that go out: their sibling pairs; the ones that do not: their twelve scalar slots zeroed again, from val[0] = 0 (their sibling slots stay zero)
+    uint2* hp = (uint2*)(h + o_pc); uint2* hq = (uint2*)(h + o_ps); size_t np = 0, nq = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!status[i] && memcmp(h + o_sik + 32 * i, &stored_sik[32 * i], 32) != 0) status[i] = ZKC_TREE_SIK_MISMATCH;
+        if (status[i]) { for (int k = 0; k < 12; k++) hp[np++] = make_uint2((uint32_t)(i * nIn + k), 0); continue; }
+        for (size_t j = i ? pc_end[i - 1] : 0; j < pc_end[i]; j++) hp[np++] = pc[j];
+        for (size_t j = i ? ps_end[i - 1] : 0; j < ps_end[i]; j++) hq[nq++] = ps[j];
+    }
+    if (np) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d + o_pc, h + o_pc, 8 * np, hipMemcpyHostToDevice, ctx->stream));
+    if (nq) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d + o_ps, h + o_ps, 8 * nq, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t* d_out = (uint32_t*)d_inputs_out;
+    if (!d_out) { if ((rc = zkc_ensure(ctx, &census->d_out, &census->d_out_sz, 32 * n * nIn))) return rc; d_out = (uint32_t*)census->d_out; }
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, 32 * n * nIn, ctx->stream));
+    const uint32_t* croot = census->d_val + 8 * (size_t)census->root; const uint32_t* sroot = sik->d_val + 8 * (size_t)sik->root;
+    hipLaunchKernelGGL(zkc_census_scalars, dim3((unsigned)((12 * n + 255) / 256)), dim3(256), 0, ctx->stream, D(o_eid), D(o_null), D(o_av), D(o_vh), sroot, croot,
+                       D(o_addr), D(o_pw), D(o_sig), D(o_vw), n, (int)nIn, d_out);
+    if (np) hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, census->d_val, (const uint2*)(d + o_pc), np, d_out);
+    if (nq) hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, sik->d_val, (const uint2*)(d + o_ps), nq, d_out);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    if (inputs_out) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(inputs_out, d_out, 32 * n * nIn, hipMemcpyDeviceToHost, ctx->stream));
+    if (roots_out) { ZKC_HIP_CHECK(ctx, hipMemcpyAsync(roots_out, croot, 32, hipMemcpyDeviceToHost, ctx->stream));
+                     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(roots_out + 32, sroot, 32, hipMemcpyDeviceToHost, ctx->stream)); }
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
+}

@@ -613,6 +613,40 @@ zkc_census_level(PoseidonTable tab, const uint32_t* __restrict__ left, const uin
     Fr x[2]; x[0] = load_std(val + 8 * (size_t)left[j]); x[1] = load_std(val + 8 * (size_t)right[j]);
     store_std(val + 8 * ((size_t)node0 + j), poseidon_trace29<3, 0>(x, 1u, tab, none, 0));
 }
+// ---- f1, the resident tree (csrc/zkc_tree.hip): val is indexed by node reference (0 = empty, leaves and inner nodes share the space); the host uploads the work of a batch
+// as lists whose references it has checked against the capacity of val: the changed leaves as (slot, key, value) and the dirty inner nodes as (node, left, right) triples,
+// grouped by depth, deepest first. ----
+// val[slot[i]] = H(key[i], value[i], 1)
+extern "C" __global__ void __launch_bounds__(64)
+zkc_tree_leaves(PoseidonTable tab, const uint32_t* __restrict__ slot, const uint32_t* __restrict__ key, const uint32_t* __restrict__ value, uint32_t count, uint32_t* val) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    Emit none{nullptr};
+    Fr x[3]; x[0] = load_std(key + 8 * (size_t)i); x[1] = load_std(value + 8 * (size_t)i); x[2] = Fr::one();
+    store_std(val + 8 * (size_t)slot[i], poseidon_trace29<4, 0>(x, 1u, tab, none, 0));
+}
+__device__ __forceinline__ void tree_node(const PoseidonTable& tab, const uint32_t* trip, uint32_t* val) {
+    Emit none{nullptr};
+    Fr x[2]; x[0] = load_std(val + 8 * (size_t)trip[1]); x[1] = load_std(val + 8 * (size_t)trip[2]);
+    store_std(val + 8 * (size_t)trip[0], poseidon_trace29<3, 0>(x, 1u, tab, none, 0));
+}
+// one wide depth, one lane per node: val[node] = H(val[left], val[right]) for the `count` triples at trip (the depth below is finished: launches go deepest first)
+extern "C" __global__ void __launch_bounds__(64)
+zkc_tree_level(PoseidonTable tab, const uint32_t* __restrict__ trip, uint32_t count, uint32_t* val) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    tree_node(tab, trip + 3 * (size_t)t, val);
+}
+// a run of consecutive narrow depths (at most one wave of nodes each) in ONE workgroup: depth k of the run is triples off[k] .. off[k + 1] of trip (k = 0 the deepest),
+// bottom-up with a barrier between depths.  Values pass only between the lanes of this workgroup, through that barrier; no other workgroup takes part.
+extern "C" __global__ void __launch_bounds__(64)
+zkc_tree_narrow(PoseidonTable tab, const uint32_t* __restrict__ trip, const uint32_t* __restrict__ off, uint32_t ndepths, uint32_t count, uint32_t* val) {
+    for (uint32_t k = 0; k < ndepths; k++) {
+        const uint32_t a = off[k], b = min(off[k + 1], count);
+        for (uint32_t t = a + threadIdx.x; t < b; t += blockDim.x) tree_node(tab, trip + 3 * (size_t)t, val);
+        __syncthreads();
+    }
+}
 // 32-byte copies val[ref] -> out[dst] for a list of (dst, ref) pairs: the sibling lists of every leaf, straight into the voters' input blocks
 extern "C" __global__ void __launch_bounds__(256)
 zkc_census_scatter(const uint32_t* __restrict__ val, const uint2* __restrict__ pairs, size_t count, uint32_t* __restrict__ out) {
