@@ -346,6 +346,27 @@ int  zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n, const uin
                             const void* vote_weight, const void* vote_hash, void* inputs_out, void* d_inputs_out, uint8_t roots_out[64], int32_t* status);
 int  zkc_tree_stats(zkc_tree* tree, double ms[2]);
 
+/* ---- f1: census proofs checked in batches (arbo CheckProof(hashFunc, key, value, root, siblings); internal/helpers.go), and the circuit's reading of the same proof
+ * (smtverifier.circom).  For n proofs: keys, values n x 32 B; siblings n x (nLevels + 1) x 32 B, zero-padded as zkc_smt_build and zkc_tree_gen_proof write them (proof i's
+ * sibling at level l in slot i (nLevels + 1) + l); roots: one 32-byte root shared by every proof, or n x 32 B when per_proof_roots != 0 -- any root, so a proof can be held
+ * against the root an election froze while the census grows on.  All 32-byte little-endian, standard form, host buffers.
+ * depth = 1 + the last level l < nLevels whose sibling is non-zero (0 when all are zero: a tree of one leaf); cur = H(key, value, 1); for l = depth - 1 down to 0:
+ * cur = H(sibling_l, cur) if bit l of the key (LSB first) is set, else H(cur, sibling_l); the proof is valid iff cur == root.
+ * status n x int32, one ZKC_SMT_* verdict per proof.  The field checks and the last-slot rule are made on the host before any hashing, in that order; the climbs run on the
+ * GPU, one lane per proof (the proofs grouped by depth; at most 64 proofs: one wave per proof), compacted to their depth before upload.  Returns ZKC_OK when it ran, whatever
+ * the verdicts; ZKC_ERR_BAD_ARG (before any device work): ctx NULL, nLevels outside 1..253, a NULL pointer with n > 0; n = 0 returns ZKC_OK and launches nothing.
+ * After a ZKC_ERR_HIP the statuses are undefined.
+ * zkc_smt_check_stats: ms of the context's last zkc_smt_check_proofs: ms[0] host (checks, depth sort, compaction; not the waits), ms[1] host-to-device copies, ms[2] kernels. ---- */
+enum {
+    ZKC_SMT_VALID = 0,
+    ZKC_SMT_ROOT_MISMATCH = 1,        /* the climb does not reach the root */
+    ZKC_SMT_NOT_BELOW_R = 2,          /* the key, the value, a sibling or the root is >= r */
+    ZKC_SMT_LAST_SIBLING = 3          /* slot nLevels is non-zero (smtlevins.circom:93, ZKC_W_ERR_LAST_SIBLING); arbo with MaxLevels = nLevels never makes one */
+};
+int zkc_smt_check_proofs(zkc_ctx* ctx, int nLevels, size_t n, const void* keys, const void* values, const void* siblings, const void* roots, int per_proof_roots,
+                         int32_t* status);
+int zkc_smt_check_stats(zkc_ctx* ctx, double ms[3]);
+
 /* ---- measurement: HIP-event timing per kernel category on zkc_ctx_stream (bit i of mask enables category i) ----
  * 0 witness, 1 buildABC mat-vec, 2 NTT+joinABC, 3 MSM digits+sort+offsets, 4 MSM bucket accumulation G1, 5 same G2,
  * 6 MSM heavy+reduce+final, 7 (no timing) bytes = (scalar, base) pairs x 96 B that entered the G1 MSMs after constant folding and

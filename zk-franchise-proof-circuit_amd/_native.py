@@ -74,6 +74,8 @@ def load():
     L.zkc_tree_gen_proof.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp, i32p, i32p]
     L.zkc_tree_census_inputs.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_char_p, i32p]
     L.zkc_tree_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    L.zkc_smt_check_proofs.argtypes = [vp, ctypes.c_int, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, i32p]
+    L.zkc_smt_check_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.zkc_profile_enable.argtypes = [vp, ctypes.c_uint32]
     L.zkc_ntt_dev.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.zkc_g1_mul_batch_dev.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_uint32, vp]

@@ -214,6 +214,29 @@ def smt_build(ctx, keys, values, nLevels=160, siblings=True):
     return int.from_bytes(root.raw, 'little'), (sib.raw if siblings else None), list(dep)
 
 
+SMT_VALID, SMT_ROOT_MISMATCH, SMT_NOT_BELOW_R, SMT_LAST_SIBLING = range(4)      # ZKC_SMT_*: the verdicts of check_proofs
+
+
+def check_proofs(ctx, keys, values, siblings, roots, nLevels=160):
+    """arbo CheckProof over a batch on the GPU (zkc_smt_check_proofs): one SMT_* verdict per proof.  keys, values: ints or packed 32-byte words; siblings: bytes,
+    n x (nLevels + 1) x 32, zero-padded as smt_build and CensusTree.gen_proof return them; roots: one int shared by every proof, or a list of n ints (one root per proof)."""
+    kb, vb = _le(keys), _le(values)
+    n = len(kb) // 32
+    per = isinstance(roots, (list, tuple))
+    rb = _le(roots) if per else _le([roots])
+    assert len(vb) == len(kb) and len(siblings) == 32 * n * (nLevels + 1) and (not per or len(rb) == len(kb)), 'keys, values, siblings and roots differ in length'
+    st = (ctypes.c_int32 * max(n, 1))()
+    ctx._check(ctx._lib.zkc_smt_check_proofs(ctx._h, int(nLevels), n, kb, vb, siblings if isinstance(siblings, bytes) else bytes(siblings), rb, int(per), st))
+    return list(st)[:n]
+
+
+def check_stats(ctx):
+    """(host ms, host-to-device ms, kernel ms) of the context's last check_proofs"""
+    ms = (ctypes.c_double * 3)()
+    ctx._check(ctx._lib.zkc_smt_check_stats(ctx._h, ms))
+    return ms[0], ms[1], ms[2]
+
+
 class CensusTree:
     """A census tree that grows in place (zkc_tree_*, csrc/zkc_tree.hip): arbo Add / Update / Get / GenProof on a resident tree, the trie on the host, the hashes on the
     GPU, each call rehashing only the nodes it changed.  Keys and values: lists of ints, or bytes of n x 32-byte little-endian words.  Statuses: ZKC_TREE_* (STATUS below).
@@ -287,6 +310,10 @@ class CensusTree:
         self.ctx._check(self._lib.zkc_tree_get(self._h, kb, n, ctypes.cast(out, ctypes.c_void_p), ex))
         raw = out.raw
         return [int.from_bytes(raw[32 * i:32 * i + 32], 'little') for i in range(n)], [bool(x) for x in ex]
+
+    def check_proofs(self, keys, values, siblings, root=None):
+        """check_proofs at this tree's nLevels against `root` (None: the tree's current root; one int; or a list of n ints); the tree is not touched"""
+        return check_proofs(self.ctx, keys, values, siblings, self.root if root is None else root, self.nLevels)
 
     def gen_proof(self, keys):
         """(root, siblings, depths, exists): siblings as bytes, n x (nLevels + 1) x 32, zero-padded like zkc_smt_build; the root they belong to"""

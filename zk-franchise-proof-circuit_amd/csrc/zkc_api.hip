@@ -221,6 +221,11 @@ extern "C" void zkc_ctx_destroy(zkc_ctx* ctx) {
     if (ctx->d_status3) (void)hipFree(ctx->d_status3);
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->d_prof_entries) (void)hipFree(ctx->d_prof_entries);
+    for (int k = 0; k < 2; k++) {
+        if (ctx->chk_h[k]) (void)hipHostFree(ctx->chk_h[k]);
+        if (ctx->chk_d[k]) (void)hipFree(ctx->chk_d[k]);
+        if (ctx->chk_ev[k]) (void)hipEventDestroy(ctx->chk_ev[k]);
+    }
     zkc_verify_ws_trim(ctx, 0);
     if (ctx->ev_vws_up) (void)hipEventDestroy(ctx->ev_vws_up);
     if (ctx->ev_vws_lines) (void)hipEventDestroy(ctx->ev_vws_lines);

@@ -647,6 +647,40 @@ zkc_tree_narrow(PoseidonTable tab, const uint32_t* __restrict__ trip, const uint
         __syncthreads();
     }
 }
+// ---- f1, proof checking (csrc/zkc_smt_check.hip, arbo CheckProof): one chunk of proofs that passed the host's field checks, grouped by depth.  Proof i of the chunk: key,
+// value (and root when root_stride is 1) at slot i, its siblings sib[off[i]] .. sib[off[i + 1]) (level 0 first, depth = their count), verdict into status[i]: 0 = the climb
+// reaches the root, 1 = it does not (ZKC_SMT_VALID / ZKC_SMT_ROOT_MISMATCH). ----
+__device__ __forceinline__ int32_t smt_climb(const PoseidonTable& tab, const uint32_t* key, const uint32_t* value, const uint32_t* root, const uint32_t* sib, int depth,
+                                             bool wave) {
+    Emit none{nullptr, false};
+    uint32_t ks[8]; load_raw(ks, key);
+    Fr x[3]; x[0] = load_std(key); x[1] = load_std(value); x[2] = Fr::one();
+    Fr cur = wave ? poseidon_wave29<4>(x, 1u, tab, none, 0) : poseidon_trace29<4, 0>(x, 1u, tab, none, 0);
+    for (int l = depth - 1; l >= 0; l--) {
+        const Fr s = load_std(sib + 8 * (size_t)l);
+        const bool right = bit_of(ks, l);
+        x[0] = right ? s : cur; x[1] = right ? cur : s;
+        cur = wave ? poseidon_wave29<3>(x, 1u, tab, none, 0) : poseidon_trace29<3, 0>(x, 1u, tab, none, 0);
+    }
+    return cur != load_std(root) ? 1 : 0;
+}
+// one lane per proof: the throughput form
+extern "C" __global__ void __launch_bounds__(64)
+zkc_smt_check(PoseidonTable tab, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ values, const uint32_t* __restrict__ roots, uint32_t root_stride,
+              const uint32_t* __restrict__ off, const uint32_t* __restrict__ sib, uint32_t count, int32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    status[i] = smt_climb(tab, keys + 8 * (size_t)i, values + 8 * (size_t)i, roots + 8 * (size_t)i * root_stride, sib + 8 * (size_t)off[i], (int)(off[i + 1] - off[i]), false);
+}
+// one wave per proof (poseidon_wave29 deals every round over the lanes): the latency form for small batches
+extern "C" __global__ void __launch_bounds__(64)
+zkc_smt_check_wave(PoseidonTable tab, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ values, const uint32_t* __restrict__ roots, uint32_t root_stride,
+                   const uint32_t* __restrict__ off, const uint32_t* __restrict__ sib, uint32_t count, int32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x;
+    if (i >= count) return;
+    const int32_t st = smt_climb(tab, keys + 8 * (size_t)i, values + 8 * (size_t)i, roots + 8 * (size_t)i * root_stride, sib + 8 * (size_t)off[i], (int)(off[i + 1] - off[i]), true);
+    if (threadIdx.x == 0) status[i] = st;
+}
 // 32-byte copies val[ref] -> out[dst] for a list of (dst, ref) pairs: the sibling lists of every leaf, straight into the voters' input blocks
 extern "C" __global__ void __launch_bounds__(256)
 zkc_census_scatter(const uint32_t* __restrict__ val, const uint2* __restrict__ pairs, size_t count, uint32_t* __restrict__ out) {
