@@ -316,13 +316,14 @@ int zkc_census_inputs(zkc_ctx* ctx, size_t n, int nLevels, const uint8_t electio
  * zkc_tree_root        : the current root (0 for an empty tree).  zkc_tree_size: the number of leaves.
  * zkc_tree_get         : values_out n x 32 B (zero where absent), exists n x int32 (1 / 0).
  * zkc_tree_gen_proof   : root (32 B) and, per key, siblings (n x (nLevels + 1) x 32 B, zero-padded as zkc_smt_build pads them), depths (levels above the leaf) and exists
- *                        (1 / 0; an absent key gets zero siblings and depth 0; non-membership proofs are not made).  The root is the one the siblings belong to.
- *                        siblings, depths may be NULL.
+ *                        (1 / 0; an absent key gets zero siblings and depth 0: its non-membership proof comes from zkc_tree_gen_absence_proof, zkcensus_delete.h).  The root is the one the
+ *                        siblings belong to.  siblings, depths may be NULL.
  * zkc_tree_census_inputs: zkc_census_inputs for n voters of two resident trees -- census: address -> available weight, sik: address -> SIK, same context, same nLevels --
  *                        without touching either tree: the SIK H(address, password, signature) and the nullifier are hashed on the GPU, availableWeight is the census
  *                        tree's stored value.  status n x int32: OK, NOT_IN_CENSUS, NOT_IN_SIK, SIK_MISMATCH (the SIK tree holds another value); a voter that is not OK
  *                        gets a zeroed block.  inputs_out / d_inputs_out / roots_out as for zkc_census_inputs (roots_out may be NULL).
- * zkc_tree_stats       : ms[0] = host trie time, ms[1] = device time (upload, kernels, synchronise) of the last add or update. ---- */
+ * zkc_tree_stats       : ms[0] = host trie time, ms[1] = device time (upload, kernels, synchronise) of the last add, update or delete
+ *                        (zkc_tree_delete, with the tree's other removal and absence-proof entry points, is declared in zkcensus_delete.h, included at the end). ---- */
 typedef struct zkc_tree zkc_tree;
 enum {
     ZKC_TREE_OK = 0,
@@ -356,12 +357,15 @@ int  zkc_tree_stats(zkc_tree* tree, double ms[2]);
  * GPU, one lane per proof (the proofs grouped by depth; at most 64 proofs: one wave per proof), compacted to their depth before upload.  Returns ZKC_OK when it ran, whatever
  * the verdicts; ZKC_ERR_BAD_ARG (before any device work): ctx NULL, nLevels outside 1..253, a NULL pointer with n > 0; n = 0 returns ZKC_OK and launches nothing.
  * After a ZKC_ERR_HIP the statuses are undefined.
- * zkc_smt_check_stats: ms of the context's last zkc_smt_check_proofs: ms[0] host (checks, depth sort, compaction; not the waits), ms[1] host-to-device copies, ms[2] kernels. ---- */
+ * zkc_smt_check_stats: ms of the context's last zkc_smt_check_proofs or zkc_smt_check_absence: ms[0] host (checks, depth sort, compaction; not the waits), ms[1]
+ * host-to-device copies, ms[2] kernels.  KEY_PRESENT and OFF_PATH are verdicts of zkc_smt_check_absence only (zkcensus_delete.h). ---- */
 enum {
     ZKC_SMT_VALID = 0,
     ZKC_SMT_ROOT_MISMATCH = 1,        /* the climb does not reach the root */
     ZKC_SMT_NOT_BELOW_R = 2,          /* the key, the value, a sibling or the root is >= r */
-    ZKC_SMT_LAST_SIBLING = 3          /* slot nLevels is non-zero (smtlevins.circom:93, ZKC_W_ERR_LAST_SIBLING); arbo with MaxLevels = nLevels never makes one */
+    ZKC_SMT_LAST_SIBLING = 3,         /* slot nLevels is non-zero (smtlevins.circom:93, ZKC_W_ERR_LAST_SIBLING); arbo with MaxLevels = nLevels never makes one */
+    ZKC_SMT_KEY_PRESENT = 4,          /* absence: !is_old0 and old_key == key (the circuit's areKeyEquals refuses it) */
+    ZKC_SMT_OFF_PATH = 5              /* absence: !is_old0 and old_key differs from key in one of the first depth path bits (a leaf there shares them) */
 };
 int zkc_smt_check_proofs(zkc_ctx* ctx, int nLevels, size_t n, const void* keys, const void* values, const void* siblings, const void* roots, int per_proof_roots,
                          int32_t* status);
@@ -384,4 +388,5 @@ int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_p
 #ifdef __cplusplus
 }
 #endif
+#include "zkcensus_delete.h"   /* census trees that shrink, and non-membership proofs */
 #endif

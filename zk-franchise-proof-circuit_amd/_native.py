@@ -68,6 +68,9 @@ def load():
     L.zkc_tree_free.argtypes = [vp]; L.zkc_tree_free.restype = None
     L.zkc_tree_add.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, i32p]
     L.zkc_tree_update.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, i32p]
+    L.zkc_tree_delete.argtypes = [vp, ctypes.c_char_p, sz, i32p]
+    L.zkc_tree_refs.argtypes = [vp, ctypes.POINTER(sz)]
+    L.zkc_tree_gen_absence_proof.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp, i32p, vp, vp, i32p, i32p]
     L.zkc_tree_root.argtypes = [vp, ctypes.c_char_p]
     L.zkc_tree_size.argtypes = [vp, ctypes.POINTER(sz)]
     L.zkc_tree_get.argtypes = [vp, ctypes.c_char_p, sz, vp, i32p]
@@ -75,6 +78,7 @@ def load():
     L.zkc_tree_census_inputs.argtypes = [vp, vp, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_char_p, i32p]
     L.zkc_tree_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.zkc_smt_check_proofs.argtypes = [vp, ctypes.c_int, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, i32p]
+    L.zkc_smt_check_absence.argtypes = [vp, ctypes.c_int, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, i32p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, i32p]
     L.zkc_smt_check_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     L.zkc_profile_enable.argtypes = [vp, ctypes.c_uint32]
     L.zkc_ntt_dev.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]

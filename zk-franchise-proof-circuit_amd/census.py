@@ -214,7 +214,7 @@ def smt_build(ctx, keys, values, nLevels=160, siblings=True):
     return int.from_bytes(root.raw, 'little'), (sib.raw if siblings else None), list(dep)
 
 
-SMT_VALID, SMT_ROOT_MISMATCH, SMT_NOT_BELOW_R, SMT_LAST_SIBLING = range(4)      # ZKC_SMT_*: the verdicts of check_proofs
+SMT_VALID, SMT_ROOT_MISMATCH, SMT_NOT_BELOW_R, SMT_LAST_SIBLING, SMT_KEY_PRESENT, SMT_OFF_PATH = range(6)   # ZKC_SMT_*: the verdicts of check_proofs / check_absence
 
 
 def check_proofs(ctx, keys, values, siblings, roots, nLevels=160):
@@ -230,15 +230,30 @@ def check_proofs(ctx, keys, values, siblings, roots, nLevels=160):
     return list(st)[:n]
 
 
+def check_absence(ctx, keys, old_keys, old_values, is_old0, siblings, roots, nLevels=160):
+    """Exclusion proofs checked in a batch on the GPU (zkc_smt_check_absence; circomlib SMTVerifier with fnc = 1): one SMT_* verdict per proof.  keys, old_keys,
+    old_values: ints or packed 32-byte words; is_old0: n ints (0 or 1); siblings and roots as for check_proofs -- the outputs of CensusTree.gen_absence_proof."""
+    kb, okb, ovb = _le(keys), _le(old_keys), _le(old_values)
+    n = len(kb) // 32
+    per = isinstance(roots, (list, tuple))
+    rb = _le(roots) if per else _le([roots])
+    assert len(okb) == len(ovb) == len(kb) and len(is_old0) == n and len(siblings) == 32 * n * (nLevels + 1) and (not per or len(rb) == len(kb)), \
+        'keys, old keys, old values, is_old0, siblings and roots differ in length'
+    o0 = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in is_old0])
+    st = (ctypes.c_int32 * max(n, 1))()
+    ctx._check(ctx._lib.zkc_smt_check_absence(ctx._h, int(nLevels), n, kb, okb, ovb, o0, siblings if isinstance(siblings, bytes) else bytes(siblings), rb, int(per), st))
+    return list(st)[:n]
+
+
 def check_stats(ctx):
-    """(host ms, host-to-device ms, kernel ms) of the context's last check_proofs"""
+    """(host ms, host-to-device ms, kernel ms) of the context's last check_proofs or check_absence"""
     ms = (ctypes.c_double * 3)()
     ctx._check(ctx._lib.zkc_smt_check_stats(ctx._h, ms))
     return ms[0], ms[1], ms[2]
 
 
 class CensusTree:
-    """A census tree that grows in place (zkc_tree_*, csrc/zkc_tree.hip): arbo Add / Update / Get / GenProof on a resident tree, the trie on the host, the hashes on the
+    """A census tree that grows and shrinks in place (zkc_tree_*, csrc/zkc_tree.hip): arbo Add / Update / Delete / Get / GenProof on a resident tree, the trie on the host, the hashes on the
     GPU, each call rehashing only the nodes it changed.  Keys and values: lists of ints, or bytes of n x 32-byte little-endian words.  Statuses: ZKC_TREE_* (STATUS below).
     Closed with its context at the latest (a context outlives its trees)."""
 
@@ -286,6 +301,19 @@ class CensusTree:
     def update(self, keys, values):
         return self._change(self._lib.zkc_tree_update, keys, values)
 
+    def delete(self, keys):
+        """arbo Delete: per-entry statuses (OK, KEY_ABSENT, NOT_BELOW_R); the rejected entries change nothing"""
+        kb = _le(keys); n = len(kb) // 32
+        st = (ctypes.c_int32 * n)()
+        self.ctx._check(self._lib.zkc_tree_delete(self._h, kb, n, st))
+        return list(st)
+
+    def refs(self):
+        """(live node references, allocated references): the second stays bounded while the census churns at constant size"""
+        out = (ctypes.c_size_t * 2)()
+        self.ctx._check(self._lib.zkc_tree_refs(self._h, out))
+        return out[0], out[1]
+
     @property
     def root(self):
         r = ctypes.create_string_buffer(32)
@@ -298,7 +326,7 @@ class CensusTree:
         return n.value
 
     def stats(self):
-        """(host trie ms, device ms) of the last add or update"""
+        """(host trie ms, device ms) of the last add, update or delete"""
         ms = (ctypes.c_double * 2)()
         self.ctx._check(self._lib.zkc_tree_stats(self._h, ms))
         return ms[0], ms[1]
@@ -322,6 +350,22 @@ class CensusTree:
         dep = (ctypes.c_int32 * n)(); ex = (ctypes.c_int32 * n)()
         self.ctx._check(self._lib.zkc_tree_gen_proof(self._h, kb, n, r, ctypes.cast(sib, ctypes.c_void_p), dep, ex))
         return int.from_bytes(r.raw, 'little'), sib.raw[:32 * n * (self.nLevels + 1)], list(dep), [bool(x) for x in ex]
+
+    def gen_absence_proof(self, keys):
+        """arbo GenProof for absent keys: (root, siblings, depths, old_keys, old_values, is_old0, statuses).  siblings as gen_proof lays them out; old_keys / old_values:
+        lists of ints (the leaf the key's path ran into, 0 when it ended at an empty child: is_old0 = 1).  A present key gets KEY_EXISTS and zeroed outputs."""
+        kb = _le(keys); n = len(kb) // 32
+        r = ctypes.create_string_buffer(32); sib = ctypes.create_string_buffer(32 * n * (self.nLevels + 1) + 1)
+        ok = ctypes.create_string_buffer(32 * n + 1); ov = ctypes.create_string_buffer(32 * n + 1)
+        dep = (ctypes.c_int32 * n)(); o0 = (ctypes.c_int32 * n)(); st = (ctypes.c_int32 * n)()
+        self.ctx._check(self._lib.zkc_tree_gen_absence_proof(self._h, kb, n, r, ctypes.cast(sib, ctypes.c_void_p), dep, ctypes.cast(ok, ctypes.c_void_p),
+                                                             ctypes.cast(ov, ctypes.c_void_p), o0, st))
+        words = lambda raw: [int.from_bytes(raw[32 * i:32 * i + 32], 'little') for i in range(n)]
+        return (int.from_bytes(r.raw, 'little'), sib.raw[:32 * n * (self.nLevels + 1)], list(dep), words(ok.raw), words(ov.raw), list(o0), list(st))
+
+    def check_absence(self, keys, old_keys, old_values, is_old0, siblings, root=None):
+        """check_absence at this tree's nLevels against `root` (None: the tree's current root; one int; or a list of n ints); the tree is not touched"""
+        return check_absence(self.ctx, keys, old_keys, old_values, is_old0, siblings, self.root if root is None else root, self.nLevels)
 
 
 def census_inputs_from_trees(ctx, census_tree, sik_tree, election_id, address, password, signature, vote_weight, vote_hash, d_out_ptr=None):

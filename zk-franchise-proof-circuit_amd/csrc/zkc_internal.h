@@ -64,7 +64,7 @@ struct zkc_ctx {
     enum { VWS_PTS = 0, VWS_RHO, VWS_IDX, VWS_GS, VWS_FOLD_TMP, VWS_FOLD_OUT, VWS_Q, VWS_LINES, VWS_TREE_A, VWS_TREE_B, VWS_BAD, VWS_N };
     void* vws[VWS_N] = {nullptr}; size_t vws_sz[VWS_N] = {0};
     hipEvent_t ev_vws_up = nullptr, ev_vws_lines = nullptr;       // the batch verifier's upload (second stream) -> its line kernel (third stream) -> the product tree (first): zkc_pairing_dev.hip
-    // zkc_smt_check_proofs (zkc_smt_check.hip): two upload buffers (pinned host, device) of chk_sz bytes each, used in turn by the chunks of a call; the event of each buffer's
+    // zkc_smt_check_proofs / zkc_smt_check_absence (zkc_smt_check.hip): two upload buffers (pinned host, device) of chk_sz bytes each, used in turn by the chunks of a call; the event of each buffer's
     // last upload; ms of the last call (host, H2D, kernels)
     void* chk_h[2] = {nullptr, nullptr}; void* chk_d[2] = {nullptr, nullptr}; size_t chk_sz = 0; hipEvent_t chk_ev[2] = {nullptr, nullptr};
     double chk_ms[3] = {0, 0, 0};

@@ -9,6 +9,10 @@
 //   compacts chunk k + 1 while the device copies and climbs chunk k.
 // - Batches of at most 64 proofs go to zkc_smt_check_wave instead: one wave per proof, every Poseidon dealt over the lanes.
 // - Verdicts come back in the sorted order and are written to the caller's order.
+//
+// zkc_smt_check_absence (exclusion proofs, circomlib SMTVerifier with fnc = 1) runs the same pipeline: per proof the old key and an is_old0 flag ride along, the host also
+// refuses a present key (old key == key) and an old key off the key's path, the proofs are sorted by (depth, is_old0) so the lanes of a wave mostly agree on the leaf hash,
+// and zkc_smt_check_absent / zkc_smt_check_absent_wave climb them.
 #include "zkc_internal.h"
 #include "zkc_field.h"
 #include <algorithm>
@@ -22,6 +26,10 @@ using namespace zkc;
 
 extern "C" __global__ void zkc_smt_check(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, int32_t*);
 extern "C" __global__ void zkc_smt_check_wave(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, int32_t*);
+extern "C" __global__ void zkc_smt_check_absent(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, const uint32_t*,
+                                                const uint32_t*, uint32_t, int32_t*);
+extern "C" __global__ void zkc_smt_check_absent_wave(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t,
+                                                     const uint32_t*, const uint32_t*, uint32_t, int32_t*);
 
 namespace {
 constexpr size_t CHUNK_BYTES = (size_t)128 << 20;      // one upload buffer (two are pinned)
@@ -32,6 +40,11 @@ constexpr int32_t PENDING = -1;
 inline bool below_r(const uint8_t* v) { uint32_t t[8]; memcpy(t, v, 32); return fp_std_lt_p<FrParams>(t); }
 inline bool is_zero(const uint8_t* v) { uint64_t w[4]; memcpy(w, v, 32); return (w[0] | w[1] | w[2] | w[3]) == 0; }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// a and b differ in one of their first d bits (LSB first: the path bits)
+inline bool prefix_differs(const uint8_t* a, const uint8_t* b, int d) {
+    for (int i = 0; i < d / 8; i++) if (a[i] != b[i]) return true;
+    return (d & 7) && ((a[d / 8] ^ b[d / 8]) & ((1u << (d & 7)) - 1));
+}
 using clk = std::chrono::steady_clock;
 inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
@@ -47,13 +60,23 @@ void parallel_for(size_t n, F fn) {
     for (auto& x : th) x.join();
 }
 
-// the layout of one chunk of c proofs holding S siblings in all: [keys c][values c][roots c, or 1 shared][off c + 1][siblings S], 32-byte words, each part 256-B aligned
+// the layout of one chunk of c proofs holding S siblings in all: [keys c][old keys c][values c][is_old0 c][roots c, or 1 shared][off c + 1][siblings S], 32-byte words
+// (is_old0, off: 4 bytes), each part 256-B aligned; the old keys and is_old0 are there for exclusion proofs only
 struct Layout {
-    size_t keys, vals, roots, off, sib, total;
-    Layout(size_t c, size_t S, bool per) {
-        keys = 0; vals = align256(32 * c); roots = vals + align256(32 * c); off = roots + align256(32 * (per ? c : 1));
-        sib = off + align256(4 * (c + 1)); total = sib + 32 * S;
+    size_t keys, okeys, vals, old0, roots, off, sib, total;
+    Layout(size_t c, size_t S, bool per, bool absent) {
+        const size_t ca = absent ? c : 0;
+        keys = 0; okeys = align256(32 * c); vals = okeys + align256(32 * ca); old0 = vals + align256(32 * c); roots = old0 + align256(4 * ca);
+        off = roots + align256(32 * (per ? c : 1)); sib = off + align256(4 * (c + 1)); total = sib + 32 * S;
     }
+};
+
+// one call's proofs: membership (old_keys, old0 null; values = the leaves' values) or exclusion (values = the old values)
+struct Batch {
+    int nLevels; size_t n; bool per;
+    const uint8_t *keys, *old_keys, *values, *siblings, *roots;
+    const int32_t* old0;
+    bool absent() const { return old_keys != nullptr; }
 };
 
 struct Events {                                        // timing events of one call, destroyed with it
@@ -62,43 +85,42 @@ struct Events {                                        // timing events of one c
 };
 }  // namespace
 
-extern "C" int zkc_smt_check_proofs(zkc_ctx* ctx, int nLevels, size_t n, const void* keys, const void* values, const void* siblings, const void* roots,
-                                    int per_proof_roots, int32_t* status) {
-    if (!ctx || nLevels < 1 || nLevels > 253 || (n && (!keys || !values || !siblings || !roots || !status)))
-        return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_proofs: bad argument");
-    if (n >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_proofs: more than 2^32 - 1 proofs in one call");
-    ZKC_LOCK(ctx);
-    ctx->chk_ms[0] = ctx->chk_ms[1] = ctx->chk_ms[2] = 0;
-    if (n == 0) return ZKC_OK;
+// the pipeline both kinds share (see the top of the file): host checks, sort, chunked compaction and upload, climbs; fills status[0 .. n), n > 0
+static int check_batch(zkc_ctx* ctx, const Batch& B, int32_t* status) {
     const clk::time_point t0 = clk::now();
-    const bool per = per_proof_roots != 0;
-    const uint8_t *K = (const uint8_t*)keys, *V = (const uint8_t*)values, *SB = (const uint8_t*)siblings, *R = (const uint8_t*)roots;
+    const int nLevels = B.nLevels; const size_t n = B.n; const bool per = B.per, absent = B.absent();
+    const uint8_t *K = B.keys, *OK = B.old_keys, *V = B.values, *SB = B.siblings, *R = B.roots;
     const size_t stride = 32 * ((size_t)nLevels + 1);
-    // pass 1: field checks, the last-slot rule, depths
+    // pass 1: field checks, the last-slot rule, (exclusion) present keys and old keys off the path, depths
     std::vector<uint8_t> depth(n, 0);
     parallel_for(n, [&](size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) {
             const uint8_t* s = SB + stride * i;
             int d = nLevels; while (d > 0 && is_zero(s + 32 * (d - 1))) d--;
-            bool ok = below_r(K + 32 * i) && below_r(V + 32 * i) && below_r(R + (per ? 32 * i : 0)) && below_r(s + 32 * (size_t)nLevels);
+            bool ok = below_r(K + 32 * i) && below_r(V + 32 * i) && (!absent || below_r(OK + 32 * i)) && below_r(R + (per ? 32 * i : 0)) && below_r(s + 32 * (size_t)nLevels);
             for (int l = 0; l < d && ok; l++) ok = below_r(s + 32 * l);
-            status[i] = !ok ? ZKC_SMT_NOT_BELOW_R : !is_zero(s + 32 * (size_t)nLevels) ? ZKC_SMT_LAST_SIBLING : PENDING;
+            int32_t st = !ok ? ZKC_SMT_NOT_BELOW_R : !is_zero(s + 32 * (size_t)nLevels) ? ZKC_SMT_LAST_SIBLING : PENDING;
+            if (absent && st == PENDING && !B.old0[i])
+                st = memcmp(OK + 32 * i, K + 32 * i, 32) == 0 ? ZKC_SMT_KEY_PRESENT : prefix_differs(OK + 32 * i, K + 32 * i, d) ? ZKC_SMT_OFF_PATH : PENDING;
+            status[i] = st;
             depth[i] = (uint8_t)d;
         }
     });
-    // the proofs that go to the device, counting-sorted by depth
-    std::vector<uint32_t> cnt(nLevels + 2, 0);
-    for (size_t i = 0; i < n; i++) if (status[i] == PENDING) cnt[depth[i] + 1]++;
-    for (int d = 0; d <= nLevels; d++) cnt[d + 1] += cnt[d];
-    const size_t m = cnt[nLevels + 1];
+    // the proofs that go to the device, counting-sorted by depth (exclusion: by depth, then is_old0 set first)
+    const int nb = absent ? 2 * (nLevels + 1) : nLevels + 1;
+    auto bucket = [&](size_t i) { return absent ? 2 * depth[i] + (B.old0[i] ? 0 : 1) : depth[i]; };
+    std::vector<uint32_t> cnt(nb + 1, 0);
+    for (size_t i = 0; i < n; i++) if (status[i] == PENDING) cnt[bucket(i) + 1]++;
+    for (int b = 0; b < nb; b++) cnt[b + 1] += cnt[b];
+    const size_t m = cnt[nb];
     std::vector<uint32_t> perm(m);
-    for (size_t i = 0; i < n; i++) if (status[i] == PENDING) perm[cnt[depth[i]]++] = (uint32_t)i;
+    for (size_t i = 0; i < n; i++) if (status[i] == PENDING) perm[cnt[bucket(i)]++] = (uint32_t)i;
     // chunks: [bound[k], bound[k + 1]) of perm
     std::vector<size_t> bound{0}; size_t need = 0;
     for (size_t a = 0; a < m;) {
         size_t b = a, S = 0;
-        while (b < m && b - a < CHUNK_PROOFS && (b == a || Layout(b + 1 - a, S + depth[perm[b]], per).total <= CHUNK_BYTES)) S += depth[perm[b++]];
-        need = std::max(need, Layout(b - a, S, per).total);
+        while (b < m && b - a < CHUNK_PROOFS && (b == a || Layout(b + 1 - a, S + depth[perm[b]], per, absent).total <= CHUNK_BYTES)) S += depth[perm[b++]];
+        need = std::max(need, Layout(b - a, S, per, absent).total);
         bound.push_back(b); a = b;
     }
     double host_ms = ms_since(t0);
@@ -135,16 +157,17 @@ extern "C" int zkc_smt_check_proofs(zkc_ctx* ctx, int nLevels, size_t n, const v
         uint8_t* h = (uint8_t*)ctx->chk_h[b];
         // offsets first (one pass), then every proof's words in parallel
         size_t S = 0;
-        { Layout L0(c, 0, per); uint32_t* off = (uint32_t*)(h + L0.off);
+        { Layout L0(c, 0, per, absent); uint32_t* off = (uint32_t*)(h + L0.off);
           for (size_t t = 0; t < c; t++) { off[t] = (uint32_t)S; S += depth[perm[a + t]]; }
           off[c] = (uint32_t)S; }
-        const Layout L(c, S, per);
+        const Layout L(c, S, per, absent);
         const uint32_t* off = (const uint32_t*)(h + L.off);
         if (!per) memcpy(h + L.roots, R, 32);
         parallel_for(c, [&](size_t lo, size_t hi) {
             for (size_t t = lo; t < hi; t++) {
                 const size_t i = perm[a + t];
                 memcpy(h + L.keys + 32 * t, K + 32 * i, 32); memcpy(h + L.vals + 32 * t, V + 32 * i, 32);
+                if (absent) { memcpy(h + L.okeys + 32 * t, OK + 32 * i, 32); ((uint32_t*)(h + L.old0))[t] = (uint32_t)B.old0[i]; }
                 if (per) memcpy(h + L.roots + 32 * t, R + 32 * i, 32);
                 memcpy(h + L.sib + 32 * (size_t)off[t], SB + stride * i, 32 * (size_t)(off[t + 1] - off[t]));
             }
@@ -156,7 +179,11 @@ extern "C" int zkc_smt_check_proofs(zkc_ctx* ctx, int nLevels, size_t n, const v
         ZKC_HIP_CHECK(ctx, hipEventRecord(ctx->chk_ev[b], ctx->stream));
         ZKC_HIP_CHECK(ctx, hipEventRecord(tev.ev[3 * k + 1], ctx->stream));
         auto P = [&](size_t o) { return (const uint32_t*)(d + o); };
-        if (wave)
+        const dim3 grid((unsigned)(wave ? c : (c + 63) / 64));
+        if (absent)
+            hipLaunchKernelGGL(wave ? zkc_smt_check_absent_wave : zkc_smt_check_absent, grid, dim3(64), 0, ctx->stream, ctx->ptab, P(L.keys), P(L.okeys), P(L.vals),
+                               P(L.old0), P(L.roots), (uint32_t)per, P(L.off), P(L.sib), (uint32_t)c, ctx->d_status + a);
+        else if (wave)
             hipLaunchKernelGGL(zkc_smt_check_wave, dim3((unsigned)c), dim3(64), 0, ctx->stream, ctx->ptab, P(L.keys), P(L.vals), P(L.roots), (uint32_t)per, P(L.off), P(L.sib),
                                (uint32_t)c, ctx->d_status + a);
         else
@@ -185,4 +212,31 @@ extern "C" int zkc_smt_check_stats(zkc_ctx* ctx, double ms[3]) {
     ZKC_LOCK(ctx);
     for (int k = 0; k < 3; k++) ms[k] = ctx->chk_ms[k];
     return ZKC_OK;
+}
+
+extern "C" int zkc_smt_check_proofs(zkc_ctx* ctx, int nLevels, size_t n, const void* keys, const void* values, const void* siblings, const void* roots,
+                                    int per_proof_roots, int32_t* status) {
+    if (!ctx || nLevels < 1 || nLevels > 253 || (n && (!keys || !values || !siblings || !roots || !status)))
+        return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_proofs: bad argument");
+    if (n >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_proofs: more than 2^32 - 1 proofs in one call");
+    ZKC_LOCK(ctx);
+    ctx->chk_ms[0] = ctx->chk_ms[1] = ctx->chk_ms[2] = 0;
+    if (n == 0) return ZKC_OK;
+    const Batch B{nLevels, n, per_proof_roots != 0, (const uint8_t*)keys, nullptr, (const uint8_t*)values, (const uint8_t*)siblings, (const uint8_t*)roots, nullptr};
+    return check_batch(ctx, B, status);
+}
+
+extern "C" int zkc_smt_check_absence(zkc_ctx* ctx, int nLevels, size_t n, const void* keys, const void* old_keys, const void* old_values, const int32_t* is_old0,
+                                     const void* siblings, const void* roots, int per_proof_roots, int32_t* status) {
+    if (!ctx || nLevels < 1 || nLevels > 253 || (n && (!keys || !old_keys || !old_values || !is_old0 || !siblings || !roots || !status)))
+        return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_absence: bad argument");
+    if (n >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_absence: more than 2^32 - 1 proofs in one call");
+    for (size_t i = 0; i < n; i++)
+        if (is_old0[i] != 0 && is_old0[i] != 1) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_smt_check_absence: an is_old0 entry is not 0 or 1");
+    ZKC_LOCK(ctx);
+    ctx->chk_ms[0] = ctx->chk_ms[1] = ctx->chk_ms[2] = 0;
+    if (n == 0) return ZKC_OK;
+    const Batch B{nLevels, n, per_proof_roots != 0, (const uint8_t*)keys, (const uint8_t*)old_keys, (const uint8_t*)old_values, (const uint8_t*)siblings,
+                  (const uint8_t*)roots, is_old0};
+    return check_batch(ctx, B, status);
 }

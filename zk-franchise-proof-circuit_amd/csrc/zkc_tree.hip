@@ -12,6 +12,11 @@
 // arbo semantics as zkc_smt_build pins them: leaf = H(key, value, 1), node = H(left, right), path bit i = bit i of the key (LSB first), an empty subtree is 0, a subtree
 // holding one leaf is that leaf's hash; inner nodes sit at depths 0 .. nLevels - 1.  Inserting walks from the root along the key bits: at an empty child the leaf goes
 // there; at a leaf with another key, a chain of inner nodes (one child each, except the last) runs down to the first bit where the two keys differ.
+//
+// Deleting (arbo Delete) keeps that canonical form: the leaf goes; when its sibling is a leaf, that leaf is lifted past its parent and every ancestor whose other child is
+// empty (those chain nodes are freed), up to the first ancestor with a non-empty other side or the root; when its sibling is an inner node, the parent stays as a one-child
+// chain node.  A leaf's hash does not depend on its depth, so a lifted leaf is not rehashed.  Freed references and leaf rows go on free lists that later inserts take from
+// first -- but only after the call's commit, so a reference freed and reused within one batch can never be hashed as the inner node it was.
 #include "zkc_internal.h"
 #include "zkc_field.h"
 #include <algorithm>
@@ -39,6 +44,8 @@ struct zkc_tree {
     std::vector<uint32_t> a{0}, b{0};
     std::vector<uint8_t> depth{0}, dirty{0};
     std::vector<uint8_t> keys, vals;         // per leaf index, 32 B each
+    std::vector<uint32_t> free_refs, free_rows;             // free references / leaf rows, taken first by new_ref / new_leaf
+    std::vector<uint32_t> freed_refs, freed_rows;           // freed by the current call: they join the free lists after its commit
     uint32_t root = 0;
     std::vector<uint32_t> dirty_nodes, dirty_leaves, path;
     // device
@@ -51,6 +58,7 @@ struct zkc_tree {
 
 namespace {
 constexpr uint8_t LEAF = 0xff;
+constexpr uint8_t FREED = 0xfe;               // depth of a reference freed by the current call (never a real depth: nLevels <= 253)
 constexpr uint32_t WAVE = 64;                // a depth with at most this many dirty nodes is narrow
 constexpr uint64_t MAX_REFS = 0xfffffff0ull;
 
@@ -65,13 +73,29 @@ inline uint8_t* leaf_val(zkc_tree* t, uint32_t r) { return t->vals.data() + 32 *
 inline uint32_t child(const zkc_tree* t, uint32_t node, int side) { return side ? t->b[node] : t->a[node]; }
 inline void set_child(zkc_tree* t, uint32_t node, int side, uint32_t r) { if (!node) t->root = r; else (side ? t->b[node] : t->a[node]) = r; }
 uint32_t new_ref(zkc_tree* t, uint32_t a, uint32_t b, uint8_t depth) {
+    if (!t->free_refs.empty()) {                 // a reference freed by an earlier call: not dirty, not in this call's lists
+        const uint32_t r = t->free_refs.back(); t->free_refs.pop_back();
+        t->a[r] = a; t->b[r] = b; t->depth[r] = depth; t->dirty[r] = 0;
+        return r;
+    }
     t->a.push_back(a); t->b.push_back(b); t->depth.push_back(depth); t->dirty.push_back(0);
     return (uint32_t)(t->a.size() - 1);
 }
 uint32_t new_leaf(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
-    const uint32_t li = (uint32_t)(t->keys.size() / 32);
-    t->keys.insert(t->keys.end(), key, key + 32); t->vals.insert(t->vals.end(), val, val + 32);
+    uint32_t li;
+    if (!t->free_rows.empty()) {
+        li = t->free_rows.back(); t->free_rows.pop_back();
+        memcpy(t->keys.data() + 32 * (size_t)li, key, 32); memcpy(t->vals.data() + 32 * (size_t)li, val, 32);
+    } else {
+        li = (uint32_t)(t->keys.size() / 32);
+        t->keys.insert(t->keys.end(), key, key + 32); t->vals.insert(t->vals.end(), val, val + 32);
+    }
     return new_ref(t, li, 0, LEAF);
+}
+void free_ref(zkc_tree* t, uint32_t r) {
+    if (t->depth[r] == LEAF) t->freed_rows.push_back(t->a[r]);
+    t->depth[r] = FREED; t->a[r] = t->b[r] = 0;
+    t->freed_refs.push_back(r);
 }
 inline void mark(zkc_tree* t, uint32_t r, std::vector<uint32_t>& list) { if (!t->dirty[r]) { t->dirty[r] = 1; list.push_back(r); } }
 void mark_path(zkc_tree* t) { for (uint32_t r : t->path) mark(t, r, t->dirty_nodes); }
@@ -116,6 +140,27 @@ int32_t add_one(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
         return ZKC_TREE_OK;
     }
 }
+// arbo Delete (see the top of the file): the leaf goes, a leaf left alone below its parent climbs past every ancestor whose other child is empty, the rest is marked dirty
+int32_t delete_one(zkc_tree* t, const uint8_t* key) {
+    if (!below_r(key)) return ZKC_TREE_NOT_BELOW_R;
+    const uint32_t l = find(t, key);
+    if (!l) return ZKC_TREE_KEY_ABSENT;
+    free_ref(t, l);
+    const std::vector<uint32_t>& p = t->path;
+    if (p.empty()) { t->root = 0; return ZKC_TREE_OK; }
+    int j = (int)p.size() - 1;                                 // p[j] is the leaf's parent, the leaf on side key bit j
+    const int s = key_bit(key, j);
+    set_child(t, p[j], s, 0);
+    const uint32_t other = child(t, p[j], !s);
+    if (other && t->depth[other] != LEAF) { for (int i = 0; i <= j; i++) mark(t, p[i], t->dirty_nodes); return ZKC_TREE_OK; }
+    // `other` (a leaf; 0 never occurs in the canonical form) replaces p[j] and every chain ancestor above it that holds nothing else
+    free_ref(t, p[j]);
+    while (j > 0 && child(t, p[j - 1], !key_bit(key, j - 1)) == 0) free_ref(t, p[--j]);
+    if (j == 0) { t->root = other; return ZKC_TREE_OK; }
+    set_child(t, p[j - 1], key_bit(key, j - 1), other);
+    for (int i = 0; i < j; i++) mark(t, p[i], t->dirty_nodes);
+    return ZKC_TREE_OK;
+}
 int32_t update_one(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
     if (!below_r(key) || !below_r(val)) return ZKC_TREE_NOT_BELOW_R;
     const uint32_t l = find(t, key);
@@ -158,9 +203,14 @@ int grow(zkc_tree* t, size_t need) {
 // hash what the entries of this call changed: the dirty leaves, then the dirty inner nodes deepest first.  Clears the dirty lists.
 int commit(zkc_tree* t, clk::time_point t0) {
     zkc_ctx* ctx = t->ctx;
-    const size_t K = t->dirty_leaves.size(), M = t->dirty_nodes.size();
     for (uint32_t r : t->dirty_leaves) t->dirty[r] = 0;
     for (uint32_t r : t->dirty_nodes) t->dirty[r] = 0;
+    if (!t->freed_refs.empty()) {                // references this call freed: nothing hashes them (they are reused only after this commit)
+        auto gone = [t](uint32_t r) { return t->depth[r] == FREED; };
+        t->dirty_leaves.erase(std::remove_if(t->dirty_leaves.begin(), t->dirty_leaves.end(), gone), t->dirty_leaves.end());
+        t->dirty_nodes.erase(std::remove_if(t->dirty_nodes.begin(), t->dirty_nodes.end(), gone), t->dirty_nodes.end());
+    }
+    const size_t K = t->dirty_leaves.size(), M = t->dirty_nodes.size();
     if (!K && !M) { t->ms[0] = ms_since(t0); t->ms[1] = 0; return ZKC_OK; }
     // the dirty nodes by depth, deepest first: position of depth d's first triple = pos[d]
     int D = 0; for (uint32_t r : t->dirty_nodes) D = std::max(D, t->depth[r] + 1);
@@ -212,8 +262,10 @@ int commit(zkc_tree* t, clk::time_point t0) {
     return ZKC_OK;
 }
 
-int change(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status, bool add) {
-    if (!t || (n && (!keys || !values || !status))) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_add / update: bad argument");
+enum Op { ADD, UPDATE, DELETE };
+int change(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status, Op op) {
+    const bool add = op == ADD;
+    if (!t || (n && (!keys || (op != DELETE && !values) || !status))) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_add / update / delete: bad argument");
     std::lock_guard<std::mutex> g(t->mu);
     zkc_ctx* ctx = t->ctx;
     ZKC_LOCK(ctx);
@@ -221,10 +273,13 @@ int change(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t*
     if (add && t->a.size() + (uint64_t)n * (t->nLevels + 2) > MAX_REFS) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_add: the tree would exceed 2^32 nodes");
     const clk::time_point t0 = clk::now();
     const uint8_t* k = (const uint8_t*)keys; const uint8_t* v = (const uint8_t*)values;
-    for (size_t i = 0; i < n; i++) status[i] = add ? add_one(t, k + 32 * i, v + 32 * i) : update_one(t, k + 32 * i, v + 32 * i);
+    for (size_t i = 0; i < n; i++)
+        status[i] = op == ADD ? add_one(t, k + 32 * i, v + 32 * i) : op == UPDATE ? update_one(t, k + 32 * i, v + 32 * i) : delete_one(t, k + 32 * i);
     const int rc = commit(t, t0);
-    if (rc) t->broken = true;
-    return rc;
+    if (rc) { t->broken = true; return rc; }
+    t->free_refs.insert(t->free_refs.end(), t->freed_refs.begin(), t->freed_refs.end()); t->freed_refs.clear();
+    t->free_rows.insert(t->free_rows.end(), t->freed_rows.begin(), t->freed_rows.end()); t->freed_rows.clear();
+    return ZKC_OK;
 }
 int read_root(zkc_tree* t, uint8_t root[32]) {
     zkc_ctx* ctx = t->ctx;
@@ -240,6 +295,23 @@ void sibling_pairs(const zkc_tree* t, const uint8_t* key, size_t base, std::vect
         const uint32_t s = child(t, t->path[l], !key_bit(key, (int)l));
         if (s) out.push_back(make_uint2((uint32_t)(base + l), s));
     }
+}
+// the zero-padded sibling lists of a gen_proof call: `words` 32-byte words, the (dst, ref) pairs' values from val scattered in on the device, copied to `siblings`
+int write_siblings(zkc_tree* t, const std::vector<uint2>& pairs, size_t words, void* siblings) {
+    zkc_ctx* ctx = t->ctx; int rc;
+    const size_t out_bytes = 32 * words;
+    if ((rc = zkc_ensure(ctx, &t->d_out, &t->d_out_sz, out_bytes)) || (rc = stage(t, pairs.size() * sizeof(uint2) + 8))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(t->d_out, 0, out_bytes, ctx->stream));
+    if (!pairs.empty()) {
+        memcpy(t->h_stage, pairs.data(), pairs.size() * sizeof(uint2));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(t->d_stage, t->h_stage, pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((pairs.size() + 255) / 256)), dim3(256), 0, ctx->stream, t->d_val, (const uint2*)t->d_stage, pairs.size(),
+                           (uint32_t*)t->d_out);
+        ZKC_HIP_CHECK(ctx, hipGetLastError());
+    }
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(siblings, t->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
 }
 }  // namespace
 
@@ -275,8 +347,9 @@ extern "C" void zkc_tree_free(zkc_tree* t) {
     delete t;
 }
 
-extern "C" int zkc_tree_add(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status) { return change(t, keys, values, n, status, true); }
-extern "C" int zkc_tree_update(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status) { return change(t, keys, values, n, status, false); }
+extern "C" int zkc_tree_add(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status) { return change(t, keys, values, n, status, ADD); }
+extern "C" int zkc_tree_update(zkc_tree* t, const void* keys, const void* values, size_t n, int32_t* status) { return change(t, keys, values, n, status, UPDATE); }
+extern "C" int zkc_tree_delete(zkc_tree* t, const void* keys, size_t n, int32_t* status) { return change(t, keys, nullptr, n, status, DELETE); }
 
 extern "C" int zkc_tree_root(zkc_tree* t, uint8_t root[32]) {
     if (!t || !root) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_root: bad argument");
@@ -289,7 +362,14 @@ extern "C" int zkc_tree_root(zkc_tree* t, uint8_t root[32]) {
 extern "C" int zkc_tree_size(zkc_tree* t, size_t* leaves) {
     if (!t || !leaves) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_size: bad argument");
     std::lock_guard<std::mutex> g(t->mu);
-    *leaves = t->keys.size() / 32;
+    *leaves = t->keys.size() / 32 - t->free_rows.size();
+    return ZKC_OK;
+}
+
+extern "C" int zkc_tree_refs(zkc_tree* t, size_t out[2]) {
+    if (!t || !out) return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_refs: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    out[0] = t->a.size() - 1 - t->free_refs.size(); out[1] = t->a.size();
     return ZKC_OK;
 }
 
@@ -332,19 +412,41 @@ extern "C" int zkc_tree_gen_proof(zkc_tree* t, const void* keys, size_t n, uint8
     int rc;
     if ((rc = read_root(t, root))) return rc;
     if (!siblings || !n) return ZKC_OK;
-    const size_t out_bytes = 32 * n * stride;
-    if ((rc = zkc_ensure(ctx, &t->d_out, &t->d_out_sz, out_bytes)) || (rc = stage(t, pairs.size() * sizeof(uint2) + 8))) return rc;
-    ZKC_HIP_CHECK(ctx, hipMemsetAsync(t->d_out, 0, out_bytes, ctx->stream));
-    if (!pairs.empty()) {
-        memcpy(t->h_stage, pairs.data(), pairs.size() * sizeof(uint2));
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(t->d_stage, t->h_stage, pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((pairs.size() + 255) / 256)), dim3(256), 0, ctx->stream, t->d_val, (const uint2*)t->d_stage, pairs.size(),
-                           (uint32_t*)t->d_out);
-        ZKC_HIP_CHECK(ctx, hipGetLastError());
+    return write_siblings(t, pairs, n * stride, siblings);
+}
+
+// arbo GenProof for absent keys (circomlib SMTVerifier, fnc = 1): where the key's path ends -- an empty child (is_old0 = 1) or a leaf of another key (is_old0 = 0, its
+// key and value) -- and the siblings of that path, laid out as zkc_tree_gen_proof lays them out
+extern "C" int zkc_tree_gen_absence_proof(zkc_tree* t, const void* keys, size_t n, uint8_t root[32], void* siblings, int32_t* depths, void* old_keys, void* old_values,
+                                          int32_t* is_old0, int32_t* status) {
+    if (!t || !root || (n && (!keys || !old_keys || !old_values || !is_old0 || !status)))
+        return zkc_fail(t ? t->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_gen_absence_proof: bad argument");
+    std::lock_guard<std::mutex> g(t->mu);
+    zkc_ctx* ctx = t->ctx;
+    ZKC_LOCK(ctx);
+    if (t->broken) return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_tree: the tree is broken by an earlier device failure");
+    const size_t stride = (size_t)t->nLevels + 1;
+    if ((uint64_t)n * stride >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_gen_absence_proof: too many keys for 32-bit slots");
+    std::vector<uint2> pairs;
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t* key = (const uint8_t*)keys + 32 * i;
+        uint8_t* ok = (uint8_t*)old_keys + 32 * i; uint8_t* ov = (uint8_t*)old_values + 32 * i;
+        memset(ok, 0, 32); memset(ov, 0, 32); is_old0[i] = 0;
+        if (depths) depths[i] = 0;
+        if (!below_r(key)) { status[i] = ZKC_TREE_NOT_BELOW_R; continue; }
+        t->path.clear();
+        uint32_t r = t->root;
+        for (int d = 0; r && t->depth[r] != LEAF; d++) { t->path.push_back(r); r = child(t, r, key_bit(key, d)); }
+        if (r && memcmp(leaf_key(t, r), key, 32) == 0) { status[i] = ZKC_TREE_KEY_EXISTS; continue; }
+        status[i] = ZKC_TREE_OK;
+        if (r) { memcpy(ok, leaf_key(t, r), 32); memcpy(ov, leaf_val(t, r), 32); } else is_old0[i] = 1;
+        if (depths) depths[i] = (int32_t)t->path.size();
+        if (siblings) sibling_pairs(t, key, i * stride, pairs);
     }
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(siblings, t->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return ZKC_OK;
+    int rc;
+    if ((rc = read_root(t, root))) return rc;
+    if (!siblings || !n) return ZKC_OK;
+    return write_siblings(t, pairs, n * stride, siblings);
 }
 
 // zkc_census_inputs for n voters of two resident trees (include/zkcensus.h): the SIK and nullifier hashed on the GPU, availableWeight and both sibling lists from the trees.

@@ -650,17 +650,34 @@ zkc_tree_narrow(PoseidonTable tab, const uint32_t* __restrict__ trip, const uint
 // ---- f1, proof checking (csrc/zkc_smt_check.hip, arbo CheckProof): one chunk of proofs that passed the host's field checks, grouped by depth.  Proof i of the chunk: key,
 // value (and root when root_stride is 1) at slot i, its siblings sib[off[i]] .. sib[off[i + 1]) (level 0 first, depth = their count), verdict into status[i]: 0 = the climb
 // reaches the root, 1 = it does not (ZKC_SMT_VALID / ZKC_SMT_ROOT_MISMATCH). ----
-__device__ __forceinline__ int32_t smt_climb(const PoseidonTable& tab, const uint32_t* key, const uint32_t* value, const uint32_t* root, const uint32_t* sib, int depth,
-                                             bool wave) {
+// ABSENT (exclusion, circomlib SMTVerifier fnc = 1): the climb starts from 0 when old0 is set, else from the leaf H(old_key, value, 1) the key's path ran into; the path bits
+// are always the key's.  Membership (ABSENT = false) starts from H(key, value, 1).
+template <bool ABSENT>
+__device__ __forceinline__ int32_t smt_climb(const PoseidonTable& tab, const uint32_t* key, const uint32_t* old_key, const uint32_t* value, bool old0, const uint32_t* root,
+                                             const uint32_t* sib, int depth, bool wave) {
     Emit none{nullptr, false};
-    uint32_t ks[8]; load_raw(ks, key);
-    Fr x[3]; x[0] = load_std(key); x[1] = load_std(value); x[2] = Fr::one();
-    Fr cur = wave ? poseidon_wave29<4>(x, 1u, tab, none, 0) : poseidon_trace29<4, 0>(x, 1u, tab, none, 0);
+    uint32_t ks[8]; if (!ABSENT) load_raw(ks, key);
+    // ABSENT, one wave: word j of the key and of the root in lane j, so neither their pointers nor their words stay in SGPRs across the climb
+    const uint32_t kw = ABSENT && wave ? key[threadIdx.x & 7] : 0, rw = ABSENT && wave ? root[threadIdx.x & 7] : 0;
+    Fr x[3]; Fr cur;
+    if (ABSENT && old0) {
+        cur = Fr::zero();
+    } else {
+        x[0] = load_std(ABSENT ? old_key : key); x[1] = load_std(value); x[2] = Fr::one();
+        cur = wave ? poseidon_wave29<4>(x, 1u, tab, none, 0) : poseidon_trace29<4, 0>(x, 1u, tab, none, 0);
+    }
     for (int l = depth - 1; l >= 0; l--) {
         const Fr s = load_std(sib + 8 * (size_t)l);
-        const bool right = bit_of(ks, l);
+        const uint32_t w = !ABSENT ? 0 : wave ? __builtin_amdgcn_readlane(kw, l >> 5) : key[l >> 5];     // ABSENT: one key word per level, not 8 held across the climb
+        const bool right = ABSENT ? (w >> (l & 31)) & 1 : bit_of(ks, l);
         x[0] = right ? s : cur; x[1] = right ? cur : s;
         cur = wave ? poseidon_wave29<3>(x, 1u, tab, none, 0) : poseidon_trace29<3, 0>(x, 1u, tab, none, 0);
+    }
+    if (ABSENT && wave) {                                                   // the root is below r (host check): standard words compare as the field elements do
+        uint32_t cs[8]; fp_to_std<FrParams>(cs, cur);
+        bool eq = true;
+        for (int k = 0; k < 8; k++) eq &= cs[k] == __builtin_amdgcn_readlane(rw, k);
+        return eq ? 0 : 1;
     }
     return cur != load_std(root) ? 1 : 0;
 }
@@ -670,7 +687,8 @@ zkc_smt_check(PoseidonTable tab, const uint32_t* __restrict__ keys, const uint32
               const uint32_t* __restrict__ off, const uint32_t* __restrict__ sib, uint32_t count, int32_t* __restrict__ status) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    status[i] = smt_climb(tab, keys + 8 * (size_t)i, values + 8 * (size_t)i, roots + 8 * (size_t)i * root_stride, sib + 8 * (size_t)off[i], (int)(off[i + 1] - off[i]), false);
+    status[i] = smt_climb<false>(tab, keys + 8 * (size_t)i, nullptr, values + 8 * (size_t)i, false, roots + 8 * (size_t)i * root_stride, sib + 8 * (size_t)off[i],
+                              (int)(off[i + 1] - off[i]), false);
 }
 // one wave per proof (poseidon_wave29 deals every round over the lanes): the latency form for small batches
 extern "C" __global__ void __launch_bounds__(64)
@@ -678,7 +696,31 @@ zkc_smt_check_wave(PoseidonTable tab, const uint32_t* __restrict__ keys, const u
                    const uint32_t* __restrict__ off, const uint32_t* __restrict__ sib, uint32_t count, int32_t* __restrict__ status) {
     const uint32_t i = blockIdx.x;
     if (i >= count) return;
-    const int32_t st = smt_climb(tab, keys + 8 * (size_t)i, values + 8 * (size_t)i, roots + 8 * (size_t)i * root_stride, sib + 8 * (size_t)off[i], (int)(off[i + 1] - off[i]), true);
+    const int32_t st = smt_climb<false>(tab, keys + 8 * (size_t)i, nullptr, values + 8 * (size_t)i, false, roots + 8 * (size_t)i * root_stride, sib + 8 * (size_t)off[i],
+                                       (int)(off[i + 1] - off[i]), true);
+    if (threadIdx.x == 0) status[i] = st;
+}
+// ---- f1, exclusion proofs (csrc/zkc_smt_check.hip, zkc_smt_check_absence): the chunk layout of zkc_smt_check plus, per proof, the old key (slot i of old_keys) and its
+// is_old0 flag; values holds the old values.  The host has already refused present keys and old keys off the key's path. ----
+// one lane per proof: the throughput form
+extern "C" __global__ void __launch_bounds__(64)
+zkc_smt_check_absent(PoseidonTable tab, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ old_keys, const uint32_t* __restrict__ values,
+                     const uint32_t* __restrict__ old0, const uint32_t* __restrict__ roots, uint32_t root_stride, const uint32_t* __restrict__ off,
+                     const uint32_t* __restrict__ sib, uint32_t count, int32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    status[i] = smt_climb<true>(tab, keys + 8 * (size_t)i, old_keys + 8 * (size_t)i, values + 8 * (size_t)i, old0[i] != 0, roots + 8 * (size_t)i * root_stride,
+                                sib + 8 * (size_t)off[i], (int)(off[i + 1] - off[i]), false);
+}
+// one wave per proof: the latency form for small batches (old0 is uniform over the wave, so the leaf hash is taken or skipped by the whole wave)
+extern "C" __global__ void __launch_bounds__(64)
+zkc_smt_check_absent_wave(PoseidonTable tab, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ old_keys, const uint32_t* __restrict__ values,
+                          const uint32_t* __restrict__ old0, const uint32_t* __restrict__ roots, uint32_t root_stride, const uint32_t* __restrict__ off,
+                          const uint32_t* __restrict__ sib, uint32_t count, int32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x;
+    if (i >= count) return;
+    const int32_t st = smt_climb<true>(tab, keys + 8 * (size_t)i, old_keys + 8 * (size_t)i, values + 8 * (size_t)i, old0[i] != 0, roots + 8 * (size_t)i * root_stride,
+                                       sib + 8 * (size_t)off[i], (int)(off[i + 1] - off[i]), true);
     if (threadIdx.x == 0) status[i] = st;
 }
 // 32-byte copies val[ref] -> out[dst] for a list of (dst, ref) pairs: the sibling lists of every leaf, straight into the voters' input blocks
