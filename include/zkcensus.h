@@ -323,7 +323,8 @@ int zkc_census_inputs(zkc_ctx* ctx, size_t n, int nLevels, const uint8_t electio
  *                        tree's stored value.  status n x int32: OK, NOT_IN_CENSUS, NOT_IN_SIK, SIK_MISMATCH (the SIK tree holds another value); a voter that is not OK
  *                        gets a zeroed block.  inputs_out / d_inputs_out / roots_out as for zkc_census_inputs (roots_out may be NULL).
  * zkc_tree_stats       : ms[0] = host trie time, ms[1] = device time (upload, kernels, synchronise) of the last add, update or delete
- *                        (zkc_tree_delete, with the tree's other removal and absence-proof entry points, is declared in zkcensus_delete.h, included at the end). ---- */
+ *                        (zkc_tree_delete, with the tree's other removal and absence-proof entry points, is declared in zkcensus_delete.h, and the snapshots of a tree
+ *                        in zkcensus_snapshot.h, both included at the end). ---- */
 typedef struct zkc_tree zkc_tree;
 enum {
     ZKC_TREE_OK = 0,
@@ -389,4 +390,5 @@ int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_p
 }
 #endif
 #include "zkcensus_delete.h"   /* census trees that shrink, and non-membership proofs */
+#include "zkcensus_snapshot.h" /* frozen views of a census tree */
 #endif

@@ -70,6 +70,8 @@ def load():
     L.zkc_tree_update.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz, i32p]
     L.zkc_tree_delete.argtypes = [vp, ctypes.c_char_p, sz, i32p]
     L.zkc_tree_refs.argtypes = [vp, ctypes.POINTER(sz)]
+    L.zkc_tree_snapshot.argtypes = [vp, ctypes.POINTER(vp)]
+    L.zkc_tree_snapshot_count.argtypes = [vp, ctypes.POINTER(sz)]
     L.zkc_tree_gen_absence_proof.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, vp, i32p, vp, vp, i32p, i32p]
     L.zkc_tree_root.argtypes = [vp, ctypes.c_char_p]
     L.zkc_tree_size.argtypes = [vp, ctypes.POINTER(sz)]

@@ -255,14 +255,17 @@ def check_stats(ctx):
 class CensusTree:
     """A census tree that grows and shrinks in place (zkc_tree_*, csrc/zkc_tree.hip): arbo Add / Update / Delete / Get / GenProof on a resident tree, the trie on the host, the hashes on the
     GPU, each call rehashing only the nodes it changed.  Keys and values: lists of ints, or bytes of n x 32-byte little-endian words.  Statuses: ZKC_TREE_* (STATUS below).
-    Closed with its context at the latest (a context outlives its trees)."""
+    Closed with its context at the latest (a context outlives its trees).  snapshot() gives a read-only view of the tree as it is now, which later changes leave alone."""
 
     OK, KEY_EXISTS, KEY_ABSENT, COLLISION, NOT_BELOW_R, NOT_IN_CENSUS, NOT_IN_SIK, SIK_MISMATCH = range(8)
 
-    def __init__(self, ctx, nLevels=160):
+    def __init__(self, ctx, nLevels=160, _handle=None):
         self.ctx, self.nLevels, self._lib = ctx, nLevels, ctx._lib
-        h = ctypes.c_void_p()
-        ctx._check(self._lib.zkc_tree_create(ctx._h, int(nLevels), ctypes.byref(h)))
+        self._snapshot = _handle is not None
+        h = _handle
+        if h is None:
+            h = ctypes.c_void_p()
+            ctx._check(self._lib.zkc_tree_create(ctx._h, int(nLevels), ctypes.byref(h)))
         self._h = h
         ctx._keys.append(self)            # the context closes what lives on it before itself
 
@@ -307,6 +310,24 @@ class CensusTree:
         st = (ctypes.c_int32 * n)()
         self.ctx._check(self._lib.zkc_tree_delete(self._h, kb, n, st))
         return list(st)
+
+    def snapshot(self):
+        """arbo Tree.Snapshot: a read-only CensusTree of this tree's current version (zkc_tree_snapshot).  It shares every node with this tree, answers root / len / get /
+        gen_proof / gen_absence_proof / census_inputs_from_trees for that version while this tree goes on changing, and refuses changes.  Close it (or use it as a context
+        manager) to release what only it still holds; it stays usable after this tree is closed."""
+        h = ctypes.c_void_p()
+        self.ctx._check(self._lib.zkc_tree_snapshot(self._h, ctypes.byref(h)))
+        return CensusTree(self.ctx, self.nLevels, _handle=h)
+
+    @property
+    def is_snapshot(self):
+        return self._snapshot
+
+    def snapshot_count(self):
+        """the number of live snapshots of this tree (the live tree and its snapshots count the same ones)"""
+        n = ctypes.c_size_t()
+        self.ctx._check(self._lib.zkc_tree_snapshot_count(self._h, ctypes.byref(n)))
+        return n.value
 
     def refs(self):
         """(live node references, allocated references): the second stays bounded while the census churns at constant size"""
@@ -369,7 +390,8 @@ class CensusTree:
 
 
 def census_inputs_from_trees(ctx, census_tree, sik_tree, election_id, address, password, signature, vote_weight, vote_hash, d_out_ptr=None):
-    """census_inputs for n voters of two resident trees (zkc_tree_census_inputs): census_tree maps address -> available weight, sik_tree address -> SIK.  Returns
+    """census_inputs for n voters of two resident trees (zkc_tree_census_inputs): census_tree maps address -> available weight, sik_tree address -> SIK; either may be a
+    snapshot (CensusTree.snapshot), whose frozen root and siblings the blocks then carry.  Returns
     (flat bytes, census root, sik root, statuses); a voter whose status is not CensusTree.OK gets a zeroed block.  vote_hash: pairs."""
     address = _le(address); n = len(address) // 32
     nIn = 12 + 2 * (census_tree.nLevels + 1)
