@@ -103,7 +103,10 @@ int  zkc_zkey_sha256(const zkc_zkey* zk, uint8_t out[32]);      /* of the .zkey 
 int  zkc_zkey_fingerprint(const void* zkey_bytes, size_t len, uint8_t out[32]);
 
 /* ---- a2-a7: Groth16 prove (replaces snarkjs groth16.prove / rapidsnark groth16_prover internals).
- * wtns   : nWitness x 32 B standard form (the payload of .wtns section 2), host (zkc_prove) or device (zkc_prove_dev)
+ * wtns   : nWitness x 32 B standard form (the payload of .wtns section 2), host (zkc_prove) or device (zkc_prove_dev), every value below r.
+ *          A host witness with a value >= r is refused before any device work: ZKC_ERR_FORMAT, the text names the first such wire (zkc_prove,
+ *          zkc_service_prove / zkc_service_submit_prove; groth16_prover returns ZKC_ERR_GENERIC with that text, rapidsnark's PROVER_ERROR).  A device
+ *          witness (zkc_prove_dev, zkc_prove_batch_dev) is not checked: a value >= 2^254 there gives a proof that does not verify.
  * r, s   : the two blinding scalars, 32 B LE, < field order.  snarkjs/rapidsnark draw them at random; they are explicit
  *          here so that identical (zkey, wtns, r, s) gives identical bytes on every backend (SURVEY.md hard part 3).
  *          zkc_random_scalars fills n x 32 B with scalars uniform in [0, r) from the OS generator (rejection sampling).
@@ -118,7 +121,8 @@ int zkc_prove_dev(zkc_zkey* zk, const void* d_wtns, uint32_t nWitness, const uin
  * proofs B x 256 B, publics B x nPublic x 32 B (may be NULL).  Up to ZKC_INFLIGHT (default 64 for a census key, 96 otherwise) proofs share one MSM
  * pipeline pass and the passes of a call rotate over ZKC_LANES pipeline lanes (default 4 for a census key; zkc_zkey_pass_info); the work space belongs to the
  * CONTEXT, is shared by its keys and grows with what calls put in flight (a single-proof caller touches one lane with room for four proofs, 0.6 GB at nLevels 160; a
- * 1 024-voter call four lanes of 64, 37 GB).  Mirrors what a rapidsnark / snarkjs caller would loop over (zk_census_test.go:89 per voter). */
+ * 1 024-voter call four lanes of 64, 37 GB).  Mirrors what a rapidsnark / snarkjs caller would loop over (zk_census_test.go:89 per voter).
+ * Every witness value must be below r (not checked on the device, see zkc_prove above). */
 int zkc_prove_batch_dev(zkc_zkey* zk, const void* d_wtns, uint32_t nWitness, int B, const uint8_t* rs, uint8_t* proofs, uint8_t* publics);
 
 /* groth16.fullProve (ts_inputs/src/example.ts:358-362) for a batch, everything on the device: B input blocks (zkc_circuit_n_inputs x 32 B
@@ -264,7 +268,8 @@ unsigned long zkc_wtns_write(const void* payload, uint32_t nWitness, void* out, 
  *                      d_src != d_dst; inverse != 0 includes the 1/n factor.
  * zkc_g1_mul_batch_dev: d_out[i] = k_i * base (scalars 32 B standard form on the device; points affine standard form, 64 B).
  * zkc_msm_g1_load_dev : n bases (device, affine standard form; checked to be on the curve) -> resident pre-shifted window tables.
- * zkc_msm_g1_dev      : sum_i s_i P_i, scalars n x 32 B standard form on the device; out = affine standard form (zero = infinity). */
+ * zkc_msm_g1_dev      : sum_i (s_i mod r) P_i, scalars n x 32 B on the device, any 256-bit little-endian integers (ffjavascript's multiExpAffine
+ *                      takes integers; they are reduced mod r on the device first); out = affine standard form (zero = infinity). */
 typedef struct zkc_msm zkc_msm;
 int zkc_ntt_dev(zkc_ctx* ctx, const void* d_src, void* d_dst, int logn, int nvec, int inverse);
 int zkc_g1_mul_batch_dev(zkc_ctx* ctx, const uint8_t base_std[64], const void* d_scalars, uint32_t n, void* d_out);
@@ -275,7 +280,7 @@ void zkc_msm_g1_free(zkc_msm* m);
 /* ---- test hooks (stage outputs for parity tests against the oracle; not part of the drop-in surface) ----
  * zkc_debug_stage: stage 0 -> A_w | B_w | C_w after buildABC (3 x domainSize x 32 B, Montgomery form);
  *                  stage 1 -> joinABC output (A'B' - C') on the odd coset (domainSize x 32 B, standard form).
- * zkc_msm_debug  : one MSM over zkey section which (0=A 1=B1 2=B2 3=C 4=H) with caller scalars (device, standard form);
+ * zkc_msm_debug  : one MSM over zkey section which (0=A 1=B1 2=B2 3=C 4=H) with caller scalars (device, standard form, below r);
  *                  host_out = affine point in standard form (64 B, or 128 B for B2). */
 int zkc_debug_stage(zkc_zkey* zk, const void* d_wtns, int stage, void* host_out);
 unsigned long long zkc_debug_early_retries(void);      /* calls of given witnesses that were laid out from their sibling wires, refused by the fold check and proved again from their fold flags (process-wide) */

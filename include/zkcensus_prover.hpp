@@ -137,10 +137,16 @@ inline Tree GenTree(const uint8_t key[20], const Big& value, int n, int nLevels 
     std::mt19937_64 rng{std::random_device{}()};
     std::vector<uint8_t> keys(32ull * n, 0), vals(32ull * n, 0);
     memcpy(keys.data(), key, 20); memcpy(vals.data(), value.data(), 32);
-    for (int i = 1; i < n; i++) { for (int k = 0; k < 20; k++) keys[32ull * i + k] = (uint8_t)rng(); vals[32ull * i] = 1; }
     Tree t; t.siblings.assign(nLevels, Big{});
     std::vector<uint8_t> sib(32ull * n * (nLevels + 1)); std::vector<int32_t> depth(n);
-    detail::check(zkc_smt_build(detail::context(), keys.data(), vals.data(), n, nLevels, t.root.data(), sib.data(), depth.data()), detail::context(), "GenTree");
+    // random padding keys may share their first nLevels path bits with another key (10 keys in a 10-level tree: 4 % of the draws), which the
+    // tree refuses (ZKC_ERR_BAD_ARG): draw them again
+    int rc = ZKC_ERR_BAD_ARG;
+    for (int attempt = 0; attempt < 64 && rc == ZKC_ERR_BAD_ARG; attempt++) {
+        for (int i = 1; i < n; i++) { for (int k = 0; k < 20; k++) keys[32ull * i + k] = (uint8_t)rng(); vals[32ull * i] = 1; }
+        rc = zkc_smt_build(detail::context(), keys.data(), vals.data(), n, nLevels, t.root.data(), sib.data(), depth.data());
+    }
+    detail::check(rc, detail::context(), "GenTree");
     for (int l = 0; l < nLevels; l++) memcpy(t.siblings[l].data(), sib.data() + 32ull * l, 32);
     t.nSiblings = depth[0];
     return t;

@@ -1,7 +1,9 @@
 """CPU: the radix-2^29 field and group arithmetic of the hot kernels (csrc/zkc_f29*.h) is host+device code; these programs run it on
 the host against the plain 8 x u32 Montgomery reference (zkc_field.h CIOS, zkc_curve.h XYZZ formulas): products, squarings, lazy
 add/sub with dominators, the zero test, exits from the limb form, and chains of mixed / full additions and doublings in G1 and G2
-including the equal-point and opposite-point cases.  Compiled with hipcc (host pass only is executed; no GPU needed)."""
+including the equal-point and opposite-point cases.  Operands are canonical and cover the whole of [0, p), with half the draws at its top
+(p - 1, p - 2^k, all-ones 29-bit limbs: tools/probe/f29_operands.h), where the lazy bounds are tightest.  Compiled with hipcc (host pass only
+is executed; no GPU needed)."""
 import os, shutil, subprocess
 import pytest
 import oracle_lib as ol

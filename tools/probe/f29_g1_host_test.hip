@@ -4,10 +4,11 @@
 #include <cstring>
 #include <random>
 #include "zkc_curve.h"
+#include "f29_operands.h"
 #include "zkc_f29_g1.h"
 using namespace zkc;
 static std::mt19937_64 rng(4242);
-static Fq rnd() { Fq r; for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)rng(); r.v[7] &= 0x0fffffff; return r; }
+static Fq rnd() { return f29_operand<FqParams>(rng); }              // canonical, over the whole of [0, q) and its top (f29_operands.h)
 static G1XYZZ rndpt() { return {rnd(), rnd(), rnd(), rnd()}; }
 static bool same(const Acc29& a, const G1XYZZ& r) {
     if (r.is_inf()) return f29_pt_is_inf(a);

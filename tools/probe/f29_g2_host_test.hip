@@ -4,10 +4,11 @@
 #include <cstring>
 #include <random>
 #include "zkc_curve.h"
+#include "f29_operands.h"
 #include "zkc_f29_g2.h"
 using namespace zkc;
 static std::mt19937_64 rng(777);
-static Fq rnd() { Fq r; for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)rng(); r.v[7] &= 0x0fffffff; return r; }
+static Fq rnd() { return f29_operand<FqParams>(rng); }              // canonical, over the whole of [0, q) and its top (f29_operands.h)
 static Fq2 rnd2() { return {rnd(), rnd()}; }
 static void enter2(F2x29& r, const Fq2& a) { f29_enter_fq(r.c0, a.c0.v); f29_enter_fq(r.c1, a.c1.v); }
 static Fq2 leave2(const F2x29& a) { return {f29_to_fp<FqParams>(a.c0), f29_to_fp<FqParams>(a.c1)}; }

@@ -2,17 +2,19 @@
 #include <cstring>
 #include <random>
 #include "zkc_curve.h"
+#include "f29_operands.h"
 #include "zkc_f29.h"
 using namespace zkc;
 static std::mt19937_64 rng(12345);
-template <class P> Fp<P> rnd() { Fp<P> r; for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)rng(); r.v[7] &= 0x0fffffff; return r; }   // < 2^252 < p : canonical
+template <class P> Fp<P> rnd() { return f29_operand<P>(rng); }      // canonical, over the whole of [0, p) and its top (f29_operands.h)
 template <class P> int run(const char* name) {
     int bad = 0;
-    constexpr L9 d1 = f29_dominator<P>(1u << 29, 1u << 25), d3 = f29_dominator<P>(3u << 29, 1u << 24);
+    // the kernels' dominators: operands now reach p - 1, so 32 x operand reaches 2^258.6 and limb 8 of a subtrahend 2^26.6
+    constexpr L9 d1 = F29K<P>::dom1, d3 = F29K<P>::dom3;
     // dominators are multiples of p
-    { uint32_t t[9]; memcpy(t, d1.l, 36); f29_carry(t); /* not < 64p necessarily: check via to_fp == 0 */
-      Fp<P> z = f29_to_fp<P>(t); if (!z.is_zero()) { printf("%s dom1 not multiple of p\n", name); bad++; }
-      memcpy(t, d3.l, 36); f29_carry(t); z = f29_to_fp<P>(t); if (!z.is_zero()) { printf("%s dom3 not multiple of p\n", name); bad++; }
+    { uint32_t t[9], u[9]; memcpy(t, d1.l, 36); f29_carry(t); /* above 32 p, the input bound of f29_to_fp: times 1 first (output < 2 p), then to_fp == 0 */
+      f29_mul<P>(u, t, F29K<P>::one.l); Fp<P> z = f29_to_fp<P>(u); if (!z.is_zero()) { printf("%s dom1 not multiple of p\n", name); bad++; }
+      memcpy(t, d3.l, 36); f29_carry(t); f29_mul<P>(u, t, F29K<P>::one.l); z = f29_to_fp<P>(u); if (!z.is_zero()) { printf("%s dom3 not multiple of p\n", name); bad++; }
       for (int i = 0; i < 8; i++) if (d1.l[i] < (1u << 29) || d1.l[i] >= (1u << 30) || d3.l[i] < (3u << 29)) { printf("%s dom limb range\n", name); bad++; }
       printf("%s dom1 top %08x dom3 top %08x one[0] %08x\n", name, d1.l[8], d3.l[8], F29K<P>::one.l[0]); }
     for (int it = 0; it < 200000; it++) {

@@ -50,11 +50,27 @@ __global__ void __launch_bounds__(64) zkc_g1_mul_same_base(G1Affine p, const uin
     uint32_t k[8]; for (int q = 0; q < 8; q++) k[q] = scalars[8 * (size_t)i + q];
     out[i] = xyzz_mul(G1XYZZ::from_affine(p), k);
 }
+// out[i] = in[i] mod r for any 256-bit in[i] (2^256 < 6 r: at most five subtractions).  The signed-digit bucketing (msm_tile_digit) needs
+// scalars below 2^254: it reads nw c bits (255 for c = 15 and 17, 256 for c = 16) and drops the carry out of the top window.
+__global__ void __launch_bounds__(256) zkc_reduce_scalars(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4* ip = reinterpret_cast<const uint4*>(in + 8 * (size_t)i); const uint4 a = ip[0], b = ip[1];
+    uint32_t s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    for (int k = 0; k < 5 && !fp_std_lt_p<FrParams>(s); k++) {
+        uint64_t br = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) { const uint64_t d = (uint64_t)s[q] - FrParams::p[q] - br; s[q] = (uint32_t)d; br = (d >> 63) & 1; }
+    }
+    uint4* op = reinterpret_cast<uint4*>(out + 8 * (size_t)i);
+    op[0] = make_uint4(s[0], s[1], s[2], s[3]); op[1] = make_uint4(s[4], s[5], s[6], s[7]);
+}
 }  // namespace
 
 struct zkc_msm {
     zkc_zkey zk;                 // only ctx and d_g1 are used by the MSM pipeline
     MsmWork w; uint32_t n = 0; int c = 0; MsmJobList jl;
+    uint32_t* d_red = nullptr;   // n x 8 u32: the caller's scalars reduced mod r (zkc_reduce_scalars)
 };
 
 // In-place-capable NTT over BN254 Fr on `nvec` contiguous vectors of 2^logn elements in MONTGOMERY form (R = 2^256), natural order in
@@ -111,8 +127,9 @@ extern "C" int zkc_msm_g1_load_dev(zkc_ctx* ctx, const void* d_bases_std, uint32
     zkc_msm* m = new zkc_msm(); m->zk.ctx = ctx; m->n = n; m->c = msm_c_for(n);
     const int nw = msm_nw(m->c);
     uint32_t* d_bad = nullptr; uint32_t bad = 0; int rc = ZKC_OK;
-    auto bail = [&](int code) { if (d_bad) (void)hipFree(d_bad); if (m->zk.d_g1) (void)hipFree(m->zk.d_g1); m->zk.d_g1 = nullptr; msm_work_free(m->w); delete m; return code; };
-    if (hipMalloc((void**)&m->zk.d_g1, (size_t)nw * n * sizeof(G1Affine)) != hipSuccess || hipMalloc((void**)&d_bad, 4) != hipSuccess || hipMemset(d_bad, 0, 4) != hipSuccess)
+    auto bail = [&](int code) { if (d_bad) (void)hipFree(d_bad); if (m->zk.d_g1) (void)hipFree(m->zk.d_g1); if (m->d_red) (void)hipFree(m->d_red); m->zk.d_g1 = nullptr; msm_work_free(m->w); delete m; return code; };
+    if (hipMalloc((void**)&m->zk.d_g1, (size_t)nw * n * sizeof(G1Affine)) != hipSuccess || hipMalloc((void**)&m->d_red, (size_t)n * 32) != hipSuccess ||
+        hipMalloc((void**)&d_bad, 4) != hipSuccess || hipMemset(d_bad, 0, 4) != hipSuccess)
         return bail(zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: hipMalloc failed"));
     hipLaunchKernelGGL(zkc_g1_std_to_mont, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)d_bases_std, m->zk.d_g1, n, d_bad);
     if (hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -125,13 +142,15 @@ extern "C" int zkc_msm_g1_load_dev(zkc_ctx* ctx, const void* d_bases_std, uint32
     *out = m;
     return ZKC_OK;
 }
-// sum_i s_i P_i over the resident bases; d_scalars: n x 32 B standard form (device); out: affine standard form (all zero = infinity)
+// sum_i (s_i mod r) P_i over the resident bases; d_scalars: n x 32 B, any 256-bit integers (device); out: affine standard form (all zero = infinity)
 extern "C" int zkc_msm_g1_dev(zkc_msm* m, const void* d_scalars, uint8_t out[64]) {
     if (!m || !d_scalars || !out) return ZKC_ERR_BAD_ARG;
     zkc_ctx* ctx = m->zk.ctx;
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    m->jl.clear(); m->jl.add((const uint32_t*)d_scalars, nullptr, m->n, 0, m->n, 0, m->c);
+    hipLaunchKernelGGL(zkc_reduce_scalars, dim3((m->n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)d_scalars, m->d_red, m->n);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    m->jl.clear(); m->jl.add(m->d_red, nullptr, m->n, 0, m->n, 0, m->c);
     int rc = msm_pass_g1(&m->zk, m->w, m->jl, 0, true, ctx->stream); if (rc) return rc;
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const G1Affine a = xyzz_to_affine(*(const G1XYZZ*)m->w.h_results);
@@ -143,6 +162,7 @@ extern "C" void zkc_msm_g1_free(zkc_msm* m) {
     ZKC_LOCK(m->zk.ctx);
     (void)hipSetDevice(m->zk.ctx->device); (void)hipStreamSynchronize(m->zk.ctx->stream);
     if (m->zk.d_g1) (void)hipFree(m->zk.d_g1);
+    if (m->d_red) (void)hipFree(m->d_red);
     m->zk.d_g1 = nullptr; msm_work_free(m->w);
     delete m;
 }

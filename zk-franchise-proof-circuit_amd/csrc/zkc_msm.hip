@@ -683,7 +683,10 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
         streamed_bytes += (uint64_t)jl.job[j].count * (sizeof(Affine<F>) + 32);     // (scalar, base) pairs that actually enter the MSM
         maxcount = std::max(maxcount, jl.job[j].count);
     }
-    const size_t seg_bound = std::min<size_t>(w.max_segments, total / seg + nb);     // launch bound on the number of segments
+    // launch bound on the number of segments: a bucket of b entries makes ceil(b / seg) <= b / seg + 1 of them.  A pass whose bound does not fit the work space is refused:
+    // clamping it would drop buckets without a word if a skew bug ever produced more segments than the sizing in msm_work_alloc_impl allows for
+    const size_t seg_bound = total / seg + nb;
+    if (!bucket_wave && seg_bound > w.max_segments) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "msm_pass: more segments than the work space holds");
     {
         zkc_prof_scope _ps(ctx, ZKC_PROF_MSM_SORT, 0, st);
         if (jl.total_windows > w.max_windows) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "msm_pass: too many virtual windows for the work space");

@@ -991,6 +991,7 @@ extern "C" int zkc_prove(zkc_zkey* zk, const void* wtns, uint32_t nWitness, cons
     zkc_ctx* ctx = zk->ctx;
     ZKC_LOCK(ctx);
     if (nWitness != zk->nVars) return zkc_fail(ctx, ZKC_ERR_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zk->nVars) + ", witness: " + std::to_string(nWitness));
+    if (const long long bad = first_unreduced_wire(wtns, nWitness); bad >= 0) return zkc_fail(ctx, ZKC_ERR_FORMAT, unreduced_wire_msg(bad));
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     int rc = zkc_ensure(ctx, &ctx->d_scratch_out, &ctx->scratch_out_sz, 32ull * nWitness); if (rc) return rc;
     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_scratch_out, wtns, 32ull * nWitness, hipMemcpyHostToDevice, ctx->stream));

@@ -1,5 +1,6 @@
 // zkc_prover.h -- device-resident proving key and the stage launchers shared by the prover translation units.
 #pragma once
+#include <cstring>
 #include "zkc_internal.h"
 #include "zkc_curve.h"
 
@@ -16,6 +17,17 @@ constexpr int MSM_C_G2_LONE = 8;
 // [r4] the window for an MSM of W full-width scalars: W x ceil(254 / c) mixed additions plus ~4 per bucket for the reduction (2^(c-1) buckets, two full additions each,
 // latency-shaped), so the best c grows with W.  Measured on circuit-shaped random R1CS (tools/gpu/csec_sweep.sh: proofs/s for c = 12 .. 17 at 15 k / 31 k / 62 k / 123 k / 246 k
 // wires per section): best 13 / 15 / 15 / 16 / 17; the 12 of rounds 1-3 is 15 % behind at 62 k wires, 17 is 3 % behind at 123 k.
+// Host witnesses are refused unless every value is below r (standard form): the signed-digit bucketing reads nw c bits of a scalar and drops the carry out
+// of its top window, so a value at or above 2^254 would give a proof that does not verify.  Returns the first wire that is not below r, or -1.
+inline long long first_unreduced_wire(const void* w, size_t count) {
+    const uint8_t* p = (const uint8_t*)w;
+    for (size_t i = 0; i < count; i++) {
+        uint32_t t[8]; memcpy(t, p + 32 * i, 32);
+        if (t[7] >= FrParams::p[7] && !fp_std_lt_p<FrParams>(t)) return (long long)i;       // the top word decides for all but a 2^-32 sliver of the field
+    }
+    return -1;
+}
+inline std::string unreduced_wire_msg(long long wire) { return "Witness value at wire " + std::to_string(wire) + " is not below the field order r"; }
 inline int msm_c_for(size_t W) { return W < 12000 ? 12 : W < 22000 ? 13 : W < 90000 ? 15 : W < 180000 ? 16 : 17; }
 constexpr int msm_nw(int c) { return (254 + c) / c; }          // 17 -> 15 windows (255 bits), 12 -> 22 windows (264 bits)
 constexpr int msm_half(int c) { return 1 << (c - 1); }         // buckets per job

@@ -539,6 +539,7 @@ static std::shared_ptr<KeyImage> image_of(zkc_service* s, const void* zkey, size
 static int submit(zkc_service* s, int kind, const void* zkey, size_t zkey_len, int nLevels, const void* data, uint32_t nW, const uint8_t* rs, uint8_t* proof, uint8_t* pub,
                   zkc_done_fn done, void* user) {
     if (!s || !zkey || !data || !proof || !done) return service_fail(ZKC_ERR_BAD_ARG, "zkc_service_submit: bad argument");
+    if (kind == KIND_PROVE) { const long long bad = zkc::first_unreduced_wire(data, nW); if (bad >= 0) return service_fail(ZKC_ERR_FORMAT, zkc::unreduced_wire_msg(bad)); }
     std::string why;
     std::shared_ptr<KeyImage> img = image_of(s, zkey, zkey_len, why);
     if (!img) return service_fail(ZKC_ERR_FORMAT, why);

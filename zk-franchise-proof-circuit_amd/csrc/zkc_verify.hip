@@ -528,6 +528,7 @@ extern "C" int groth16_prover(const void* zkey_buffer, unsigned long zkey_size, 
     const uint8_t* payload; uint32_t nw;
     if (zkc_wtns_parse(wtns_buffer, wtns_size, &payload, &nw)) return err(ZKC_ERR_GENERIC, "Invalid witness file");
     if (nw != zh.nVars) return err(ZKC_ERR_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zh.nVars) + ", witness: " + std::to_string(nw));
+    if (const long long bad = zkc::first_unreduced_wire(payload, nw); bad >= 0) return err(ZKC_ERR_GENERIC, zkc::unreduced_wire_msg(bad));
     const unsigned long need_proof = 8 * 80 + 128, need_public = (unsigned long)zh.nPub * 80 + 8;      // hold ANY proof of this shape (77 decimal digits per coordinate)
     if (!proof_buffer || !public_buffer || *proof_size < need_proof || *public_size < need_public) {
         *proof_size = need_proof; *public_size = need_public;
