@@ -7,13 +7,10 @@ import ctypes
 import random
 import pytest
 import oracle_lib as ol
+from census_lib import (W, words, VALID, ROOT_MISMATCH, NOT_BELOW_R, LAST_SIBLING, KEY_PRESENT, OFF_PATH, ZKC_ERR_BAD_ARG, equals_rebuild, fresh_keys, oracle_verdict,
+                        sib_list, tree_keys)
 
 pytestmark = pytest.mark.gpu
-
-W = lambda x: int(x).to_bytes(32, 'little')
-words = lambda xs: b''.join(W(x) for x in xs)
-VALID, ROOT_MISMATCH, NOT_BELOW_R, LAST_SIBLING, KEY_PRESENT, OFF_PATH = range(6)
-ZKC_ERR_BAD_ARG = 4
 
 
 @pytest.fixture(scope='module')
@@ -31,49 +28,6 @@ def py_root(items, d=0):
     if len(items) == 1:
         return ol.poseidon([items[0][0], items[0][1], 1])
     return ol.poseidon([py_root([x for x in items if not (x[0] >> d) & 1], d + 1), py_root([x for x in items if (x[0] >> d) & 1], d + 1)])
-
-
-def sib_list(sib, i, nl):
-    blk = 32 * (nl + 1)
-    return [int.from_bytes(sib[blk * i + 32 * l:blk * i + 32 * l + 32], 'little') for l in range(nl + 1)]
-
-
-def oracle_absence(key, old_key, old_value, is_old0, sibs, root, nl):
-    """circomlib SMTVerifier with fnc = 1 over this project's conventions, in Python over the oracle's Poseidon (no GPU code on this side)"""
-    if any(x >= ol.R for x in [key, old_key, old_value, root] + sibs):
-        return NOT_BELOW_R
-    if sibs[nl]:
-        return LAST_SIBLING
-    d = max((l + 1 for l in range(nl) if sibs[l]), default=0)
-    if not is_old0 and old_key == key:
-        return KEY_PRESENT
-    if not is_old0 and (old_key ^ key) & ((1 << d) - 1):
-        return OFF_PATH
-    cur = 0 if is_old0 else ol.poseidon([old_key, old_value, 1])
-    for l in range(d - 1, -1, -1):
-        cur = ol.poseidon([sibs[l], cur]) if (key >> l) & 1 else ol.poseidon([cur, sibs[l]])
-    return VALID if cur == root else ROOT_MISMATCH
-
-
-def equals_rebuild(ctx, tree, kv, nl):
-    """the tree equals zkc_smt_build over kv (a dict): root, every key's siblings and depth"""
-    from zkcensus_amd import census
-    if not kv:
-        assert tree.root == 0 and len(tree) == 0
-        return
-    ks = list(kv)
-    root, sib, dep = census.smt_build(ctx, ks, [kv[k] for k in ks], nl)
-    assert tree.root == root and len(tree) == len(ks)
-    r, s, d, ex = tree.gen_proof(ks)
-    assert r == root and all(ex)
-    assert d == dep
-    assert s == sib
-
-
-def tree_keys(rng, nl, n):
-    if nl >= 64:
-        return list(dict.fromkeys(rng.getrandbits(nl) for _ in range(n + 64)))[:n]
-    return [l | (rng.getrandbits(200) << nl) for l in rng.sample(range(1 << nl), n)]
 
 
 @pytest.mark.parametrize('nl,order', [(160, 'random'), (160, 'adversarial'), (12, 'random'), (12, 'adversarial')])
@@ -221,14 +175,7 @@ def test_churn_is_bounded(ctx):
     rng = random.Random(4096)
     nl = 160
     seen = set()
-
-    def fresh(m):
-        out = []
-        while len(out) < m:
-            k = rng.getrandbits(160)
-            if k not in seen:
-                seen.add(k); out.append(k)
-        return out
+    fresh = lambda m: fresh_keys(rng, seen, m, 160)
     ks = fresh(4096)
     kv = {k: rng.randrange(ol.R) for k in ks}
     with census.CensusTree(ctx, nl) as tree:
@@ -262,7 +209,7 @@ def _check_all(ctx, tree, keys, root=None):
     for i in range(len(keys)):
         s = sib_list(sib, i, nl)
         assert all(x == 0 for x in s[dep[i]:])
-        assert oracle_absence(keys[i], ok[i], ov[i], o0[i], s, r, nl) == VALID
+        assert oracle_verdict(keys[i], ov[i], s, r, nl, ok[i], o0[i]) == VALID
     assert census.check_absence(ctx, keys, ok, ov, o0, sib, [r] * len(keys), nl) == [VALID] * len(keys)
     return r, sib, dep, ok, ov, o0
 
@@ -308,7 +255,7 @@ def test_absence_proofs(ctx):
             args = (keys[i] if key is None else key, ok[i] if okey is None else okey, ov[i] if oval is None else oval, o0[i] if old0 is None else old0)
             rt = r if root is None else root
             got = census.check_absence(ctx, [args[0]], [args[1]], [args[2]], [args[3]], words(s), rt, nl)[0]
-            assert got == oracle_absence(*args, s, rt, nl)
+            assert got == oracle_verdict(args[0], args[2], s, rt, nl, args[1], args[3])
             return got
         for i in (i0, i1):
             assert one(i) == VALID
@@ -381,7 +328,7 @@ def test_both_kernel_forms_and_every_depth(ctx):
     whole = census.check_absence(ctx, keys, oks, ovs, o0s, sibs, roots, nl)
     assert whole == want
     for i in rng.sample(range(n), 40):
-        assert oracle_absence(keys[i], oks[i], ovs[i], o0s[i], sib_list(sibs, i, nl), roots[i], nl) == want[i]
+        assert oracle_verdict(keys[i], ovs[i], sib_list(sibs, i, nl), roots[i], nl, oks[i], o0s[i]) == want[i]
     cut = []
     for lo in range(0, n, 64):
         hi = min(n, lo + 64)
@@ -396,7 +343,7 @@ def test_two_to_the_17_proofs_in_one_call(ctx):
     from zkcensus_amd import census
     rng = random.Random(17)
     nl = 40
-    ks = tree_keys(rng, nl, 8192); vs = [rng.randrange(ol.R) for _ in ks]
+    ks = [l | (rng.getrandbits(200) << nl) for l in rng.sample(range(1 << nl), 8192)]; vs = [rng.randrange(ol.R) for _ in ks]      # distinct low 40 bits, random high bits
     present = set(ks)
     n = 1 << 17
     absent = [k for k in dict.fromkeys(rng.getrandbits(nl) for _ in range(n + 4096)) if k not in present][:n]
@@ -413,5 +360,5 @@ def test_two_to_the_17_proofs_in_one_call(ctx):
                   + census.check_absence(ctx, absent[h:], ok[h:], ov[h:], o0[h:], sib[blk * h:], roots[h:], nl))
         assert halves == want
         for i in rng.sample(range(n), 64):
-            assert oracle_absence(absent[i], ok[i], ov[i], o0[i], sib_list(sib, i, nl), roots[i], nl) == want[i]
+            assert oracle_verdict(absent[i], ov[i], sib_list(sib, i, nl), roots[i], nl, ok[i], o0[i]) == want[i]
         assert min(census.check_stats(ctx)) >= 0

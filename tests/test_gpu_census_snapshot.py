@@ -8,12 +8,9 @@ import random
 import threading
 import pytest
 import oracle_lib as ol
+from census_lib import W, ZKC_ERR_BAD_ARG, equals_rebuild, fresh_tree, tree_keys
 
 pytestmark = pytest.mark.gpu
-
-W = lambda x: int(x).to_bytes(32, 'little')
-VALID = 0
-ZKC_ERR_BAD_ARG = 4
 
 
 @pytest.fixture(scope='module')
@@ -22,50 +19,6 @@ def ctx():
     c = zkcensus_amd.Context(0)
     yield c
     c.close()
-
-
-def tree_keys(rng, nl, n, avoid=()):
-    """n distinct random keys below r; at nLevels < 32 their low nl bits are distinct too (and of `avoid`'s), the high bits random"""
-    if nl >= 32:
-        return [k for k in dict.fromkeys(rng.getrandbits(nl) for _ in range(n + 64)) if k not in avoid][:n]
-    taken = {k & ((1 << nl) - 1) for k in avoid}
-    free = [l for l in range(1 << nl) if l not in taken]
-    return [l | (rng.getrandbits(200) << nl) for l in rng.sample(free, n)]
-
-
-def fresh_tree(ctx, kv, nl):
-    from zkcensus_amd import census
-    t = census.CensusTree(ctx, nl)
-    if kv:
-        assert t.add(list(kv), list(kv.values())) == [0] * len(kv)
-    return t
-
-
-def equals_rebuild(ctx, tree, kv, nl, others=()):
-    """tree (live or snapshot) equals zkc_smt_build over kv (a dict): root, size, every key's siblings / depth / value; the keys of `others` that kv does not hold are
-    absent from it (no siblings, depth 0, value 0), and their absence proofs are those of a tree built fresh from kv and valid against the tree's root"""
-    from zkcensus_amd import census
-    ks = list(kv)
-    absent = [k for k in dict.fromkeys(others) if k not in kv]
-    if ks:
-        root, sib, dep = census.smt_build(ctx, ks, [kv[k] for k in ks], nl)
-    else:
-        root, sib, dep = 0, b'', []
-    assert tree.root == root and len(tree) == len(ks)
-    r, s, d, ex = tree.gen_proof(ks + absent)
-    blk = 32 * (nl + 1)
-    assert r == root and ex == [True] * len(ks) + [False] * len(absent)
-    assert d == dep + [0] * len(absent)
-    assert s[:blk * len(ks)] == sib and s[blk * len(ks):] == b'\0' * blk * len(absent)
-    vals, ex = tree.get(ks + absent)
-    assert vals == [kv[k] for k in ks] + [0] * len(absent) and ex == [True] * len(ks) + [False] * len(absent)
-    if absent:
-        got = tree.gen_absence_proof(absent)
-        with fresh_tree(ctx, kv, nl) as f:
-            assert got == f.gen_absence_proof(absent)
-        r, sib_a, dep_a, ok, ov, o0, st = got
-        assert st == [0] * len(absent) and r == root
-        assert tree.check_absence(absent, ok, ov, o0, sib_a) == [VALID] * len(absent)
 
 
 def depths(tree, keys):

@@ -4,10 +4,9 @@ builds for voters of two resident trees equal the static census builder's and pa
 import random
 import pytest
 import oracle_lib as ol
+from census_lib import W, VALID, fresh_keys, oracle_verdict, sib_list, tree_keys
 
 pytestmark = pytest.mark.gpu
-
-W = lambda x: int(x).to_bytes(32, 'little')
 
 
 @pytest.fixture(scope='module')
@@ -53,14 +52,7 @@ def test_tree_equals_the_static_builder_at_160_levels(ctx, schedule):
         tree.close()
         return
     seen = set()
-
-    def fresh(m):
-        out = []
-        while len(out) < m:
-            k = rng.getrandbits(253)
-            if k not in seen:
-                seen.add(k); out.append(k)
-        return out
+    fresh = lambda m: fresh_keys(rng, seen, m, 253)
     sizes = [1] * 40 + [7] * 40 + [1024] * 127
     for b, m in enumerate(sizes):
         ks = fresh(m); vs = [rng.randrange(ol.R) for _ in range(m)]
@@ -86,8 +78,7 @@ def test_tree_equals_the_static_builder_at_12_levels(ctx):
     from zkcensus_amd import census
     rng = random.Random(12)
     nl = 12
-    low = rng.sample(range(1 << nl), 3000)
-    ks = [l | (rng.getrandbits(200) << nl) for l in low]; vs = [rng.randrange(ol.R) for _ in ks]
+    ks = tree_keys(rng, nl, 3000); vs = [rng.randrange(ol.R) for _ in ks]
     kb, vb = b''.join(map(W, ks)), b''.join(map(W, vs))
     with census.CensusTree(ctx, nl) as whole:
         assert whole.add(kb, vb) == [0] * len(ks)
@@ -109,19 +100,15 @@ def test_proofs_climb_to_the_root_with_the_oracle_poseidon(ctx):
     rng = random.Random(40)
     nl = 12
     ks = rng.sample(range(1 << nl), 40); vs = [rng.randrange(ol.R) for _ in ks]; vs[3] = ol.R - 1
-    blk = 32 * (nl + 1)
     with census.CensusTree(ctx, nl) as tree:
         for j, (k, v) in enumerate(zip(ks, vs)):
             assert tree.add([k], [v]) == [0]
             root, sib, dep, ex = tree.gen_proof(ks[:j + 1])
             assert all(ex) and root == tree.root
             for i in range(j + 1):
-                s = [int.from_bytes(sib[blk * i + 32 * l:blk * i + 32 * l + 32], 'little') for l in range(nl + 1)]
+                s = sib_list(sib, i, nl)
                 assert all(x == 0 for x in s[dep[i]:])
-                cur = ol.poseidon([ks[i], vs[i], 1])
-                for l in range(dep[i] - 1, -1, -1):
-                    cur = ol.poseidon([s[l], cur]) if (ks[i] >> l) & 1 else ol.poseidon([cur, s[l]])
-                assert cur == root, (j, i)
+                assert oracle_verdict(ks[i], vs[i], s, root, nl) == VALID, (j, i)
         assert len(tree) == 40
 
 

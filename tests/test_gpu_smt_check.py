@@ -7,12 +7,9 @@ import os
 import random
 import pytest
 import oracle_lib as ol
+from census_lib import words, VALID, ROOT_MISMATCH, NOT_BELOW_R, LAST_SIBLING, oracle_verdict, sib_list, tree_keys
 
 pytestmark = pytest.mark.gpu
-
-W = lambda x: int(x).to_bytes(32, 'little')
-words = lambda xs: b''.join(W(x) for x in xs)
-VALID, ROOT_MISMATCH, NOT_BELOW_R, LAST_SIBLING = range(4)
 
 
 @pytest.fixture(scope='module')
@@ -21,28 +18,6 @@ def ctx():
     c = zkcensus_amd.Context(0)
     yield c
     c.close()
-
-
-def sib_list(sib, i, nl):
-    blk = 32 * (nl + 1)
-    return [int.from_bytes(sib[blk * i + 32 * l:blk * i + 32 * l + 32], 'little') for l in range(nl + 1)]
-
-
-def oracle_check(key, value, sibs, root, nl):
-    """arbo CheckProof with the circuit's extra rules, in Python over the oracle's Poseidon (no GPU code on this side)"""
-    if any(x >= ol.R for x in [key, value, root] + sibs):
-        return NOT_BELOW_R
-    if sibs[nl]:
-        return LAST_SIBLING
-    d = max((l + 1 for l in range(nl) if sibs[l]), default=0)
-    cur = ol.poseidon([key, value, 1])
-    for l in range(d - 1, -1, -1):
-        cur = ol.poseidon([sibs[l], cur]) if (key >> l) & 1 else ol.poseidon([cur, sibs[l]])
-    return VALID if cur == root else ROOT_MISMATCH
-
-
-def random_keys(rng, n, bits=160):
-    return list(dict.fromkeys(rng.getrandbits(bits) for _ in range(n + 64)))[:n]
 
 
 def test_reference_paths(ctx):
@@ -71,10 +46,7 @@ def test_every_proof_of_a_tree_is_valid(ctx, nl):
     tree (checked through CensusTree.check_proofs, against its current root, which it leaves alone): all valid; a seeded sample of 512 agrees with the oracle's climb."""
     from zkcensus_amd import census
     rng = random.Random(nl)
-    if nl == 160:
-        ks = random_keys(rng, 1 << 17)
-    else:
-        ks = [l | (rng.getrandbits(200) << nl) for l in rng.sample(range(1 << nl), 3000)]
+    ks = tree_keys(rng, nl, 1 << 17 if nl == 160 else 3000)
     vs = [rng.randrange(ol.R) for _ in ks]
     kb, vb = words(ks), words(vs)
     n = len(ks)
@@ -88,7 +60,7 @@ def test_every_proof_of_a_tree_is_valid(ctx, nl):
         assert tree.root == root and len(tree) == n
     sample = rng.sample(range(n), 512)
     got = census.check_proofs(ctx, [ks[i] for i in sample], [vs[i] for i in sample], b''.join(sib[32 * (nl + 1) * i:32 * (nl + 1) * (i + 1)] for i in sample), root, nl)
-    assert got == [oracle_check(ks[i], vs[i], sib_list(sib, i, nl), root, nl) for i in sample] == [VALID] * 512
+    assert got == [oracle_verdict(ks[i], vs[i], sib_list(sib, i, nl), root, nl) for i in sample] == [VALID] * 512
 
 
 def test_tamper_classes(ctx):
@@ -96,7 +68,7 @@ def test_tamper_classes(ctx):
     from zkcensus_amd import census
     rng = random.Random(7)
     nl = 160
-    ks = random_keys(rng, 4096); vs = [rng.randrange(1, ol.R - 1) for _ in ks]
+    ks = tree_keys(rng, nl, 4096); vs = [rng.randrange(1, ol.R - 1) for _ in ks]
     root, sib, dep = census.smt_build(ctx, ks, vs, nl)
     cases = []                                       # (key, value, siblings, root, expected)
 
@@ -138,7 +110,7 @@ def test_tamper_classes(ctx):
     assert got == [c[4] for c in cases]
     assert {c[4] for c in cases} == {VALID, ROOT_MISMATCH, NOT_BELOW_R, LAST_SIBLING}
     check = rng.sample(range(len(cases)), 300)
-    assert [oracle_check(*cases[j][:4], nl) for j in check] == [got[j] for j in check]
+    assert [oracle_verdict(*cases[j][:4], nl) for j in check] == [got[j] for j in check]
 
 
 def test_frozen_root(ctx):
@@ -147,7 +119,7 @@ def test_frozen_root(ctx):
     from zkcensus_amd import census
     rng = random.Random(1024)
     nl = 160
-    ks = random_keys(rng, 5120); vs = [rng.randrange(1, 101) for _ in ks]
+    ks = tree_keys(rng, nl, 5120); vs = [rng.randrange(1, 101) for _ in ks]
     with census.CensusTree(ctx, nl) as tree:
         assert tree.add(ks[:4096], vs[:4096]) == [0] * 4096
         old_keys = rng.sample(ks[:4096], 512)
@@ -265,7 +237,7 @@ def test_size_and_chunking(ctx):
     rng = random.Random(18)
     nl = 160
     n = 1 << (20 if os.environ.get('ZKC_TEST_FULL') == '1' else 18)
-    ks = random_keys(rng, n)
+    ks = tree_keys(rng, nl, n)
     vs = [rng.randrange(1, 101) for _ in ks]
     kb, vb = words(ks), words(vs)
     root, sib, dep = census.smt_build(ctx, kb, vb, nl)

@@ -2,6 +2,7 @@
 // CPU fallback here -- without a working HIP device every call fails with ZKC_ERR_HIP.
 #include "zkc_internal.h"
 #include "zkc_f29.h"
+#include "zkc_kernels.h"
 #include <array>
 #include <cstring>
 #include <ctime>
@@ -11,14 +12,10 @@
 
 using namespace zkc;
 
-extern "C" __global__ void zkc_witness_chains(WitnessLayout L, PoseidonTable tab, const uint32_t* inputs, uint32_t* wtns, int32_t* status, int B, int tmpl_mode);
-extern "C" __global__ void zkc_witness_chains_wave(WitnessLayout L, PoseidonTable tab, const uint32_t* inputs, uint32_t* wtns, int32_t* status, int B, int tmpl_mode);
 // a wave per chain halves the latency of a chain and costs 64 times its issue slots: worth it while the chains alone cannot fill the part
 // (5 % of a pass' VALU work for 1024 voters).  Inside the batch pipeline, where the chains run underneath the MSMs, only small launches take it; a
 // stand-alone zkc_witness[_dev] call has nothing to hide behind and takes it up to 1024 voters (3072 waves on 1024 SIMDs).
 static constexpr int ZKC_WITNESS_WAVE_MAX_B = 128, ZKC_WITNESS_WAVE_MAX_B_ALONE = 1024;
-extern "C" __global__ void zkc_witness_fill(const uint4* tmpl, uint4* wtns, int nWires, int B);
-extern "C" __global__ void zkc_witness_tostd(uint32_t* wtns, size_t nwires_total);
 
 static thread_local std::string g_create_err;
 
@@ -56,8 +53,6 @@ void zkc_verify_ws_trim(zkc_ctx* ctx, size_t keep_bytes) {
     if (total <= keep_bytes && keep_bytes) return;
     for (int i = 0; i < zkc_ctx::VWS_N; i++) { if (ctx->vws[i]) (void)hipFree(ctx->vws[i]); ctx->vws[i] = nullptr; ctx->vws_sz[i] = 0; }
 }
-
-extern "C" __global__ void zkc_poseidon_batch_kernel(PoseidonTable tab, const uint32_t* in, uint32_t* out, int nin, size_t B);
 
 static hipEvent_t prof_event(zkc_ctx* ctx) {
     if (!ctx->prof.free_events.empty()) { hipEvent_t e = ctx->prof.free_events.back(); ctx->prof.free_events.pop_back(); return e; }

@@ -11,6 +11,7 @@
 #include "zkc_internal.h"
 #include "zkc_prover.h"
 #include "zkc_f29.h"
+#include "zkc_kernels.h"
 
 namespace zkc {
 

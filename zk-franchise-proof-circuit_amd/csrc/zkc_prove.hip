@@ -9,6 +9,7 @@
 #include "zkc_prover.h"
 #include "zkc_fixedbase.h"
 #include "zkc_hostparse.h"
+#include "zkc_kernels.h"
 #include <cstring>
 #include <ctime>
 #include <cstdio>
@@ -17,10 +18,6 @@
 
 using namespace zkc;
 
-extern "C" __global__ void zkc_matvec_jds(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const Fr*, const Fr*, size_t, Fr*, int, uint32_t, const Fr*, size_t);
-extern "C" __global__ void zkc_wtns_mont(const Fr*, size_t, Fr*, size_t, uint32_t);
-extern "C" __global__ void zkc_pointwise_mul(Fr*, int);
-extern "C" __global__ void zkc_join_abc(const Fr*, uint32_t*, int);
 // buildABC for `nb` proofs on stream `mv` (zkc_ntt.hip): unit coefficients add the wire's Montgomery form, made once per wire in the lane's transform scratch (d_t is idle here:
 // the pair runs in place, the two-transform form writes it afterwards) when it is large enough for nVars elements per proof
 static void matvec_launch(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv) {

@@ -13,23 +13,14 @@
 // zkc_smt_check_absence (exclusion proofs, circomlib SMTVerifier with fnc = 1) runs the same pipeline: per proof the old key and an is_old0 flag ride along, the host also
 // refuses a present key (old key == key) and an old key off the key's path, the proofs are sorted by (depth, is_old0) so the lanes of a wave mostly agree on the leaf hash,
 // and zkc_smt_check_absent / zkc_smt_check_absent_wave climb them.
-#include "zkc_internal.h"
-#include "zkc_field.h"
+#include "zkc_census_host.h"
+#include "zkc_kernels.h"
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
-#include <cstring>
 #include <thread>
 #include <vector>
 
 using namespace zkc;
-
-extern "C" __global__ void zkc_smt_check(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, int32_t*);
-extern "C" __global__ void zkc_smt_check_wave(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t, int32_t*);
-extern "C" __global__ void zkc_smt_check_absent(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, const uint32_t*,
-                                                const uint32_t*, uint32_t, int32_t*);
-extern "C" __global__ void zkc_smt_check_absent_wave(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t,
-                                                     const uint32_t*, const uint32_t*, uint32_t, int32_t*);
 
 namespace {
 constexpr size_t CHUNK_BYTES = (size_t)128 << 20;      // one upload buffer (two are pinned)
@@ -37,16 +28,11 @@ constexpr size_t CHUNK_PROOFS = (size_t)1 << 17;         // 2 048 waves: every l
 constexpr size_t WAVE_MAX_DEFAULT = 64;                // batches up to this size take the wave-per-proof form; ZKC_SMT_WAVE_MAX overrides (0: never; A/B)
 constexpr int32_t PENDING = -1;
 
-inline bool below_r(const uint8_t* v) { uint32_t t[8]; memcpy(t, v, 32); return fp_std_lt_p<FrParams>(t); }
-inline bool is_zero(const uint8_t* v) { uint64_t w[4]; memcpy(w, v, 32); return (w[0] | w[1] | w[2] | w[3]) == 0; }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // a and b differ in one of their first d bits (LSB first: the path bits)
 inline bool prefix_differs(const uint8_t* a, const uint8_t* b, int d) {
     for (int i = 0; i < d / 8; i++) if (a[i] != b[i]) return true;
     return (d & 7) && ((a[d / 8] ^ b[d / 8]) & ((1u << (d & 7)) - 1));
 }
-using clk = std::chrono::steady_clock;
-inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
 // fn(lo, hi) over [0, n) on up to 16 host threads (at least 2 048 items each)
 template <class F>
@@ -183,11 +169,8 @@ static int check_batch(zkc_ctx* ctx, const Batch& B, int32_t* status) {
         if (absent)
             hipLaunchKernelGGL(wave ? zkc_smt_check_absent_wave : zkc_smt_check_absent, grid, dim3(64), 0, ctx->stream, ctx->ptab, P(L.keys), P(L.okeys), P(L.vals),
                                P(L.old0), P(L.roots), (uint32_t)per, P(L.off), P(L.sib), (uint32_t)c, ctx->d_status + a);
-        else if (wave)
-            hipLaunchKernelGGL(zkc_smt_check_wave, dim3((unsigned)c), dim3(64), 0, ctx->stream, ctx->ptab, P(L.keys), P(L.vals), P(L.roots), (uint32_t)per, P(L.off), P(L.sib),
-                               (uint32_t)c, ctx->d_status + a);
         else
-            hipLaunchKernelGGL(zkc_smt_check, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, ctx->stream, ctx->ptab, P(L.keys), P(L.vals), P(L.roots), (uint32_t)per, P(L.off),
+            hipLaunchKernelGGL(wave ? zkc_smt_check_wave : zkc_smt_check, grid, dim3(64), 0, ctx->stream, ctx->ptab, P(L.keys), P(L.vals), P(L.roots), (uint32_t)per, P(L.off),
                                P(L.sib), (uint32_t)c, ctx->d_status + a);
         ZKC_HIP_CHECK(ctx, hipGetLastError());
         ZKC_HIP_CHECK(ctx, hipEventRecord(tev.ev[3 * k + 2], ctx->stream));

@@ -5,9 +5,9 @@
 //   Leaves and inner nodes share one reference space; 0 is the empty subtree.  A leaf keeps its reference when a later key pushes it down a chain, so its hash stays valid.
 // - The hashes stay on the device in ONE array val[reference] (val[0] = 0), doubled in place when full.  The device holds no child table: per batch the host uploads the
 //   whole description of the work -- the changed leaves as (slot, key, value) and the dirty inner nodes as (node, left, right) triples grouped by depth, deepest first --
-//   and rehashes only those: zkc_tree_leaves, then one zkc_tree_level launch per depth with more than a wave of dirty nodes and one zkc_tree_narrow launch per maximal run
-//   of narrower depths (the top of the tree, and the one-child chains below two keys with a long common path prefix: up to nLevels levels in one launch instead of one
-//   launch each).  Kernels live in zkc_witness.hip beside poseidon_trace29.
+//   and rehashes only those: zkc_tree_leaves, then zkc_hash_levels (zkc_census.hip, shared with the static builder): one zkc_tree_level launch per depth with more than
+//   a wave of dirty nodes and one zkc_tree_narrow launch per maximal run of narrower depths (the top of the tree, and the one-child chains below two keys with a long
+//   common path prefix: up to nLevels levels in one launch instead of one launch each).  Kernels live in zkc_witness.hip beside poseidon_trace29, declared in zkc_kernels.h.
 //
 // arbo semantics as zkc_smt_build pins them: leaf = H(key, value, 1), node = H(left, right), path bit i = bit i of the key (LSB first), an empty subtree is 0, a subtree
 // holding one leaf is that leaf's hash; inner nodes sit at depths 0 .. nLevels - 1.  Inserting walks from the root along the key bits: at an empty child the leaf goes
@@ -26,24 +26,14 @@
 // by a delete is not copied (its hash does not depend on its depth).  The clones are the nodes the commit rehashes anyway, so path copying adds no hashing.  A pinned
 // reference a change would free is retired with its [birth, death) versions instead; releasing a snapshot frees the retired references no live snapshot falls into.
 // Without a live snapshot nothing is pinned and every change takes the path it took before snapshots existed, reference for reference.
-#include "zkc_internal.h"
-#include "zkc_field.h"
+#include "zkc_census_host.h"
+#include "zkc_kernels.h"
 #include <algorithm>
-#include <chrono>
-#include <cstring>
 #include <mutex>
 #include <set>
 #include <vector>
 
 using namespace zkc;
-
-extern "C" __global__ void zkc_tree_leaves(PoseidonTable, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*);
-extern "C" __global__ void zkc_tree_level(PoseidonTable, const uint32_t*, uint32_t, uint32_t*);
-extern "C" __global__ void zkc_tree_narrow(PoseidonTable, const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void zkc_census_hash(PoseidonTable, int, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, size_t);
-extern "C" __global__ void zkc_census_scatter(const uint32_t*, const uint2*, size_t, uint32_t*);
-extern "C" __global__ void zkc_census_scalars(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
-                                              const uint32_t*, const uint32_t*, size_t, int, uint32_t*);
 
 namespace {
 // what every handle of one tree shares: the trie, the device values, the buffers, the mutex
@@ -87,15 +77,8 @@ struct zkc_tree {
 namespace {
 constexpr uint8_t LEAF = 0xff;
 constexpr uint8_t FREED = 0xfe;               // depth of a reference freed by the current call (never a real depth: nLevels <= 253)
-constexpr uint32_t WAVE = 64;                // a depth with at most this many dirty nodes is narrow
 constexpr uint64_t MAX_REFS = 0xfffffff0ull;
 const char* const BROKEN = "zkc_tree: the tree is broken by an earlier device failure";
-
-inline int key_bit(const uint8_t* key, int d) { return (key[d >> 3] >> (d & 7)) & 1; }
-inline bool below_r(const uint8_t* v) { uint32_t t[8]; memcpy(t, v, 32); return fp_std_lt_p<FrParams>(t); }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-using clk = std::chrono::steady_clock;
-inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
 inline const uint8_t* leaf_key(const zkc_store* s, uint32_t r) { return s->keys.data() + 32 * (size_t)s->a[r]; }
 inline uint8_t* leaf_val(zkc_store* s, uint32_t r) { return s->vals.data() + 32 * (size_t)s->a[r]; }
@@ -122,11 +105,14 @@ uint32_t new_leaf(zkc_store* s, const uint8_t* key, const uint8_t* val) {
     }
     return new_ref(s, li, 0, LEAF);
 }
-void free_ref(zkc_store* s, uint32_t r) {
-    if (s->depth[r] == LEAF) s->freed_rows.push_back(s->a[r]);
+// r (and its leaf row) onto the given lists: a running change frees into freed_refs / freed_rows, which join the free lists only after its commit (free_ref); with no
+// change running, unpin frees into the free lists themselves
+void free_into(zkc_store* s, uint32_t r, std::vector<uint32_t>& refs, std::vector<uint32_t>& rows) {
+    if (s->depth[r] == LEAF) rows.push_back(s->a[r]);
     s->depth[r] = FREED; s->a[r] = s->b[r] = 0;
-    s->freed_refs.push_back(r);
+    refs.push_back(r);
 }
+void free_ref(zkc_store* s, uint32_t r) { free_into(s, r, s->freed_refs, s->freed_rows); }
 // a reference the change drops: freed, or retired untouched while a snapshot may still read it
 void release(zkc_store* s, uint32_t r) {
     if (pinned(s, r)) s->retired.push_back({r, s->birth[r], s->cur}); else free_ref(s, r);
@@ -148,24 +134,24 @@ void own_path(zkc_tree* t, const uint8_t* key, size_t k) {
 inline void mark(zkc_store* s, uint32_t r, std::vector<uint32_t>& list) { if (!s->dirty[r]) { s->dirty[r] = 1; list.push_back(r); } }
 void mark_path(zkc_store* s) { for (uint32_t r : s->path) mark(s, r, s->dirty_nodes); }
 
-// the leaf reference of `key` in t's tree (0: absent); t->s->path = the inner nodes from the root down to where the walk ended
-uint32_t find(zkc_tree* t, const uint8_t* key) {
+// the walk from t's root along the key's path bits: returns where it ends, a leaf (of this key or another) or an empty child (0); t->s->path = the inner nodes passed,
+// root first, so the end hangs below path[d - 1] on side key bit d - 1 with d = path.size() (below the root handle when d = 0)
+uint32_t descend(zkc_tree* t, const uint8_t* key) {
     zkc_store* s = t->s;
     s->path.clear();
     uint32_t r = t->root;
-    for (int d = 0; r; d++) {
-        if (s->depth[r] == LEAF) return memcmp(leaf_key(s, r), key, 32) == 0 ? r : 0;
-        s->path.push_back(r);
-        r = child(s, r, key_bit(key, d));
-    }
-    return 0;
+    for (int d = 0; r && s->depth[r] != LEAF; d++) { s->path.push_back(r); r = child(s, r, key_bit(key, d)); }
+    return r;
+}
+// the leaf reference of `key` in t's tree (0: absent); t->s->path as descend leaves it
+uint32_t find(zkc_tree* t, const uint8_t* key) {
+    const uint32_t r = descend(t, key);
+    return r && memcmp(leaf_key(t->s, r), key, 32) == 0 ? r : 0;
 }
 int32_t add_one(zkc_tree* t, const uint8_t* key, const uint8_t* val) {
     if (!below_r(key) || !below_r(val)) return ZKC_TREE_NOT_BELOW_R;
     zkc_store* s = t->s;
-    s->path.clear();
-    uint32_t r = t->root; int d = 0;
-    for (; r && s->depth[r] != LEAF; d++) { s->path.push_back(r); r = child(s, r, key_bit(key, d)); }
+    const uint32_t r = descend(t, key); const int d = (int)s->path.size();
     // r: the empty child or the leaf at depth d where the walk ended, below path[d - 1] on side key bit d - 1 (the root when d = 0)
     if (r == 0) {                                                                  // an empty child: the leaf goes here
         own_path(t, key, d);
@@ -277,11 +263,11 @@ int commit(zkc_store* s, clk::time_point t0) {
     }
     const size_t K = s->dirty_leaves.size(), M = s->dirty_nodes.size();
     if (!K && !M) { s->ms[0] = ms_since(t0); s->ms[1] = 0; return ZKC_OK; }
-    // the dirty nodes by depth, deepest first: position of depth d's first triple = pos[d]
+    // the dirty nodes by depth, deepest first (depth d is the (D - 1 - d)-th deepest): the k-th deepest depth's triples are off[k] .. off[k + 1], off[D] = M
     int D = 0; for (uint32_t r : s->dirty_nodes) D = std::max(D, s->depth[r] + 1);
-    std::vector<uint32_t> cnt(D, 0), pos(D + 1, 0);
-    for (uint32_t r : s->dirty_nodes) cnt[s->depth[r]]++;
-    { uint32_t p = 0; for (int d = D - 1; d >= 0; d--) { pos[d] = p; p += cnt[d]; } pos[D] = 0; }
+    std::vector<uint32_t> off(D + 1, 0);
+    for (uint32_t r : s->dirty_nodes) off[D - s->depth[r]]++;
+    for (int k = 0; k < D; k++) off[k + 1] += off[k];
     // one upload: [slots K][keys K x 32 B][values K x 32 B][triples M x 3][offsets: position of the k-th deepest depth, D + 1]
     const size_t o_keys = align256(4 * K), o_vals = o_keys + align256(32 * K), o_trip = o_vals + align256(32 * K), o_off = o_trip + align256(12 * M), total = o_off + 4 * ((size_t)D + 1);
     int rc;
@@ -293,10 +279,9 @@ int commit(zkc_store* s, clk::time_point t0) {
         const uint32_t r = s->dirty_leaves[i];
         hs[i] = r; memcpy(h + o_keys + 32 * i, leaf_key(s, r), 32); memcpy(h + o_vals + 32 * i, leaf_val(s, r), 32);
     }
-    { std::vector<uint32_t> fill(pos.begin(), pos.end() - 1);
-      for (uint32_t r : s->dirty_nodes) { uint32_t* q = ht + 3 * (size_t)fill[s->depth[r]]++; q[0] = r; q[1] = s->a[r]; q[2] = s->b[r]; } }
-    for (int k = 0; k < D; k++) ho[k] = pos[D - 1 - k];
-    ho[D] = (uint32_t)M;
+    { std::vector<uint32_t> fill(off.begin(), off.end() - 1);
+      for (uint32_t r : s->dirty_nodes) { uint32_t* q = ht + 3 * (size_t)fill[D - 1 - s->depth[r]]++; q[0] = r; q[1] = s->a[r]; q[2] = s->b[r]; } }
+    memcpy(ho, off.data(), 4 * ((size_t)D + 1));
     // every reference a kernel will follow is below the number of references (and so below val's capacity, grown to it next)
     for (size_t i = 0; i < K; i++) if (hs[i] == 0 || hs[i] >= nref) return zkc_fail(ctx, ZKC_ERR_GENERIC, "zkc_tree: leaf slot out of range");
     for (size_t i = 0; i < 3 * M; i++) if (ht[i] >= nref || (i % 3 == 0 && ht[i] == 0)) return zkc_fail(ctx, ZKC_ERR_GENERIC, "zkc_tree: node reference out of range");
@@ -310,17 +295,7 @@ int commit(zkc_store* s, clk::time_point t0) {
     const uint32_t* dt = (const uint32_t*)(dst + o_trip); const uint32_t* dof = (const uint32_t*)(dst + o_off);
     if (K) hipLaunchKernelGGL(zkc_tree_leaves, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, ctx->stream, ctx->ptab, (const uint32_t*)dst, (const uint32_t*)(dst + o_keys),
                               (const uint32_t*)(dst + o_vals), (uint32_t)K, s->d_val);
-    for (int k = 0; k < D;) {                        // k-th deepest depth
-        const uint32_t c = ho[k + 1] - ho[k];
-        if (c > WAVE) {
-            hipLaunchKernelGGL(zkc_tree_level, dim3((c + 63) / 64), dim3(64), 0, ctx->stream, ctx->ptab, dt + 3 * (size_t)ho[k], c, s->d_val);
-            k++;
-        } else {
-            int j = k; while (j < D && ho[j + 1] - ho[j] <= WAVE) j++;
-            hipLaunchKernelGGL(zkc_tree_narrow, dim3(1), dim3(64), 0, ctx->stream, ctx->ptab, dt, dof + k, (uint32_t)(j - k), (uint32_t)M, s->d_val);
-            k = j;
-        }
-    }
+    zkc_hash_levels(ctx, dt, dof, ho, D, (uint32_t)M, s->d_val);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     s->ms[1] = ms_since(t1);
@@ -363,9 +338,7 @@ void unpin(zkc_store* s) {
     for (const zkc_store::Retired& e : s->retired) {
         const auto it = s->snaps.lower_bound(e.birth);
         if (it != s->snaps.end() && *it < e.death) { s->retired[k++] = e; continue; }
-        if (s->depth[e.ref] == LEAF) s->free_rows.push_back(s->a[e.ref]);
-        s->depth[e.ref] = FREED; s->a[e.ref] = s->b[e.ref] = 0;
-        s->free_refs.push_back(e.ref);
+        free_into(s, e.ref, s->free_refs, s->free_rows);
     }
     s->retired.resize(k);
 }
@@ -400,6 +373,27 @@ int write_siblings(zkc_store* s, const std::vector<uint2>& pairs, size_t words, 
     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(siblings, s->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKC_OK;
+}
+// what zkc_tree_gen_proof and zkc_tree_gen_absence_proof share (`name`: the entry point, for the error text): the locks, the broken and 32-bit slot checks, then per
+// key per_key(i, key), which fills that key's outputs and says whether its sibling list, for the path its walk left in s->path, goes out; then the root and the siblings
+template <class PerKey>
+int gen_proofs(zkc_tree* t, const char* name, const void* keys, size_t n, uint8_t root[32], void* siblings, PerKey per_key) {
+    zkc_store* s = t->s;
+    std::lock_guard<std::mutex> g(s->mu);
+    zkc_ctx* ctx = s->ctx;
+    ZKC_LOCK(ctx);
+    if (s->broken) return zkc_fail(ctx, ZKC_ERR_HIP, BROKEN);
+    const size_t stride = (size_t)s->nLevels + 1;
+    if ((uint64_t)n * stride >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, std::string(name) + ": too many keys for 32-bit slots");
+    std::vector<uint2> pairs;
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t* key = (const uint8_t*)keys + 32 * i;
+        if (per_key(i, key) && siblings) sibling_pairs(s, key, i * stride, pairs);
+    }
+    int rc;
+    if ((rc = read_root(t, root))) return rc;
+    if (!siblings || !n) return ZKC_OK;
+    return write_siblings(s, pairs, n * stride, siblings);
 }
 }  // namespace
 
@@ -516,25 +510,12 @@ extern "C" int zkc_tree_get(zkc_tree* t, const void* keys, size_t n, void* value
 
 extern "C" int zkc_tree_gen_proof(zkc_tree* t, const void* keys, size_t n, uint8_t root[32], void* siblings, int32_t* depths, int32_t* exists) {
     if (!t || !root || (n && (!keys || !exists))) return zkc_fail(t ? t->s->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_gen_proof: bad argument");
-    zkc_store* s = t->s;
-    std::lock_guard<std::mutex> g(s->mu);
-    zkc_ctx* ctx = s->ctx;
-    ZKC_LOCK(ctx);
-    if (s->broken) return zkc_fail(ctx, ZKC_ERR_HIP, BROKEN);
-    const size_t stride = (size_t)s->nLevels + 1;
-    if ((uint64_t)n * stride >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_gen_proof: too many keys for 32-bit slots");
-    std::vector<uint2> pairs;
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* key = (const uint8_t*)keys + 32 * i;
+    return gen_proofs(t, "zkc_tree_gen_proof", keys, n, root, siblings, [&](size_t i, const uint8_t* key) {
         const uint32_t l = find(t, key);
         exists[i] = l != 0;
-        if (depths) depths[i] = l ? (int32_t)s->path.size() : 0;
-        if (l && siblings) sibling_pairs(s, key, i * stride, pairs);
-    }
-    int rc;
-    if ((rc = read_root(t, root))) return rc;
-    if (!siblings || !n) return ZKC_OK;
-    return write_siblings(s, pairs, n * stride, siblings);
+        if (depths) depths[i] = l ? (int32_t)t->s->path.size() : 0;
+        return l != 0;
+    });
 }
 
 // arbo GenProof for absent keys (circomlib SMTVerifier, fnc = 1): where the key's path ends -- an empty child (is_old0 = 1) or a leaf of another key (is_old0 = 0, its
@@ -543,33 +524,19 @@ extern "C" int zkc_tree_gen_absence_proof(zkc_tree* t, const void* keys, size_t 
                                           int32_t* is_old0, int32_t* status) {
     if (!t || !root || (n && (!keys || !old_keys || !old_values || !is_old0 || !status)))
         return zkc_fail(t ? t->s->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_tree_gen_absence_proof: bad argument");
-    zkc_store* s = t->s;
-    std::lock_guard<std::mutex> g(s->mu);
-    zkc_ctx* ctx = s->ctx;
-    ZKC_LOCK(ctx);
-    if (s->broken) return zkc_fail(ctx, ZKC_ERR_HIP, BROKEN);
-    const size_t stride = (size_t)s->nLevels + 1;
-    if ((uint64_t)n * stride >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_gen_absence_proof: too many keys for 32-bit slots");
-    std::vector<uint2> pairs;
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* key = (const uint8_t*)keys + 32 * i;
+    return gen_proofs(t, "zkc_tree_gen_absence_proof", keys, n, root, siblings, [&](size_t i, const uint8_t* key) {
+        zkc_store* s = t->s;
         uint8_t* ok = (uint8_t*)old_keys + 32 * i; uint8_t* ov = (uint8_t*)old_values + 32 * i;
         memset(ok, 0, 32); memset(ov, 0, 32); is_old0[i] = 0;
         if (depths) depths[i] = 0;
-        if (!below_r(key)) { status[i] = ZKC_TREE_NOT_BELOW_R; continue; }
-        s->path.clear();
-        uint32_t r = t->root;
-        for (int d = 0; r && s->depth[r] != LEAF; d++) { s->path.push_back(r); r = child(s, r, key_bit(key, d)); }
-        if (r && memcmp(leaf_key(s, r), key, 32) == 0) { status[i] = ZKC_TREE_KEY_EXISTS; continue; }
+        if (!below_r(key)) { status[i] = ZKC_TREE_NOT_BELOW_R; return false; }
+        const uint32_t r = descend(t, key);
+        if (r && memcmp(leaf_key(s, r), key, 32) == 0) { status[i] = ZKC_TREE_KEY_EXISTS; return false; }
         status[i] = ZKC_TREE_OK;
         if (r) { memcpy(ok, leaf_key(s, r), 32); memcpy(ov, leaf_val(s, r), 32); } else is_old0[i] = 1;
         if (depths) depths[i] = (int32_t)s->path.size();
-        if (siblings) sibling_pairs(s, key, i * stride, pairs);
-    }
-    int rc;
-    if ((rc = read_root(t, root))) return rc;
-    if (!siblings || !n) return ZKC_OK;
-    return write_siblings(s, pairs, n * stride, siblings);
+        return true;
+    });
 }
 
 // zkc_census_inputs for n voters of two resident trees (include/zkcensus.h): the SIK and nullifier hashed on the GPU, availableWeight and both sibling lists from the trees.
@@ -582,15 +549,13 @@ extern "C" int zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n,
         !password || !signature || !vote_weight || !vote_hash || (!inputs_out && !d_inputs_out) || !status)
         return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: bad argument");
     const uint8_t *addr = (const uint8_t*)address, *pw = (const uint8_t*)password, *sg = (const uint8_t*)signature, *vw = (const uint8_t*)vote_weight, *vh = (const uint8_t*)vote_hash;
-    for (size_t i = 0; i < 2 * n; i++)
-        if ((i < 2 && !below_r(election_id + 32 * i)) || !below_r(vh + 32 * i) || (i < n && (!below_r(addr + 32 * i) || !below_r(pw + 32 * i) || !below_r(sg + 32 * i) || !below_r(vw + 32 * i))))
-            return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: a value is not below the field order");
+    if (!all_below_r(election_id, 2) || !all_below_r(addr, n) || !all_below_r(pw, n) || !all_below_r(sg, n) || !all_below_r(vw, n) || !all_below_r(vh, 2 * n))
+        return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: a value is not below the field order");
     std::unique_lock<std::mutex> gc(cs->mu, std::defer_lock), gs(ss->mu, std::defer_lock);
     if (cs == ss) gc.lock(); else std::lock(gc, gs);
     ZKC_LOCK(ctx);
     if (cs->broken || ss->broken) return zkc_fail(ctx, ZKC_ERR_HIP, BROKEN);
-    const int nLevels = cs->nLevels;
-    const size_t nIn = 12 + 2 * ((size_t)nLevels + 1);
+    const InputBlock L(cs->nLevels); const size_t nIn = L.nIn;
     if ((uint64_t)n * nIn >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_tree_census_inputs: too many voters for 32-bit slots");
     // the trees: per voter its stored weight and stored SIK, its two sibling lists (kept per voter until the SIK check says whether it goes out)
     std::vector<uint8_t> avail(32 * n, 0), stored_sik(32 * n, 0);
@@ -600,16 +565,16 @@ extern "C" int zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n,
         status[i] = ZKC_TREE_OK;
         const uint32_t lc = find(census, key);
         if (!lc) status[i] = ZKC_TREE_NOT_IN_CENSUS;
-        else { memcpy(&avail[32 * i], leaf_val(cs, lc), 32); sibling_pairs(cs, key, i * nIn + 12, pc); }
+        else { memcpy(&avail[32 * i], leaf_val(cs, lc), 32); sibling_pairs(cs, key, i * nIn + L.census_sibs, pc); }
         const uint32_t ls = find(sik, key);
         if (!ls) { if (!status[i]) status[i] = ZKC_TREE_NOT_IN_SIK; }
-        else { memcpy(&stored_sik[32 * i], leaf_val(ss, ls), 32); sibling_pairs(ss, key, i * nIn + 12 + (size_t)nLevels + 1, ps); }
+        else { memcpy(&stored_sik[32 * i], leaf_val(ss, ls), 32); sibling_pairs(ss, key, i * nIn + L.sik_sibs, ps); }
         pc_end[i] = pc.size(); ps_end[i] = ps.size();
     }
-    // uploads: election id, address, password, signature, availableWeight, voteWeight, voteHash; then SIK and nullifier out; then the pairs (at most pc + ps + 12 n)
+    // uploads: election id, address, password, signature, availableWeight, voteWeight, voteHash; then SIK and nullifier out; then the pairs (at most pc + ps + 12 n: the scalar slots of refused voters)
     const size_t o_eid = 0, o_addr = 256, o_pw = o_addr + align256(32 * n), o_sig = o_pw + align256(32 * n), o_av = o_sig + align256(32 * n), o_vw = o_av + align256(32 * n),
                  o_vh = o_vw + align256(32 * n), o_sik = o_vh + align256(64 * n), o_null = o_sik + align256(32 * n), o_pc = o_null + align256(32 * n),
-                 o_ps = o_pc + align256(8 * (pc.size() + 12 * n)), total = o_ps + 8 * ps.size() + 8;
+                 o_ps = o_pc + align256(8 * (pc.size() + L.kScalars * n)), total = o_ps + 8 * ps.size() + 8;
     int rc;
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if ((rc = stage(cs, total))) return rc;
@@ -618,17 +583,15 @@ extern "C" int zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n,
     memcpy(h + o_av, avail.data(), 32 * n); memcpy(h + o_vw, vw, 32 * n); memcpy(h + o_vh, vh, 64 * n);
     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d, h, o_sik, hipMemcpyHostToDevice, ctx->stream));
     auto D = [&](size_t o) { return (uint32_t*)(d + o); };
-    const unsigned g64 = (unsigned)((n + 63) / 64);
-    hipLaunchKernelGGL(zkc_census_hash, dim3(g64), dim3(64), 0, ctx->stream, ctx->ptab, 1, D(o_addr), D(o_pw), D(o_sig), D(o_sik), n);        // census.circom:74-77
-    hipLaunchKernelGGL(zkc_census_hash, dim3(g64), dim3(64), 0, ctx->stream, ctx->ptab, 2, D(o_sig), D(o_pw), D(o_eid), D(o_null), n);        // :105-109
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    const VoterArrays v{D(o_eid), D(o_addr), D(o_pw), D(o_sig), D(o_av), D(o_vw), D(o_vh), D(o_sik), D(o_null)};
+    if ((rc = zkc_voter_hashes(ctx, v, n))) return rc;
     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h + o_sik, d + o_sik, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     // the voters that go out: their sibling pairs; the ones that do not: their twelve scalar slots zeroed again, from val[0] = 0 (their sibling slots stay zero)
     uint2* hp = (uint2*)(h + o_pc); uint2* hq = (uint2*)(h + o_ps); size_t np = 0, nq = 0;
     for (size_t i = 0; i < n; i++) {
         if (!status[i] && memcmp(h + o_sik + 32 * i, &stored_sik[32 * i], 32) != 0) status[i] = ZKC_TREE_SIK_MISMATCH;
-        if (status[i]) { for (int k = 0; k < 12; k++) hp[np++] = make_uint2((uint32_t)(i * nIn + k), 0); continue; }
+        if (status[i]) { for (size_t k = 0; k < L.kScalars; k++) hp[np++] = make_uint2((uint32_t)(i * nIn + k), 0); continue; }
         for (size_t j = i ? pc_end[i - 1] : 0; j < pc_end[i]; j++) hp[np++] = pc[j];
         for (size_t j = i ? ps_end[i - 1] : 0; j < ps_end[i]; j++) hq[nq++] = ps[j];
     }
@@ -636,16 +599,6 @@ extern "C" int zkc_tree_census_inputs(zkc_tree* census, zkc_tree* sik, size_t n,
     if (nq) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d + o_ps, h + o_ps, 8 * nq, hipMemcpyHostToDevice, ctx->stream));
     uint32_t* d_out = (uint32_t*)d_inputs_out;
     if (!d_out) { if ((rc = zkc_ensure(ctx, &cs->d_out, &cs->d_out_sz, 32 * n * nIn))) return rc; d_out = (uint32_t*)cs->d_out; }
-    ZKC_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, 32 * n * nIn, ctx->stream));
-    const uint32_t* croot = cs->d_val + 8 * (size_t)census->root; const uint32_t* sroot = ss->d_val + 8 * (size_t)sik->root;
-    hipLaunchKernelGGL(zkc_census_scalars, dim3((unsigned)((12 * n + 255) / 256)), dim3(256), 0, ctx->stream, D(o_eid), D(o_null), D(o_av), D(o_vh), sroot, croot,
-                       D(o_addr), D(o_pw), D(o_sig), D(o_vw), n, (int)nIn, d_out);
-    if (np) hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, cs->d_val, (const uint2*)(d + o_pc), np, d_out);
-    if (nq) hipLaunchKernelGGL(zkc_census_scatter, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, ss->d_val, (const uint2*)(d + o_ps), nq, d_out);
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    if (inputs_out) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(inputs_out, d_out, 32 * n * nIn, hipMemcpyDeviceToHost, ctx->stream));
-    if (roots_out) { ZKC_HIP_CHECK(ctx, hipMemcpyAsync(roots_out, croot, 32, hipMemcpyDeviceToHost, ctx->stream));
-                     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(roots_out + 32, sroot, 32, hipMemcpyDeviceToHost, ctx->stream)); }
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return ZKC_OK;
+    return zkc_write_input_blocks(ctx, v, n, L, cs->d_val, census->root, ss->d_val, sik->root, (const uint2*)(d + o_pc), np, (const uint2*)(d + o_ps), nq, d_out, inputs_out,
+                                  roots_out);
 }

@@ -19,6 +19,7 @@
 #include "zkc_field.h"
 #include "zkc_device.h"
 #include "zkc_f29.h"
+#include "zkc_kernels.h"
 
 namespace zkc {
 
@@ -582,7 +583,8 @@ zkc_poseidon_batch_kernel(PoseidonTable tab, const uint32_t* __restrict__ in, ui
 }
 
 // ---- f1: the hashing of the census builder (csrc/zkc_census.hip: arbo-style Poseidon sparse Merkle trees, internal/helpers.go:36-85), one lane per hash, standard form in and
-// out.  The tree's values live in ONE array: val[0] = 0 (an empty subtree), val[1 + i] = leaf i, val[1 + n + j] = inner node j. ----
+// out.  The tree's values live in ONE array: val[0] = 0 (an empty subtree), val[1 + i] = leaf i, val[1 + n + j] = inner node j; the inner nodes
+// are hashed by the triple kernels below, which the static builder shares with the resident tree. ----
 __device__ __forceinline__ void store_std(uint32_t* p, const Fr& h) {
     uint32_t s[8]; fp_to_std<FrParams>(s, h);
     uint4* d = reinterpret_cast<uint4*>(p); d[0] = make_uint4(s[0], s[1], s[2], s[3]); d[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -602,20 +604,9 @@ zkc_census_hash(PoseidonTable tab, int kind, const uint32_t* __restrict__ a, con
     else { x[2] = load_std(c); x[3] = load_std(c + 8); h = poseidon_trace29<5, 1>(x, 1u, tab, none, 0); }
     store_std(out + 8 * i, h);
 }
-// the inner nodes of one depth: node j = order[first + t] gets val[node0 + j] = H(val[left[j]], val[right[j]]) (children one level down are finished: launches go bottom-up)
-extern "C" __global__ void __launch_bounds__(64)
-zkc_census_level(PoseidonTable tab, const uint32_t* __restrict__ left, const uint32_t* __restrict__ right, const uint32_t* __restrict__ order, uint32_t first, uint32_t count,
-                 uint32_t* val, uint32_t node0) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const uint32_t j = order[first + t];
-    Emit none{nullptr};
-    Fr x[2]; x[0] = load_std(val + 8 * (size_t)left[j]); x[1] = load_std(val + 8 * (size_t)right[j]);
-    store_std(val + 8 * ((size_t)node0 + j), poseidon_trace29<3, 0>(x, 1u, tab, none, 0));
-}
-// ---- f1, the resident tree (csrc/zkc_tree.hip): val is indexed by node reference (0 = empty, leaves and inner nodes share the space); the host uploads the work of a batch
-// as lists whose references it has checked against the capacity of val: the changed leaves as (slot, key, value) and the dirty inner nodes as (node, left, right) triples,
-// grouped by depth, deepest first. ----
+// ---- f1, hashing from lists (the resident tree of csrc/zkc_tree.hip per batch; the inner nodes of the static builder too, through zkc_hash_levels): val is indexed by node
+// reference (0 = empty, leaves and inner nodes share the space); the host uploads the work as lists whose references are below the size of val (checked per batch by the tree, so
+// by construction in the builder): the changed leaves as (slot, key, value), the inner nodes to hash as (node, left, right) triples grouped by depth, deepest first. ----
 // val[slot[i]] = H(key[i], value[i], 1)
 extern "C" __global__ void __launch_bounds__(64)
 zkc_tree_leaves(PoseidonTable tab, const uint32_t* __restrict__ slot, const uint32_t* __restrict__ key, const uint32_t* __restrict__ value, uint32_t count, uint32_t* val) {
