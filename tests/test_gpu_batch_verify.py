@@ -113,3 +113,82 @@ def test_batch_verify_gpu_path_odd_sizes_and_several_rounds():
         finally:
             os.environ.pop('ZKC_VERIFY_CHUNK', None)
     pk.close(); ctx.close()
+
+
+# ---- the G1 side and tiny batches: sizes whose product tree has one or two levels (and a lone, dense line in the odd slot), members at infinity, signals 0 and r - 1, and a
+# batch whose A points are P, P, -P.  The oracle's single verdicts decide what is expected; both paths must agree with their AND. ----
+@pytest.fixture(scope='module')
+def twelve():
+    """Twelve honest proofs at nLevels = 10, as the tests above make them: (ctx, groth16, vk, [proof], [public-signal block])"""
+    import torch, numpy as np
+    import zkcensus_amd
+    from zkcensus_amd import groth16, setup
+    from census_gen import random_voter
+    nl, base = 10, 12
+    ctx = zkcensus_amd.Context(0)
+    _, zp, vp = setup.ensure_test_artifacts(nl)
+    pk = zkcensus_amd.ProvingKey(ctx, open(zp, 'rb').read()); vk = json.load(open(vp))
+    rng = random.Random(12)
+    voters = [random_voter(rng, ol.poseidon, nLevels=nl, depth_c=rng.randint(1, nl), depth_s=rng.randint(1, nl)) for _ in range(base)]
+    ws, st = ctx.witness(voters, nLevels=nl); assert st == [0] * base
+    d = torch.from_numpy(np.frombuffer(b''.join(ws), dtype=np.uint8).copy()).cuda()
+    rs = b''.join(rng.randrange(ol.R).to_bytes(32, 'little') for _ in range(2 * base))
+    proofs, pubs = pk.prove_batch_dev(d.data_ptr(), base, rs)
+    P = [proofs[256 * i:256 * (i + 1)] for i in range(base)]; U = [pubs[256 * i:256 * (i + 1)] for i in range(base)]
+    assert all(ol.verify(vk, u, p) for p, u in zip(P, U))
+    yield ctx, groth16, vk, P, U
+    pk.close(); ctx.close()
+
+
+def _both_paths_agree_with_oracle(ctx, groth16, vk, P, U, seed=None):
+    """verify_batch with the Miller loops on host threads ('0') and on the GPU ('1') against the AND of the oracle's single verdicts; returns that AND"""
+    expected = all(ol.verify(vk, u, p) for p, u in zip(P, U))
+    for path in ('0', '1'):
+        os.environ['ZKC_VERIFY_BATCH_GPU'] = path
+        try:
+            assert groth16.verify_batch(ctx, vk, b''.join(U), b''.join(P), seed) is expected, (path, len(P))
+        finally:
+            del os.environ['ZKC_VERIFY_BATCH_GPU']
+    return expected
+
+
+@pytest.mark.parametrize('N', [2, 3, 5])
+def test_batch_verify_tiny_batches(twelve, N):
+    """N = 2, 3, 5 on the GPU path: one pair-product kernel of one or two outputs, the last pair alone in the odd slot at 3 and 5 (its sparse line made dense), a tree of one
+    or two levels.  Honest, bad member first, bad member last."""
+    ctx, groth16, vk, P, U = twelve
+    seed = bytes(range(32))
+    assert _both_paths_agree_with_oracle(ctx, groth16, vk, P[:N], U[:N], seed) is True
+    for bad_at in (0, N - 1):
+        Pb = list(P[:N]); Pb[bad_at] = Pb[bad_at][:192] + P[N][192:]                  # another proof's C: every point still on the curve
+        assert _both_paths_agree_with_oracle(ctx, groth16, vk, Pb, U[:N], seed) is False, bad_at
+    assert _both_paths_agree_with_oracle(ctx, groth16, vk, P[:N], U[:N]) is True      # weights from the OS
+
+
+@pytest.mark.parametrize('what', ['A_zero', 'C_zero', 'signals_zero', 'signals_r-1'])
+def test_batch_verify_degenerate_member(twelve, what):
+    """One member whose A or C is the 64 zero bytes (the encoding of the point at infinity) or whose public signals are all 0 / all r - 1: whatever the oracle says of that
+    member, both paths say of the batch -- and the context verifies the honest batch afterwards."""
+    ctx, groth16, vk, P, U = twelve
+    Pb, Ub, k = list(P), list(U), 4
+    if what == 'A_zero': Pb[k] = bytes(64) + Pb[k][64:]
+    elif what == 'C_zero': Pb[k] = Pb[k][:192] + bytes(64)
+    elif what == 'signals_zero': Ub[k] = bytes(256)
+    else: Ub[k] = ol.le32(ol.R - 1) * 8
+    seed = bytes(range(32))
+    for n in (12, 5):                                                                 # k = 4: in the middle of twelve, the lone last pair of five
+        _both_paths_agree_with_oracle(ctx, groth16, vk, Pb[:n], Ub[:n], seed)
+        assert _both_paths_agree_with_oracle(ctx, groth16, vk, P[:n], U[:n], seed) is True
+
+
+@pytest.mark.parametrize('first', [0, 100])
+def test_batch_verify_two_copies_and_a_negated_a(twelve, first):
+    """A, A, -A under one B: on-curve points whose weighted fold rho_1 A + rho_2 A - rho_3 A could only cancel for related weights.  The third member is invalid, so is the batch."""
+    ctx, groth16, vk, P, U = twelve
+    seed = bytes(range(first, first + 32))
+    y = int.from_bytes(P[0][32:64], 'little')
+    neg = P[0][:32] + ol.le32((ol.Q - y) % ol.Q) + P[0][64:]
+    assert not ol.verify(vk, U[0], neg)
+    for order in ([P[0], P[0], neg], [neg, P[0], P[0]], [P[0], neg, P[0]]):
+        assert _both_paths_agree_with_oracle(ctx, groth16, vk, order, [U[0]] * 3, seed) is False
+    assert _both_paths_agree_with_oracle(ctx, groth16, vk, [P[0], P[0]], [U[0]] * 2, seed) is True
