@@ -192,6 +192,25 @@ def test_small_pass_blinding_without_variable_base_products_matches_the_general_
         pk_general.close(); pk_stub.close()
 
 
+def test_key_load_switches_are_read_at_every_load_and_clamped(env):
+    """ZKC_INFLIGHT is a key-load switch (csrc/zkc_switches.h: LIVE): three loads in one process see 5, then 100000 clamped to MSM_MAX_JOBS / 4 = 128 (the per-key limit on
+    MSM entries per pass is far above that at nLevels = 10), then, with the variable removed, the census key's default of 64."""
+    zkc, ctx, pk, zk, vk, nl = env
+    old = os.environ.get('ZKC_INFLIGHT')
+    sizes = []
+    try:
+        for v in ('5', '100000', None):
+            if v is None: os.environ.pop('ZKC_INFLIGHT')
+            else: os.environ['ZKC_INFLIGHT'] = v
+            k = zkc.ProvingKey(ctx, zk)
+            sizes.append(k.pass_size)
+            k.close()
+    finally:
+        if old is None: os.environ.pop('ZKC_INFLIGHT', None)
+        else: os.environ['ZKC_INFLIGHT'] = old
+    assert sizes == [5, 128, 64]
+
+
 def test_lone_calls_soak_against_the_oracle(env):
     """Sixty inputs -> proof calls of one or two voters (the path that lays its pass out from the inputs' sibling depths while the witness kernel runs, blinds without variable-base
     products, takes the 8-bit-window G2 table and lets the host divide): random depths 0..nLevels in both trees, random (r, s), every sixth voter rejected by the circuit (weight),

@@ -24,8 +24,7 @@ int zkc_fail(zkc_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 hipError_t zkc_wait_event(hipEvent_t ev, unsigned spin_us) {
-    static const bool spin = getenv("ZKC_SPIN_WAIT") != nullptr;
-    if (spin) return hipEventSynchronize(ev);
+    if (sw::on<sw::ZKC_SPIN_WAIT>()) return hipEventSynchronize(ev);
     timespec t0; if (spin_us) clock_gettime(CLOCK_MONOTONIC, &t0);
     for (int i = 0;; i++) {
         const hipError_t e = hipEventQuery(ev);
@@ -156,7 +155,7 @@ extern "C" int zkc_ctx_create(int device, zkc_ctx** out) {
     // [r5] host threads that wait for this device SLEEP (hipStreamSynchronize and friends yield to the driver's interrupt instead of spinning on a flag): a rank of an
     // 8-GPU run has two cores' worth of CPU time on these boxes (cpu.max = 16 cores for the container, profiles/r04_cpu_baseline_scaling.json).  Best effort -- a host that
     // has already initialised the device with other flags (torch) keeps them; the events this library waits on carry hipEventBlockingSync themselves.  ZKC_SPIN_WAIT=1: leave the default.
-    { const char* eb = getenv("ZKC_DEVICE_BLOCKING_SYNC"); if (eb && atoi(eb) == 1 && hipSetDeviceFlags(hipDeviceScheduleBlockingSync) != hipSuccess) (void)hipGetLastError(); }
+    { if (sw::on<sw::ZKC_DEVICE_BLOCKING_SYNC>() && hipSetDeviceFlags(hipDeviceScheduleBlockingSync) != hipSuccess) (void)hipGetLastError(); }
     if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
     if ((e = hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate(2)");
     if ((e = hipStreamCreateWithFlags(&ctx->fin_stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate(fin)");

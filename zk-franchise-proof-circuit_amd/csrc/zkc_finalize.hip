@@ -360,7 +360,7 @@ int finalize_tree_g2_launch(zkc_ctx* ctx, hipStream_t st, const FinalizeArgs& a,
 size_t finalize_scratch_bytes(int nproofs) { return (size_t)nproofs * (7 * sizeof(G1XYZZ) + sizeof(G2XYZZ) + 2 * 16 * sizeof(Acc29)); }
 
 int finalize_launch(zkc_ctx* ctx, hipStream_t st, const FinalizeArgs& a, int nproofs) {
-    static const bool v1 = getenv("ZKC_FINALIZE_WAVES") != nullptr;          // the one-wave-per-task kernel (variable-base products on one lane each)
+    const bool v1 = sw::on<sw::ZKC_FINALIZE_WAVES>();          // the one-wave-per-task kernel (variable-base products on one lane each)
     if (a.per == 5) {           // the pass carries the two blinding sums as MSM jobs and piB has been written on the G2 stream (zkc_prove.hip)
         hipLaunchKernelGGL(zkc_blind_tree_g1, dim3(10, nproofs), dim3(64), 0, st, a);
         hipLaunchKernelGGL(zkc_blind_tree_g1_out, dim3(nproofs), dim3(128), 0, st, a);

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "zkc_json.h"
+#include "zkc_switches.h"
 
 namespace zkc { namespace parse {
 
@@ -316,7 +317,7 @@ inline bool sha_ni_available() {
         unsigned a, b, c, d;
         if (!__get_cpuid(1, &a, &b, &c, &d) || !(c & (1u << 19)) || !(c & (1u << 9))) return false;       // SSE4.1, SSSE3
         if (!__get_cpuid_count(7, 0, &a, &b, &c, &d)) return false;
-        return (b & (1u << 29)) != 0 && getenv("ZKC_NO_SHA_NI") == nullptr;                                // SHA
+        return (b & (1u << 29)) != 0 && !sw::on<sw::ZKC_NO_SHA_NI>();                                // SHA
     }();
     return ok;
 }

@@ -7,6 +7,7 @@
 #include <mutex>
 #include "../../include/zkcensus.h"
 #include "zkc_device.h"
+#include "zkc_switches.h"
 
 #define ZKC_LOCK(ctx) std::lock_guard<std::recursive_mutex> _zkc_guard((ctx)->mu)
 #define ZKC_HIP_CHECK(ctx, call)                                                                            \

@@ -643,7 +643,7 @@ void msm_work_free(MsmWork& w) {
     w = MsmWork();
 }
 
-static const bool g_debug_sync = getenv("ZKC_DEBUG_SYNC") != nullptr;   // serialise + log every launch (diagnostics only)
+static const bool g_debug_sync = sw::on<sw::ZKC_DEBUG_SYNC>();   // serialise + log every launch (diagnostics only)
 #define ZKC_LAUNCH_CHECK(ctx, name)                                                                        \
     do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess)                                          \
         return zkc_fail((ctx), ZKC_ERR_HIP, std::string(name ": ") + hipGetErrorString(_e));               \
@@ -672,10 +672,9 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
     // serially, so a small pass (one proof) wants short ones: aim at ~2 waves per SIMD
     const uint32_t seg = (uint32_t)std::min<size_t>(MSM_SEG, std::max<size_t>(MSM_SEG_MIN, total / 131072));
     constexpr bool kG2 = sizeof(F) == sizeof(Fq2);
-    static const bool bw_off = [] { const char* e = getenv("ZKC_G2_BUCKET_WAVE"); return e && atoi(e) == 0; }();
     const uint32_t bw_slices = (uint32_t)std::min<size_t>(32, w.max_segments / std::max<uint32_t>(nb, 1u));      // slices a heavy bucket may be cut into: nb x slices partial sums must fit
     const uint32_t* const g2_table29 = (kG2 && jl.job[0].c == (uint32_t)MSM_C_G2_LONE) ? zk->d_g2_29_lone : (kG2 && zk->c_deep && jl.job[0].c == (uint32_t)zk->c_deep) ? zk->d_g2_29_deep : zk->d_g2_29;       // a G2 pass is of one window size
-    const bool bucket_wave = kG2 && !bw_off && nb <= 8192 && bw_slices >= 1;         // a small G2 pass: half a wave per bucket (zkc_msm_bucketwave_g2), no segment lists
+    const bool bucket_wave = kG2 && sw::on<sw::ZKC_G2_BUCKET_WAVE>() && nb <= 8192 && bw_slices >= 1;         // a small G2 pass: half a wave per bucket (zkc_msm_bucketwave_g2), no segment lists
     uint64_t alg_bytes = 0; uint32_t maxcount = 0;
     uint64_t streamed_bytes = 0;
     for (int j = 0; j < nj; j++) {
@@ -714,8 +713,7 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
     XYZZ<F>* wres = reinterpret_cast<XYZZ<F>*>(w.wres);
     XYZZ<F>* results = reinterpret_cast<XYZZ<F>*>(w.results) + (size_t)slot * w.max_jobs;
     if (wait_before_acc) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, wait_before_acc, 0));      // hold the (VALU-bound) accumulation until the other stream reaches its memory-bound phase
-    static const bool acc_chain_on = [] { const char* e = getenv("ZKC_ACC_CHAIN"); return !(e && atoi(e) == 0); }();
-    const bool acc_chain = !kG2 && acc_chain_on && total >= ((size_t)1 << 22);       // (a lone proof's 0.2 ms accumulation is not worth an event)
+    const bool acc_chain = !kG2 && sw::on<sw::ZKC_ACC_CHAIN>() && total >= ((size_t)1 << 22);       // (a lone proof's 0.2 ms accumulation is not worth an event)
     if (acc_chain) {
         if (!ctx->ev_acc_chain) ZKC_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_acc_chain, hipEventDisableTiming));
         if (ctx->acc_chain_armed) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_acc_chain, 0));
@@ -730,7 +728,7 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
                                w.heavy + MSM_MAX_HEAVY, reinterpret_cast<XYZZ<Fq2>*>(partial), nb, bw_slices);
           }
           else {
-            static const int g2_form = [] { const char* e = getenv("ZKC_G2_ACC"); return e ? atoi(e) : 0; }();      // 0: registers hold the next row (one wave per SIMD); 1 / 2: LDS-DMA prefetch at one / two waves per SIMD
+            const int g2_form = (int)sw::value<sw::ZKC_G2_ACC>(0);      // 0: registers hold the next row (one wave per SIMD); 1 / 2: LDS-DMA prefetch at one / two waves per SIMD
             if (g2_form == 2)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_accumulate29_g2_dma<2>), dim3((unsigned)((seg_bound + G2DMA_T - 1) / G2DMA_T)), dim3(G2DMA_T), 0, st,
                                    g2_table29, (const MsmJobList*)w.d_jobs, w.vals2, w.off, w.bcnt, w.segoff, w.seg2bucket, w.perm, nb, reinterpret_cast<XYZZ<Fq2>*>(partial), (uint32_t)w.max_segments);

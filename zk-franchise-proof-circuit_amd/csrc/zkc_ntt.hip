@@ -423,7 +423,7 @@ int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv2
     // instructions per butterfly; alternating on one box 3196 / 3166 against 3175 / 3146 proofs/s, +0.65 %, equal on a second box).  ZKC_NTT_RADIX=1: one stage at a time, the
     // round-2 form ("measured slower two at a time" was true of the round-2 pipeline, whose transforms ran alone).  Three stages at a time on eight slots was built and measured
     // too: 137 instead of 145 instructions per element and stage, but 162-168 VGPRs (three waves per SIMD instead of four) -- 2856 / 2845 against 2997 / 2990 proofs/s, -5 %; removed.
-    static const int radix = [] { const char* e = getenv("ZKC_NTT_RADIX"); return e ? atoi(e) : 4; }();
+    const int radix = (int)sw::value<sw::ZKC_NTT_RADIX>(4);
     auto head = radix >= 4 ? zkc_ntt_nr_head_r4 : zkc_ntt_nr_head;
     hipLaunchKernelGGL(head, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_inv29, logn, 0, b1);
     if (b2) hipLaunchKernelGGL(head, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_inv29, logn, b1, b2);

@@ -104,10 +104,7 @@ static MillerConsts miller_consts() {
 }
 static int dev_fail(zkc_ctx* ctx, hipError_t e, const char* what) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); (void)hipGetLastError(); return ZKC_ERR_HIP; }
 
-static uint32_t verify_chunk() {                                              // pairs per round of kernels (tests shrink it to walk several rounds with a few hundred proofs)
-    const char* ce = getenv("ZKC_VERIFY_CHUNK");
-    return ce ? (uint32_t)std::min(16384, std::max(2, atoi(ce))) : 16384u;
-}
+static uint32_t verify_chunk() { return (uint32_t)sw::value<sw::ZKC_VERIFY_CHUNK>(16384); }      // pairs per round of kernels (tests shrink it to walk several rounds with a few hundred proofs)
 static uint32_t n_lines(const MillerConsts& C) { return 66 + (uint32_t)__builtin_popcountll(C.pos | C.neg); }
 void miller_join(zkc_ctx* ctx) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamSynchronize(ctx->fin_stream); }
 
@@ -144,7 +141,7 @@ int miller_product_dev(zkc_ctx* ctx, const G1XYZZ* d_P, uint32_t N, Fq12* produc
     const AteLoop& L = ate_loop(); const MillerConsts C = miller_consts();
     const uint32_t nlines = n_lines(C), CHUNK = verify_chunk();
     const uint32_t cap = std::min(N, CHUNK), hcap = (cap + 1) / 2;
-    const bool vtrace = getenv("ZKC_VERIFY_TRACE") != nullptr;
+    const bool vtrace = sw::on<sw::ZKC_VERIFY_TRACE>();
     auto vnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double mt0 = vnow(); double mt_chunks = 0;
     std::vector<Fq12> step(nlines), acc(nlines, one12());

@@ -22,8 +22,7 @@ using namespace zkc;
 // the pair runs in place, the two-transform form writes it afterwards) when it is large enough for nVars elements per proof
 static void matvec_launch(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv) {
     const uint32_t n = zk->n, nv = zk->nVars;
-    static const bool unit_off = [] { const char* e = getenv("ZKC_MATVEC_UNITS"); return e && atoi(e) == 0; }();
-    const bool units = zk->n_unit_coeffs > 0 && nv <= 3 * (size_t)n && !unit_off;
+    const bool units = zk->n_unit_coeffs > 0 && nv <= 3 * (size_t)n && sw::on<sw::ZKC_MATVEC_UNITS>();
     if (units) hipLaunchKernelGGL(zkc_wtns_mont, dim3((nv + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)d_wtns0, (size_t)nv, L.d_t, 3 * (size_t)n, nv);
     hipLaunchKernelGGL(zkc_matvec_jds, dim3((2 * n + 63 * zk->nlong + 255) / 256, nb), dim3(256), 0, mv, zk->d_perm, zk->d_rowlen, zk->d_jdptr, zk->d_col, zk->d_val,
                        (const Fr*)d_wtns0, (size_t)nv, L.d_abc, (int)n, zk->nlong, units ? (const Fr*)L.d_t : (const Fr*)nullptr, 3 * (size_t)n);
@@ -145,8 +144,7 @@ void zkc_ctx_lanes_destroy(zkc_ctx* ctx) {
 static int lane_init(zkc_ctx* ctx, int l) {
     zkc_lane& L = ctx_lanes(ctx)[l];
     if (L.made) return ZKC_OK;
-    static const bool red_wanted = [] { const char* e = getenv("ZKC_REDUCE_STREAM"); return e && atoi(e) == 1; }();
-    zkc_ctx::LaneStreams ls; int rc = zkc_lane_streams(ctx, l, red_wanted, &ls); if (rc) return rc;
+    zkc_ctx::LaneStreams ls; int rc = zkc_lane_streams(ctx, l, sw::on<sw::ZKC_REDUCE_STREAM>(), &ls); if (rc) return rc;
     L.st = ls.st; L.st2 = ls.st2; L.fin = ls.fin; L.red = ls.red;
     for (hipEvent_t* e : {&L.ev_msm, &L.ev_msm2, &L.ev_sorted, &L.ev_ntt, &L.ev_mv, &L.ev_acc, &L.ev_fin[0], &L.ev_fin[1], &L.ev_red}) if (!*e) ZKC_HIP_CHECK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     L.made = true; return ZKC_OK;
@@ -176,8 +174,8 @@ static int lane_ensure(zkc_zkey* zk, int l, int inflight) {
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     lane_release(L);
     const size_t free_before = dev_free_bytes();
-    const char* fail_at = getenv("ZKC_TEST_FAIL_ALLOC");          // test hook: pretend the allocation for this many proofs in flight (or more) fails
-    rc = (fail_at && inflight >= atoi(fail_at)) ? zkc_fail(ctx, ZKC_ERR_HIP, "lanes_ensure: allocation failure injected by ZKC_TEST_FAIL_ALLOC") : ZKC_OK;
+    const auto fail_at = sw::given<sw::ZKC_TEST_FAIL_ALLOC>();          // test hook: pretend the allocation for this many proofs in flight (or more) fails
+    rc = (fail_at && inflight >= *fail_at) ? zkc_fail(ctx, ZKC_ERR_HIP, "lanes_ensure: allocation failure injected by ZKC_TEST_FAIL_ALLOC") : ZKC_OK;
     if (!rc) rc = dmalloc(ctx, &L.d_abc, nd.abc);
     if (!rc) rc = dmalloc(ctx, &L.d_t, nd.abc);
     if (!rc) rc = dmalloc(ctx, &L.d_p, nd.p);
@@ -227,7 +225,7 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
         for (uint32_t i = 0; i < nv; i++) { zk->fold.infA[i] = zero64(sec[5] + 64ull * i); zk->fold.infB[i] = zero64(sec[6] + 64ull * i); if (i > np) zk->fold.infC[i] = zero64(sec[8] + 64ull * (i - np - 1)); }
     }
     // a key whose shape is ZkFranchiseProofCircuit(nLevels) can use the voter-independent witness template
-    if (np == 8 && !getenv("ZKC_NO_FOLD")) for (int nl = 3; nl <= 253; nl++) if ((uint32_t)WitnessLayout::make(nl).nWires == nv) { zk->nLevels = nl; break; }
+    if (np == 8 && !sw::on<sw::ZKC_NO_FOLD>()) for (int nl = 3; nl <= 253; nl++) if ((uint32_t)WitnessLayout::make(nl).nWires == nv) { zk->nLevels = nl; break; }
     int rc = ZKC_OK;
     auto bail = [&](int code) { zkc_zkey_free(zk); return code; };
     // from here on every failure releases the half-built key: no early return without bail()
@@ -295,16 +293,15 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     // ---- bases: one G1 array [A | B1 | C | H] and one G2 array [B2]; window 0 = the zkey points as stored (affine,
     //      Montgomery), windows 1..19 pre-shifted on the device ----
     // [r4] windows per key (msm_c_for, zkc_prover.h: the best window grows with the number of scalars):
-    auto c_for = [](size_t W) { return msm_c_for(W); };
     //   sections of a census key : 12 -- what folding leaves in a voter's MSMs is 8-11 k wires per section (13 measured equal) -- plus the deep tables below
     //   sections of any other key: by its wire count;   H: 17 for a census key (16 measured 2.7 % behind in the census pass: 3097 / 3106 against 3190 / 3174 proofs/s), else by the domain size, never below the sections'
     //   (msm_pass wants the jobs with the larger window first, and the H jobs are first)
-    { const char* e_c = getenv("ZKC_C_SECTIONS"); zk->c_sec = e_c ? std::max(8, std::min(atoi(e_c), MSM_C_BIG)) : zk->nLevels >= 0 ? MSM_C_SMALL : c_for(nv); }
-    { const char* e_h = getenv("ZKC_C_H"); zk->c_h = e_h ? std::max(8, std::min(atoi(e_h), MSM_C_BIG)) : zk->nLevels >= 0 ? MSM_C_BIG : std::max(c_for(n), n >= 12000 ? 15 : 12); }      // (H's scalars are all full width: at 2^14 points 15 bits measured 3 % ahead of 13, 17 5 % behind)
+    { const auto e_c = sw::given<sw::ZKC_C_SECTIONS>(); zk->c_sec = e_c ? (int)*e_c : zk->nLevels >= 0 ? MSM_C_SMALL : msm_c_for(nv); }
+    { const auto e_h = sw::given<sw::ZKC_C_H>(); zk->c_h = e_h ? (int)*e_h : zk->nLevels >= 0 ? MSM_C_BIG : std::max(msm_c_for(n), n >= 12000 ? 15 : 12); }      // (H's scalars are all full width: at 2^14 points 15 bits measured 3 % ahead of 13, 17 5 % behind)
     const int NWS = msm_nw(zk->c_sec);
     // (ZKC_DEEP_TABLES=0: not built; =2: built for a census key of any size -- with ZKC_DEEP_WIRES=1 the switch test drives the deep path at nLevels = 10)
-    { const char* e_d = getenv("ZKC_DEEP_TABLES"); const int dt = e_d ? atoi(e_d) : 1; const char* e_c = getenv("ZKC_C_DEEP");
-      const int cd = e_c ? std::max(13, std::min(atoi(e_c), MSM_C_BIG)) : c_for(dt == 2 ? (size_t)40000 : (size_t)nv * 4 / 5);        // a deep voter keeps most of the key's wires
+    { const int dt = (int)sw::value<sw::ZKC_DEEP_TABLES>(1); const auto e_c = sw::given<sw::ZKC_C_DEEP>();
+      const int cd = e_c ? (int)*e_c : msm_c_for(dt == 2 ? (size_t)40000 : (size_t)nv * 4 / 5);        // a deep voter keeps most of the key's wires
       zk->c_deep = (zk->nLevels >= 0 && (nv >= (1u << 16) || dt == 2) && zk->c_sec < cd && dt != 0) ? cd : 0; }
     zk->c_h = std::max(zk->c_h, std::max(zk->c_sec, zk->c_deep));
     const int NWB = msm_nw(zk->c_h);
@@ -337,8 +334,7 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
         if (e2 != hipSuccess) return bail(zkc_fail(ctx, ZKC_ERR_HIP, std::string("second section tables: ") + hipGetErrorString(e2)));
     }
     {   // [r3] the 8-bit-window G2 table of the lone-proof path (MSM_C_G2_LONE): shifted in a temporary affine table, kept in radix 2^29 only
-        const char* e_lone = getenv("ZKC_G2_LONE_TABLE");
-        if (!(e_lone && atoi(e_lone) == 0) && (zk->nLevels >= 0 || nv < (1u << 16))) {      // (a key of 2^16 wires and more that is not the census circuit: 32 x 240 B per wire for a latency path its proofs are too large to notice)
+        if (sw::on<sw::ZKC_G2_LONE_TABLE>() && (zk->nLevels >= 0 || nv < (1u << 16))) {      // (a key of 2^16 wires and more that is not the census circuit: 32 x 240 B per wire for a latency path its proofs are too large to notice)
             constexpr int NWL = msm_nw(MSM_C_G2_LONE);
             G2Affine* tmp = nullptr;
             if ((rc = dmalloc(ctx, &tmp, (size_t)NWL * nv))) return bail(rc);
@@ -354,9 +350,9 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     }
     // ---- work buffers: up to `max_inflight` proofs share one MSM pipeline pass; the buffers themselves are sized by lanes_ensure() for
     //      the number of proofs a call actually puts in flight (a single-proof caller does not reserve the work space of 96) ----
-    const char* e_inf = getenv("ZKC_INFLIGHT");
+    const auto e_inf = sw::given<sw::ZKC_INFLIGHT>();
     // [r5] a census key: passes of 64 proofs over four lanes (below); any other key: 96 (cut down by its size, next block) on one lane as before
-    zk->max_inflight = opt_inflight > 0 ? std::min(opt_inflight, MSM_MAX_JOBS / 4) : e_inf ? std::max(1, std::min(atoi(e_inf), MSM_MAX_JOBS / 4)) : zk->nLevels >= 0 ? 64 : 96;
+    zk->max_inflight = opt_inflight > 0 ? std::min(opt_inflight, MSM_MAX_JOBS / 4) : e_inf ? (int)*e_inf : zk->nLevels >= 0 ? 64 : 96;
     {   // [r4] the pass is sized for the census key (96 proofs of 7.4 M (scalar, window) entries unfolded): a larger circuit puts fewer proofs in flight -- the same ~0.7 G entries per
         // pass, which also keeps every entry index of a pass inside 32 bits (MsmJob::ent_off) -- 11 at a 2^20 domain, where ONE proof is 60 M additions and fills the chip
         const size_t per_proof_entries = (size_t)NWS * 3 * nv + (size_t)NWB * n, census_pass = 96ull * (22ull * 3 * 82754 + 15ull * 131072);
@@ -370,8 +366,8 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     // a hardware queue of its own (GPU_MAX_HW_QUEUES, zkc_api.hip) and the lanes made only when a call reaches them, the overlap that rounds 1-4 could not find is there:
     // alternating on one box, (1 lane, 96) 3243 / 3235 proofs/s, (4, 96) 3291, (4, 64) 3314 / 3308 (+2.2 %), (4, 48) 3251, (3, 64) 3179, (2, 96) 3146 / 3155.  A lone proof
     // still touches lane 0 only (0.6 GB); a 1 024-voter call all four (37 GB; ZKC_LANES=1 ZKC_INFLIGHT=96: 14 GB and the old shape).
-    { const char* e_l = getenv("ZKC_LANES"); zk->nlanes = opt_lanes > 0 ? std::min(opt_lanes, (int)MAX_LANES) : e_l ? std::max(1, std::min(atoi(e_l), (int)MAX_LANES)) : zk->nLevels >= 0 ? (int)MAX_LANES : 1; }
-    zk->serial_streams = getenv("ZKC_SERIAL_STREAMS") != nullptr;          // (lane_st)
+    { const auto e_l = sw::given<sw::ZKC_LANES>(); zk->nlanes = opt_lanes > 0 ? std::min(opt_lanes, (int)MAX_LANES) : e_l ? (int)*e_l : zk->nLevels >= 0 ? (int)MAX_LANES : 1; }
+    zk->serial_streams = sw::on<sw::ZKC_SERIAL_STREAMS>();          // (lane_st)
     // the lanes are the context's: lane 0 is made (or found) now with room for a lone caller, the others when a call first lands on them
     if ((rc = lanes_ensure(zk, 1, 0, 1))) return bail(rc);
     {   // fixed-base tables for the blinding step (delta1, alpha1, beta1 in G1; delta2 in G2)
@@ -466,8 +462,7 @@ static int fold_prepare(zkc_zkey* zk) {
 // 4-bit fixed-base tables of everything the blinding of a small pass multiplies by r or s (zkc_finalize.hip): delta1, alpha1, beta1, and -- with folding -- alpha1 and beta1
 // plus the base constants of A and B1 and the per-depth suffix constants of both trees.  960 points per base: 80 MB at nLevels = 160, built on the device in about a millisecond.
 static int fb4_prepare(zkc_zkey* zk) {
-    const char* e_off = getenv("ZKC_BLIND_TREE");                      // = 0 at key load: this key's small passes take the general blinding kernels (A/B, tests)
-    if ((e_off && atoi(e_off) == 0) || zk->d_fb4) return ZKC_OK;
+    if (!sw::on<sw::ZKC_BLIND_TREE>() || zk->d_fb4) return ZKC_OK;      // = 0 at key load: this key's small passes take the general blinding kernels (A/B, tests)
     zkc_ctx* ctx = zk->ctx;
     std::vector<G1XYZZ> bases = {G1XYZZ::from_affine(zk->delta1), G1XYZZ::from_affine(zk->alpha1), G1XYZZ::from_affine(zk->beta1)};
     const auto& f = zk->fold;
@@ -550,8 +545,7 @@ static int h_evals_dev(zkc_zkey* zk, zkc_lane& L, hipStream_t st, const uint32_t
     if (with_matvec) { int rc0 = h_matvec_dev(zk, L, d_wtns0, nb, st); if (rc0) return rc0; }
     zkc_prof_scope _pn(ctx, ZKC_PROF_NTT, (uint64_t)nb * (6ull * 2 * n * 32 + 4ull * n * 32), st);   // 6 transforms r+w, joinABC
     int rc;
-    static const bool ntt_two_transforms = getenv("ZKC_NTT_SEPARATE") != nullptr;      // diagnostics: the round-1 path (two full transforms, four HBM round trips)
-    if (!ntt_two_transforms && zk->logn >= 12 && zk->logn <= 27) {
+    if (!sw::on<sw::ZKC_NTT_SEPARATE>() && zk->logn >= 12 && zk->logn <= 27) {      // (the switch is diagnostics: the round-1 path, two full transforms, four HBM round trips)
         if ((rc = ntt_pair_run(ctx, st, L.d_abc, zk->d_tw_inv29, zk->d_tw_fwd29, zk->d_coset_br, (int)zk->logn, 3 * nb))) return rc;
     } else {
         if ((rc = ntt_run(ctx, st, L.d_abc, L.d_t, zk->d_tw_inv29, zk->d_coset, (int)zk->logn, 3 * nb))) return rc;
@@ -667,9 +661,8 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     // sibling wires of the witness itself -- on the host) begin has no GPU round trip at all: the depth kernel below is microseconds of work, but its stream waits for a
     // hardware queue behind whatever long kernels the other lanes have in flight, and begin holds the context's lock meanwhile.
     CS.early_n = 0; CS.arg_wtns = d_wtns; CS.arg_nw = nWitness; CS.arg_publics = want_publics; CS.arg_lane0 = lane0; CS.arg_inputs = d_inputs != nullptr; CS.arg_wait = nullptr;
-    static const bool early_any = [] { const char* e = getenv("ZKC_EARLY_LAYOUT"); return !(e && atoi(e) == 0); }();
     const size_t ecap = MSM_MAX_JOBS / 4;                                          // voters of a pass at most
-    const bool early_wanted = !no_early && can_fold && B <= zk->max_inflight && (B <= 2 ? zk->d_fb4 != nullptr : early_any);      // one pass
+    const bool early_wanted = !no_early && can_fold && B <= zk->max_inflight && (B <= 2 ? zk->d_fb4 != nullptr : sw::on<sw::ZKC_EARLY_LAYOUT>());      // one pass
     if (early_wanted && !CS.h_early) { ZKC_HIP_CHECK(ctx, hipHostMalloc((void**)&CS.h_early, (ecap + ecap * 2 * 256) * 4)); CS.early_cap = ecap; }      // status [ecap], then fold flags [B][2][n <= 254]
     if (early_wanted && host_depths) {
         bool ok = true; for (int i = 0; i < 2 * B; i++) ok = ok && host_depths[i] < (uint8_t)L.n && L.n <= 255;
@@ -693,7 +686,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         if ((rc = zkc_ensure(ctx, (void**)&CS.d_status3, &CS.status3_cap, std::max<size_t>((size_t)B, 256) * 3 * sizeof(int32_t)))) return rc;      // per call slot: the witness kernels of two calls may run side by side
         d_status3 = CS.d_status3;
     }
-    static const int wgroup = [] { const char* e = getenv("ZKC_WITNESS_GROUP"); return e ? std::max(1, atoi(e)) : 8; }();      // same box: 2 -> 2452, 4 -> 2472, 8 -> 2482 proofs/s at batch 1024
+    const int wgroup = (int)sw::value<sw::ZKC_WITNESS_GROUP>(8);      // same box: 2 -> 2452, 4 -> 2472, 8 -> 2482 proofs/s at batch 1024
     for (int c = 0; c < npasses; c++) {
         const int p0 = c * per_pass, nb = std::min(per_pass, B - p0);
         uint32_t* wc = (uint32_t*)d_wtns + (size_t)p0 * nv * 8;
@@ -721,7 +714,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     }
     // (npass is NOT reset per call: the result slots and their ev_fin guards carry over, because the previous call's last blinding may still be reading them)
     // ZKC_TRACE_HOST=1: where the enqueueing thread spends its time, per pass (diagnostics: a blocking call here idles a stream)
-    static const bool trace_host = getenv("ZKC_TRACE_HOST") != nullptr;
+    const bool trace_host = sw::on<sw::ZKC_TRACE_HOST>();
     auto now_ms = [] { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; };
     const double t_begin = now_ms(); double tr[6] = {0};
     int pass = 0, done_on_st_lane = -1;
@@ -749,7 +742,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         }
         static thread_local zkc_zkey::Fold::VMap vms[MSM_MAX_JOBS / 4];
         if (fold) for (int q = 0; q < nb; q++) if ((rc = fold_vmap(zk, dcq[q], dsq[q], &vms[q]))) return rc;
-        static const bool nofold_lists = [] { const char* e = getenv("ZKC_NOFOLD_LISTS"); return !(e && atoi(e) == 0); }();
+        const bool nofold_lists = sw::on<sw::ZKC_NOFOLD_LISTS>();
         if (!fold && nofold_lists) {                        // an unfolded pass still leaves out the wires whose bases are at infinity (one list set per key)
             zkc_zkey::Fold::VMap nf; if ((rc = nofold_vmap(zk, &nf))) return rc;
             for (int q = 0; q < nb; q++) vms[q] = nf;
@@ -759,8 +752,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         LN.npass++;
         // [r2] buildABC is gather-bound and needs only the witness: the one of pass p+1 is issued on the blinding stream as soon as the accumulation
         // of pass p starts (VALU-bound, 15 ms) and is through long before the G1 stream gets there; only the first pass runs it in line
-        static const bool mv_prefetch_env = getenv("ZKC_MATVEC_INLINE") == nullptr;
-        const bool mv_prefetch = mv_prefetch_env && one_lane;
+        const bool mv_prefetch = !sw::on<sw::ZKC_MATVEC_INLINE>() && one_lane;
         const bool mv_done = mv_prefetch && pass > 0;
         if (mv_done) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_mv, 0));
         // (tried for passes of a few proofs while their G2 side was the longer chain: G2 enqueued first and its accumulation not held for the transforms -- its 1024 fat waves
@@ -773,8 +765,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         // the tree -- fixed cost per wave, so a full pass wants large windows (fewer additions in all), a small one small windows (fewer in a row).  [r4] re-measured on the
         // round-4 pipeline, one box, (H, sections): (1024, 256) 3195 / 3205 / 3212 / 3214 proofs/s -- round 1's optimum, the default until now -- (2048, 512) 3235 / 3238,
         // (4096, 1024) 3229, (4096, 2048) 3248 / 3261 / 3264 / 3268 (+1.8 %), (8192, 1024) 3100.  Passes of fewer than 32 proofs keep the smaller windows (latency).
-        static const uint32_t vwb_env = [] { const char* e = getenv("ZKC_VW_BIG"); return e ? (uint32_t)atoi(e) : 0u; }();
-        static const uint32_t vws_env = [] { const char* e = getenv("ZKC_VW_SMALL"); return e ? (uint32_t)atoi(e) : 0u; }();
+        const uint32_t vwb_env = (uint32_t)sw::value<sw::ZKC_VW_BIG>(0), vws_env = (uint32_t)sw::value<sw::ZKC_VW_SMALL>(0);
         const uint32_t vws = nb <= 4 ? 64u : vws_env ? vws_env : nb < 32 ? 256u : 2048u, vwb = nb <= 4 ? 256u : vwb_env ? vwb_env : nb < 32 ? 1024u : 4096u;
         // the G2 section of one or two proofs takes the 8-bit-window table: 128 buckets per job, reduced by one wave (vw = 128), if the G2 work space holds 32 entries per scalar
         size_t lone_entries = 0; for (int q = 0; q < nb; q++) lone_entries += (size_t)msm_nw(MSM_C_G2_LONE) * (listed ? vms[q].nB : nv);
@@ -782,13 +773,13 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         // do not fold): the sections take the key's second tables (c_deep bits: msm_c_for).  Per section of W full-width scalars: 22 W + 2048 x 4.2 additions at 12 bits,
         // 17 W + 16384 x 4.2 at 15: break-even at W = 12 k by that count, at 14 k measured (profiles/r04_deep_pass_threshold.json: voters 30 levels down; +1.4 % at 40 levels,
         // +16 % at 160); a census of 2^13 .. 2^20 voters keeps 6-9 k and stays at 12 bits (-3 % if forced over the second tables).
-        static const size_t deep_wires = [] { const char* e = getenv("ZKC_DEEP_WIRES"); return e ? (size_t)atol(e) : (size_t)16000; }();
+        const size_t deep_wires = (size_t)sw::value<sw::ZKC_DEEP_WIRES>(16000);
         size_t live_wires = 0; for (int q = 0; q < nb; q++) live_wires += listed ? (size_t)vms[q].nA + vms[q].nB + vms[q].nC : 2 * (size_t)nv + nc;
         const bool deep = zk->c_deep != 0 && nb > 2 && live_wires >= 3 * deep_wires * (size_t)nb;
         const int cw = deep ? zk->c_deep : zk->c_sec;                                                     // window bits of this pass' witness sections
         const uint32_t oA = deep ? zk->offA_deep : zk->offA, oB1 = deep ? zk->offB1_deep : zk->offB1, oC = deep ? zk->offC_deep : zk->offC;
         const int c2 = (nb <= 2 && zk->d_g2_29_lone && lone_entries <= LN.w2.max_entries) ? MSM_C_G2_LONE : cw;
-        static const uint32_t vwg2_env = [] { const char* e = getenv("ZKC_VW_G2"); return e ? (uint32_t)atoi(e) : 0u; }();      // A/B: the G2 jobs' window apart from the G1 sections'
+        const uint32_t vwg2_env = (uint32_t)sw::value<sw::ZKC_VW_G2>(0);      // A/B: the G2 jobs' window apart from the G1 sections'
         j1.clear(vws, vwb, MSM_MAX_VW_G1); j2.clear(c2 == MSM_C_G2_LONE ? 128u : (vwg2_env && nb >= 32) ? vwg2_env : vws, 1024, MSM_MAX_VW_PER_JOB);
         // job order of the G1 pass: the nb H jobs first (the 16-bit bucket sort wants the jobs with the larger bucket count in front), then
         // A, B1, C per proof.  zkc_finalize reads results[q] = H_q and results[nb + 3 q + {0, 1, 2}] = A_q, B1_q, C_q.
@@ -832,7 +823,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         // The G2 MSM needs only the witness: by default it starts with the pass and runs beside buildABC/NTT/G1 sort.  ZKC_G2_LATE holds it back
         // until the G1 stream has finished its short kernels (they were seen to stall next to the G2 chain's low-occupancy kernels); the G2
         // kernels then starve behind the 13 ms G1 accumulation instead and spill into the next pass -- measured equal within noise.
-        static const bool g2_early = getenv("ZKC_G2_LATE") == nullptr;
+        const bool g2_early = !sw::on<sw::ZKC_G2_LATE>();
         // [r2] its bucketing starts with the pass, but its accumulation (VALU-bound, 3.3 ms alone) is held until the G1 stream leaves the NTT: it then
         // runs beside the G1 bucketing and segment kernels, which wait on memory and LDS atomics, instead of beside the NTT, which is VALU-bound too
         // [r4] ... which was right for round 2's pipeline and is not for this one: with the larger reduction windows the G2 side's tail is longer (one wave walks a job's 2048
@@ -841,7 +832,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         // (Two pipeline lanes, -4 % in round 2, are +1.4 % now too -- 3202 / 3206 / 3197 / 3202 / 3201 -- but not on top of this (3107 / 3115 with both) and for twice the work space.)
         // Passes of fewer than 32 proofs keep the hold: a lone proof's G2 kernels (1024 waves of 400 registers) slowed buildABC and the first transform kernel threefold when they were
         // not held (round 3), and the twelve-proof passes of a 2^20-domain key run 140 proofs/s held against 136 early (their bucketing phase is 9 ms long: room for the G2 accumulation).
-        static const bool g2_hold_env = getenv("ZKC_G2_ACC_HOLD") != nullptr, g2_early_env = getenv("ZKC_G2_ACC_EARLY") != nullptr;
+        const bool g2_hold_env = sw::on<sw::ZKC_G2_ACC_HOLD>(), g2_early_env = sw::on<sw::ZKC_G2_ACC_EARLY>();
         // [r5] ... and with the passes of a call rotating over four lanes the hold is right again for full passes: the G2 accumulation of lane k then lands beside lane k's own
         // bucketing instead of beside another lane's transforms (alternating on one box: 3380 / 3386 proofs/s held, 3363 / 3363 started with the pass: +0.6 %)
         const bool g2_acc_with_sort = g2_hold_env || ((nb < 32 || !one_lane) && !g2_early_env);
@@ -856,8 +847,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_red, 0));
         // (measured, alternating on one box: 3102 / 3089 / 3083 proofs/s with the reduction on its own stream, 3074 / 3087 / 3097 without -- nothing: the pass is bound by the
         // sum of its kernels' VALU work, and where the reduction's waves run does not change that sum.  Off unless ZKC_REDUCE_STREAM=1.)
-        static const bool red_on = [] { const char* e = getenv("ZKC_REDUCE_STREAM"); return e && atoi(e) == 1; }();
-        const bool red_split = red_on && !zk->serial_streams && nb >= 32;
+        const bool red_split = sw::on<sw::ZKC_REDUCE_STREAM>() && !zk->serial_streams && nb >= 32;
         if ((rc = msm_pass_g1(zk, LN.w1, j1, slot, false, st, LN.ev_sorted, LN.ev_acc, (red_split && LS.red) ? LS.red : nullptr, LN.ev_red))) return rc;
         tr[4] = now_ms();
         if (!g2_early) {
@@ -871,8 +861,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm, st));
         if (mv_prefetch && p0 + per_pass < B) {                                   // buildABC of the next pass, beside this pass' accumulation
             const int p1 = p0 + per_pass, nb1 = std::min(per_pass, B - p1);
-            static const bool mv_at_ntt = [] { const char* e = getenv("ZKC_MV_PREFETCH_AT_NTT"); return e && atoi(e) == 1; }();      // A/B: start it beside this pass' bucketing instead
-            ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, mv_at_ntt ? LN.ev_ntt : LN.ev_sorted, 0));         // this pass' NTT and joinABC are through (d_abc is free), its accumulation is next (waiting on ev_ntt instead, i.e. starting beside the bucketing, is 1 % slower: 3113 / 3093 against 3143 / 3137 proofs/s on one box)
+            ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, sw::on<sw::ZKC_MV_PREFETCH_AT_NTT>() ? LN.ev_ntt : LN.ev_sorted, 0));         // this pass' NTT and joinABC are through (d_abc is free), its accumulation is next (waiting on ev_ntt instead, i.e. starting beside the bucketing, is 1 % slower: 3113 / 3093 against 3143 / 3137 proofs/s on one box)
             ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, CS.ev_chunk[pass + 1], 0));
             if ((rc = h_matvec_dev(zk, LN, (const uint32_t*)d_wtns + (size_t)p1 * nv * 8, nb1, fin))) return rc;
             ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_mv, fin));

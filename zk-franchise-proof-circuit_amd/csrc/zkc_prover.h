@@ -47,6 +47,10 @@ constexpr int MSM_MAX_JOBS = 512;                  // jobs per pipeline pass (pr
 // [r5] pipeline lanes (stream sets + per-pass work space) and call slots of a key.  A direct caller uses one lane and slots 0 / 1 (bench.py); the proving service loads its
 // keys with one lane per worker so that the calls of concurrent single-proof callers are independent stream sets and really overlap on the GPU (zkc_service.hip).
 constexpr int MAX_LANES = 4, CALL_SLOTS = 4;
+// the clamps that zkc_switches.h writes out as numbers are these constants
+static_assert(sw::rows[sw::ZKC_C_SECTIONS].hi == MSM_C_BIG && sw::rows[sw::ZKC_C_H].hi == MSM_C_BIG && sw::rows[sw::ZKC_C_DEEP].hi == MSM_C_BIG, "zkc_switches.h: MSM_C_BIG");
+static_assert(sw::rows[sw::ZKC_INFLIGHT].hi == MSM_MAX_JOBS / 4 && sw::rows[sw::ZKC_SERVICE_PASS].hi == MSM_MAX_JOBS / 4, "zkc_switches.h: MSM_MAX_JOBS / 4");
+static_assert(sw::rows[sw::ZKC_LANES].hi == MAX_LANES && sw::rows[sw::ZKC_SERVICE_WORKERS].hi == MAX_LANES, "zkc_switches.h: MAX_LANES");
 
 // One multi-scalar multiplication inside a pipeline pass: sum_j scalar[j] * P[point(j)]
 struct MsmJob {

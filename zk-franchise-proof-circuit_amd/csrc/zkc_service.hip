@@ -39,6 +39,7 @@
 #include <thread>
 #include <vector>
 
+namespace sw = zkc::sw;
 int zkc_lane_streams(zkc_ctx* ctx, int l, bool with_red, zkc_ctx::LaneStreams* out);      // zkc_api.hip
 namespace {
 enum { KIND_FULLPROVE = 0, KIND_PROVE = 1 };
@@ -254,10 +255,10 @@ int ensure_key(zkc_service* s, zkc_service::Dev* d, const std::shared_ptr<KeyIma
             if (!evict_lru(s, d)) break;
         }
         zkc_zkey* key = nullptr;
-        const char* fail_loads = getenv("ZKC_TEST_FAIL_KEY_LOADS");           // test hook: pretend the device is out of memory while it holds this many keys or more
+        const auto fail_loads = sw::given<sw::ZKC_TEST_FAIL_KEY_LOADS>();          // test hook: pretend the device is out of memory while it holds this many keys or more
         for (;;) {
             size_t held; { std::lock_guard<std::mutex> fl(d->fl_mu); held = d->keys.size(); }
-            if (fail_loads && held >= (size_t)atoi(fail_loads)) { rc = ZKC_ERR_HIP; why = "zkc_zkey_load: out of memory (injected by ZKC_TEST_FAIL_KEY_LOADS)"; }
+            if (fail_loads && held >= (size_t)*fail_loads) { rc = ZKC_ERR_HIP; why = "zkc_zkey_load: out of memory (injected by ZKC_TEST_FAIL_KEY_LOADS)"; }
             else {
                 rc = zkc::zkey_load_opts(d->ctx, img->bytes.data(), img->bytes.size(), s->workers_per_dev, s->pass, &key);
                 if (rc) { key = nullptr; why = zkc_last_error(d->ctx); }
@@ -271,8 +272,7 @@ int ensure_key(zkc_service* s, zkc_service::Dev* d, const std::shared_ptr<KeyIma
         // middle of the first burst stalled the device for ~0.5 s (free + re-allocation of GBs).  [r5] The lanes are the CONTEXT's (zkc_prove.hip lane_ensure): the first key of
         // a device pays for them (~37 GB at nLevels 160 with four lanes of 64 proofs), later keys of the same shape find them there; a failed reserve is counted, not fatal
         // (the lanes then grow on demand).  ZKC_SERVICE_RESERVE=0: always on demand, as the direct entry points do.
-        static const bool reserve = [] { const char* e = getenv("ZKC_SERVICE_RESERVE"); return !(e && atoi(e) == 0); }();
-        if (!rc && reserve && zkc::prove_reserve(key, 1 << 20) != ZKC_OK) { (void)zkc_last_error(d->ctx); std::lock_guard<std::mutex> g(s->mu); s->reserve_failures++; }
+        if (!rc && sw::on<sw::ZKC_SERVICE_RESERVE>() && zkc::prove_reserve(key, 1 << 20) != ZKC_OK) { (void)zkc_last_error(d->ctx); std::lock_guard<std::mutex> g(s->mu); s->reserve_failures++; }
         if (!rc) { std::lock_guard<std::mutex> fl(d->fl_mu); zkc_service::KeySlot k; k.img = img; k.key = key; k.last_use = ++d->use_clock; d->keys.push_back(k); }
         std::lock_guard<std::mutex> g(s->mu); s->key_loads++;
         if (!rc) { d->resident.push_back(img); *out = key; }
@@ -465,16 +465,16 @@ extern "C" const char* zkc_service_last_error(void) { return g_service_err.c_str
 extern "C" int zkc_service_create(const int* hip_devices, int n, zkc_service** out) {
     if (!out || n < 0 || n > 64 || (n > 0 && !hip_devices)) return service_fail(ZKC_ERR_BAD_ARG, "zkc_service_create: bad argument");
     std::vector<int> devs(hip_devices, hip_devices + n);
-    if (n == 0 && !parse_device_list(getenv("ZKC_DEVICE"), devs)) return service_fail(ZKC_ERR_HIP, "zkc_service_create: no GPU visible (or $ZKC_DEVICE is not a list of device numbers)");
+    if (n == 0 && !parse_device_list(sw::text<sw::ZKC_DEVICE>(), devs)) return service_fail(ZKC_ERR_HIP, "zkc_service_create: no GPU visible (or $ZKC_DEVICE is not a list of device numbers)");
     zkc_service* s = new zkc_service();
-    if (const char* e = getenv("ZKC_SERVICE_MAX_BATCH")) s->max_batch = std::max(1, std::min(atoi(e), 4096));
-    if (const char* e = getenv("ZKC_SERVICE_SPILL")) s->spill = std::max(1, atoi(e));
-    if (const char* e = getenv("ZKC_SERVICE_KEYS")) s->keys_per_dev = std::max(1, std::min(atoi(e), 64));
+    s->max_batch = (int)sw::value<sw::ZKC_SERVICE_MAX_BATCH>(s->max_batch);
+    s->spill = (int)sw::value<sw::ZKC_SERVICE_SPILL>(s->spill);
+    s->keys_per_dev = (int)sw::value<sw::ZKC_SERVICE_KEYS>(s->keys_per_dev);
     // [r5] workers per device = lanes of a service key = calls in flight per key; passes of up to `pass` proofs on each lane (work space: workers x pass x ~62 MB at nLevels 160)
-    if (const char* e = getenv("ZKC_SERVICE_WORKERS")) s->workers_per_dev = std::max(1, std::min(atoi(e), (int)zkc::MAX_LANES));
-    if (const char* e = getenv("ZKC_SERVICE_PASS")) s->pass = std::max(1, std::min(atoi(e), zkc::MSM_MAX_JOBS / 4));
-    if (const char* e = getenv("ZKC_SERVICE_BUSY_WAIT_US")) s->busy_wait_us = (uint64_t)std::max(0, atoi(e));
-    if (const char* e = getenv("ZKC_SERVICE_MIN_BATCH")) s->min_batch = std::max(1, atoi(e));
+    s->workers_per_dev = (int)sw::value<sw::ZKC_SERVICE_WORKERS>(s->workers_per_dev);
+    s->pass = (int)sw::value<sw::ZKC_SERVICE_PASS>(s->pass);
+    s->busy_wait_us = (uint64_t)sw::value<sw::ZKC_SERVICE_BUSY_WAIT_US>((long long)s->busy_wait_us);
+    s->min_batch = (int)sw::value<sw::ZKC_SERVICE_MIN_BATCH>(s->min_batch);
     for (int dv : devs) { s->devs.emplace_back(new zkc_service::Dev()); s->devs.back()->device = dv; }
     int idx = 0;
     for (auto& d : s->devs) for (int k = 0; k < s->workers_per_dev; k++) { s->workers.emplace_back(new zkc_service::Worker()); s->workers.back()->dev = d.get(); s->workers.back()->index = idx++; s->workers.back()->slot = k; }

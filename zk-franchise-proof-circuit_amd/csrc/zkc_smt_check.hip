@@ -129,8 +129,7 @@ static int check_batch(zkc_ctx* ctx, const Batch& B, int32_t* status) {
     }
     int rc;
     if ((rc = zkc_ensure(ctx, (void**)&ctx->d_status, &ctx->status_n, m * sizeof(int32_t)))) return rc;
-    size_t wave_max = WAVE_MAX_DEFAULT;
-    if (const char* e = getenv("ZKC_SMT_WAVE_MAX")) wave_max = (size_t)strtoull(e, nullptr, 10);
+    const size_t wave_max = (size_t)sw::value<sw::ZKC_SMT_WAVE_MAX>(WAVE_MAX_DEFAULT);
     const bool wave = m <= wave_max;
     const size_t nchunks = bound.size() - 1;
     Events tev; tev.ev.resize(3 * nchunks, nullptr);

@@ -297,7 +297,7 @@ extern "C" int zkc_verify_batch(zkc_ctx* ctx, const uint8_t* vk, int nPublic, co
     const std::shared_ptr<const VkReady> V = vk_ready(vk, nPublic, &code);
     if (!V) return code;
     const std::vector<G1Affine>& ic = V->ic;
-    const bool vtrace = getenv("ZKC_VERIFY_TRACE") != nullptr; double vt0 = 0, vt1 = 0, vt2 = 0, vt3 = 0;
+    const bool vtrace = sw::on<sw::ZKC_VERIFY_TRACE>(); double vt0 = 0, vt1 = 0, vt2 = 0, vt3 = 0;
     auto vnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     vt0 = vnow();
     Xoshiro rng;
@@ -335,7 +335,7 @@ extern "C" int zkc_verify_batch(zkc_ctx* ctx, const uint8_t* vk, int nPublic, co
         for (unsigned t = 0; t < np; t++) { if (!okp[t]) return 0; rsum = rsum + rs[t]; for (int j = 0; j < nPublic; j++) xsum[j] = xsum[j] + xs[t][j]; }
     }
     vt1 = vnow();
-    const char* gpu_e = getenv("ZKC_VERIFY_BATCH_GPU"); const int gpu_env = gpu_e ? atoi(gpu_e) : -1;
+    const int gpu_env = (int)sw::value<sw::ZKC_VERIFY_BATCH_GPU>(-1);
     const bool on_gpu = gpu_env < 0 ? N >= 128 : gpu_env != 0;
     Fq12 gpu_product = one12(); int gpu_bad = 0;
     // groups: N singletons (rho_i A_i), then the rho_i C_i in runs of 64 -- a group is summed by ONE lane, and one lane adding all N of them was 100 ms at N = 8192
