@@ -62,8 +62,10 @@ struct zkc_ctx {
     // [r5] the batch verifier's device buffers (zkc_verify_batch, zkc_pairing_dev.hip): points, weights, group table, fold sums, line coefficients, product-tree levels.
     // Kept between calls (a node verifies batch after batch; hipFree waits for the whole device, including any proving lanes) while they add up to at most 256 MB, released
     // at the end of a call that needed more (zkc_verify_ws_trim).
-    enum { VWS_PTS = 0, VWS_RHO, VWS_IDX, VWS_GS, VWS_FOLD_TMP, VWS_FOLD_OUT, VWS_Q, VWS_LINES, VWS_TREE_A, VWS_TREE_B, VWS_BAD, VWS_N };
+    enum { VWS_PTS = 0, VWS_RHO, VWS_IDX, VWS_GS, VWS_FOLD_TMP, VWS_FOLD_OUT, VWS_Q, VWS_LINES, VWS_TREE_A, VWS_TREE_B, VWS_BAD,
+           VWS_FLAGS, VWS_SUM_TREE, VWS_TREE_ALL, VWS_NODES /* zkc_verify_batch_each, and only once a batch has failed: per-proof membership flags, the G1 sum trees, a round's product tree with every level kept, the staging of node downloads */, VWS_N };
     void* vws[VWS_N] = {nullptr}; size_t vws_sz[VWS_N] = {0};
+    uint64_t each_stats[4] = {0, 0, 0, 0};                         // zkc_verify_each_stats: of the last zkc_verify_batch_each
     hipEvent_t ev_vws_up = nullptr, ev_vws_lines = nullptr;       // the batch verifier's upload (second stream) -> its line kernel (third stream) -> the product tree (first): zkc_pairing_dev.hip
     // zkc_smt_check_proofs / zkc_smt_check_absence (zkc_smt_check.hip): two upload buffers (pinned host, device) of chk_sz bytes each, used in turn by the chunks of a call; the event of each buffer's
     // last upload; ms of the last call (host, H2D, kernels)

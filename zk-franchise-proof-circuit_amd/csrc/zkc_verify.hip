@@ -15,19 +15,17 @@
 #include "zkc_prover.h"
 #include "zkc_hostparse.h"
 #include "zkc_pairing.h"
+#include "zkc_pairing_dev.h"
 #include <sys/random.h>
 #include <cerrno>
 #include <mutex>
 #include <memory>
 #include <array>
+#include <atomic>
+#include <functional>
 
 using namespace zkc;
 using namespace zkc::pairing;
-namespace zkc {      // zkc_pairing_dev.hip
-int miller_membership_begin(zkc_ctx* ctx, const G2Affine* h_Q, uint32_t N);
-void miller_join(zkc_ctx* ctx);
-int miller_product_dev(zkc_ctx* ctx, const G1XYZZ* d_P, uint32_t N, pairing::Fq12* product, int* bad);
-}
 
 namespace {
 
@@ -408,6 +406,293 @@ extern "C" int zkc_verify_batch(zkc_ctx* ctx, const uint8_t* vk, int nPublic, co
     vt3 = vnow();
     if (vtrace) fprintf(stderr, "zkc_verify_batch N=%d: parse %.2f ms, device %.2f ms, host tail %.2f ms\n", N, vt1 - vt0, vt2 - vt1, vt3 - vt2);
     return verdict;
+}
+
+// ---- zkc_verify_batch_each: the batch check above with a verdict per proof (include/zkcensus_verify_each.h; DESIGN.md "A verdict per proof").  The first pass IS
+// zkc_verify_batch's -- same kernels, same buffers, one root check -- except that a proof that fails a format check is recorded and replaced by a neutral member (A, B, C at
+// infinity, no share in the sums of weights) instead of ending the call.  Only a batch whose root check fails goes further: the tops of the rounds it downloaded are the
+// upper levels of a product tree whose every node is the Miller value of a dyadic range of proofs, so the same check runs on any node, and the bad members are found by
+// descending from the root.  All checks share the call's one weight vector. ----
+namespace {
+// fn(i) for i < n on at most 16 host threads
+template <class Fn> void each_parallel(size_t n, Fn fn) {
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>({16, std::thread::hardware_concurrency(), n}));
+    std::atomic<size_t> next{0};
+    auto run = [&] { for (size_t i; (i = next.fetch_add(1)) < n;) fn(i); };
+    std::vector<std::thread> th; for (unsigned t = 1; t < nt; t++) th.emplace_back(run);
+    run(); for (auto& x : th) x.join();
+}
+// the host tail on any set of members: their Miller value, the sums of their weights and weighted signals, the sum of their rho_i C_i
+bool each_tail_ok(const VkReady& V, const Fq12& miller_value, const Fr& rs, const Fr* xs, const G1XYZZ& csum) {
+    const int nPublic = V.nPublic;
+    std::vector<std::array<uint32_t, 8>> ks((size_t)nPublic + 1);
+    fp_to_std<FrParams>(ks[0].data(), rs);
+    for (int j = 0; j < nPublic; j++) fp_to_std<FrParams>(ks[j + 1].data(), xs[j]);
+    const G1XYZZ vx = g1_sum_of_products(V.ic.data(), (const uint32_t (*)[8])ks.data(), nPublic + 1);
+    const G1Affine ralpha = xyzz_to_affine_gcd(g1_sum_of_products(&V.alpha, (const uint32_t (*)[8])ks.data(), 1));
+    const Pair tail[3] = {{ralpha, &V.pbeta}, {xyzz_to_affine_gcd(vx), &V.pgamma}, {xyzz_to_affine_gcd(csum), &V.pdelta}};
+    return is_one12(final_exp(multi_miller(tail, 3) * miller_value));
+}
+struct EachNode { uint32_t level, t; };
+// one tree of the descent: the tree over the rounds (nodes on the host) or the tree of one round (nodes on the device).  Level 0 is its bottom; node t of level k has the
+// children 2t and 2t + 1 of level k - 1, the second only where it exists.
+struct EachTree {
+    std::function<uint32_t(uint32_t)> width;                                           // nodes of a level
+    std::function<void(EachNode, uint32_t&, uint32_t&)> range;                         // the proofs [lo, hi) under a node
+    std::function<int(const std::vector<EachNode>&, std::vector<Fq12>&)> products;     // nlines products per node, node after node
+    std::function<G1XYZZ(EachNode)> csum;
+};
+}  // namespace
+
+extern "C" int zkc_verify_batch_each(zkc_ctx* ctx, const uint8_t* vk, int nPublic, const uint8_t* pubs, const uint8_t* proofs, int N, const uint8_t* seed32, int32_t* verdict) {
+    g_err.clear();
+    if (!ctx || !vk || !pubs || !proofs || !verdict || nPublic < 0 || nPublic > 4096 || N <= 0) return vfail(-ZKC_ERR_BAD_ARG, "zkc_verify_batch_each: bad argument");
+    int code = 0;
+    const std::shared_ptr<const VkReady> V = vk_ready(vk, nPublic, &code);
+    if (!V) return code;
+    ZKC_LOCK(ctx);
+    uint64_t* st = ctx->each_stats; st[0] = st[1] = st[2] = st[3] = 0;
+    Xoshiro rng;
+    if (seed32) memcpy(rng.s, seed32, 32); else { std::random_device rd; for (auto& x : rng.s) x = ((uint64_t)rd() << 32) | rd(); }
+    if (!(rng.s[0] | rng.s[1] | rng.s[2] | rng.s[3])) rng.s[0] = 1;
+    // ---- parse: zkc_verify_batch's checks in its order, a failure recorded per proof ----
+    std::vector<G1Affine> pts(2 * (size_t)N); std::vector<G2Affine> Bs(N); std::vector<uint32_t> rho(8 * 2 * (size_t)N, 0);
+    for (int i = 0; i < N; i++) {
+        uint32_t* r = rho.data() + 8 * (size_t)i;
+        const uint64_t lo = rng.next(), hi = rng.next(); r[0] = (uint32_t)lo; r[1] = (uint32_t)(lo >> 32); r[2] = (uint32_t)hi; r[3] = (uint32_t)(hi >> 32);
+        memcpy(rho.data() + 8 * ((size_t)N + i), r, 32);
+    }
+    auto neutral = [&](int i, int32_t why) { verdict[i] = why; pts[i] = pts[(size_t)N + i] = G1Affine::inf(); Bs[i] = G2Affine::inf(); };
+    auto parse_range = [&](int lo, int hi) {
+        for (int i = lo; i < hi; i++) {
+            const uint8_t* pr = proofs + 256 * (size_t)i;
+            verdict[i] = ZKC_PROOF_VALID;
+            if (!rd_g1_std(pts[i], pr) || !rd_g2_std(Bs[i], pr + 64) || !rd_g1_std(pts[N + i], pr + 192) ||
+                !g1_on_curve(pts[i]) || !g1_on_curve(pts[N + i]) || !g2_on_curve(Bs[i])) { neutral(i, ZKC_PROOF_MALFORMED); continue; }
+            for (int j = 0; j < nPublic; j++) {
+                uint32_t k[8]; memcpy(k, pubs + 32 * ((size_t)i * nPublic + j), 32);
+                if (!fp_std_lt_p<FrParams>(k)) { neutral(i, ZKC_PROOF_PUBLIC_RANGE); break; }
+            }
+        }
+    };
+    // sum of rho_i and of rho_i x_ij over the members of [lo, hi) that are still in the batch
+    auto sums_range = [&](int lo, int hi, std::vector<Fr>& xs, Fr& rs) {
+        for (int i = lo; i < hi; i++) {
+            if (verdict[i] != ZKC_PROOF_VALID) continue;
+            const Fr rm = fp_from_std<FrParams>(rho.data() + 8 * (size_t)i); rs = rs + rm;
+            for (int j = 0; j < nPublic; j++) { uint32_t k[8]; memcpy(k, pubs + 32 * ((size_t)i * nPublic + j), 32); xs[j] = xs[j] + rm * fp_from_std<FrParams>(k); }
+        }
+    };
+    std::vector<Fr> xsum; Fr rsum;
+    auto sums_all = [&](bool parse) {
+        const unsigned np = N >= 4096 ? std::max(1u, std::min({std::thread::hardware_concurrency(), N >= 32768 ? 16u : 8u})) : 1u;
+        std::vector<std::vector<Fr>> xs(np, std::vector<Fr>(nPublic, Fr::zero())); std::vector<Fr> rs(np, Fr::zero());
+        std::vector<std::thread> th;
+        auto run = [&](unsigned t) { const int lo = (int)((size_t)N * t / np), hi = (int)((size_t)N * (t + 1) / np); if (parse) parse_range(lo, hi); sums_range(lo, hi, xs[t], rs[t]); };
+        for (unsigned t = 1; t < np; t++) th.emplace_back(run, t);
+        run(0); for (auto& x : th) x.join();
+        xsum.assign(nPublic, Fr::zero()); rsum = Fr::zero();
+        for (unsigned t = 0; t < np; t++) { rsum = rsum + rs[t]; for (int j = 0; j < nPublic; j++) xsum[j] = xsum[j] + xs[t][j]; }
+    };
+    sums_all(true);
+    const int gpu_env = (int)sw::value<sw::ZKC_VERIFY_BATCH_GPU>(-1);
+    const bool on_gpu = gpu_env < 0 ? N >= 128 : gpu_env != 0;
+    if (!on_gpu) {                                                       // the membership tests of the host path, per proof
+        std::vector<char> out(N, 0);
+        each_parallel((size_t)N, [&](size_t i) { out[i] = !g2_in_subgroup(Bs[i]); });
+        bool any = false; for (int i = 0; i < N; i++) if (out[i]) { neutral(i, ZKC_PROOF_MALFORMED); any = true; }
+        if (any) sums_all(false);
+    }
+    // ---- the device pass of zkc_verify_batch ----
+    const uint32_t ncg = ((uint32_t)N + 63) / 64, ngroups = (uint32_t)N + ncg;
+    std::vector<G1XYZZ> gout(ngroups); std::vector<Fq12> tops; Fq12 gpu_product = one12(); int gpu_bad = 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) return vfail(-ZKC_ERR_HIP, "zkc_verify_batch_each: hipSetDevice failed");
+    struct Trim { zkc_ctx* c; ~Trim() { zkc_verify_ws_trim(c, (size_t)256 << 20); } } trim{ctx};
+    std::vector<uint32_t> idx(2 * (size_t)N), gs((size_t)ngroups + 1);
+    for (size_t i = 0; i < idx.size(); i++) idx[i] = (uint32_t)i;
+    for (int i = 0; i < N; i++) gs[i] = (uint32_t)i;
+    for (uint32_t g = 0; g <= ncg; g++) gs[(size_t)N + g] = (uint32_t)N + std::min(64 * g, (uint32_t)N);
+    auto device_pass = [&]() -> int {
+        void *d_pts, *d_rho, *d_idx, *d_gs, *d_tmp, *d_gout; int e;
+        if ((e = zkc_vws(ctx, zkc_ctx::VWS_PTS, pts.size() * sizeof(G1Affine), &d_pts)) || (e = zkc_vws(ctx, zkc_ctx::VWS_RHO, rho.size() * 4, &d_rho)) ||
+            (e = zkc_vws(ctx, zkc_ctx::VWS_IDX, idx.size() * 4, &d_idx)) || (e = zkc_vws(ctx, zkc_ctx::VWS_GS, gs.size() * 4, &d_gs)) ||
+            (e = zkc_vws(ctx, zkc_ctx::VWS_FOLD_TMP, 2 * (size_t)N * sizeof(G1XYZZ), &d_tmp)) || (e = zkc_vws(ctx, zkc_ctx::VWS_FOLD_OUT, (size_t)ngroups * sizeof(G1XYZZ), &d_gout))) return e;
+        if (on_gpu && (e = miller_membership_begin(ctx, Bs.data(), (uint32_t)N))) return e;
+        struct Join { zkc_ctx* c; bool armed; ~Join() { if (armed) miller_join(c); } } join{ctx, on_gpu};
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_pts, pts.data(), pts.size() * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, rho.data(), rho.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_gs, gs.data(), gs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if ((e = fold_group_sums_g1_ws(ctx, (const G1Affine*)d_pts, (const uint32_t*)d_rho, (const uint32_t*)d_idx, 2 * (uint32_t)N, (const uint32_t*)d_gs, ngroups,
+                                       (G1XYZZ*)d_tmp, (G1XYZZ*)d_gout, gout.data()))) return e;
+        tops.clear();
+        if (on_gpu && (e = miller_product_dev(ctx, (const G1XYZZ*)d_gout, (uint32_t)N, &gpu_product, &gpu_bad, &tops))) return e;
+        return ZKC_OK;
+    };
+    auto dev_error = [&](int rc) { return vfail(-rc, std::string("zkc_verify_batch_each: ") + zkc_last_error(ctx)); };
+    int rc = device_pass();
+    if (rc) return dev_error(rc);
+    if (on_gpu && gpu_bad) {                                             // some B_i is outside G2: which ones, and the pass again without them
+        std::vector<int32_t> flag(N);
+        if ((rc = miller_membership_each(ctx, (uint32_t)N, flag.data()))) return dev_error(rc);
+        for (int i = 0; i < N; i++) if (flag[i]) neutral(i, ZKC_PROOF_MALFORMED);
+        sums_all(false);
+        if ((rc = device_pass())) return dev_error(rc);
+        if (gpu_bad) return vfail(-ZKC_ERR_GENERIC, "zkc_verify_batch_each: the membership kernels disagree");
+    }
+    Fq12 root = gpu_product;
+    if (!on_gpu) {                                                       // Miller loops on host threads: a thread's pairs share one accumulator, sixteen at a time
+        const unsigned nthr = std::max(1u, std::min({std::thread::hardware_concurrency(), 32u, ((unsigned)N + 7) / 8}));
+        std::vector<Fq12> part(nthr, one12());
+        auto work = [&](unsigned t) {
+            constexpr int CH = 16;
+            const int lo = (int)((size_t)N * t / nthr), hi = (int)((size_t)N * (t + 1) / nthr);
+            Fq12 f = one12(); G2Prepared prep[CH]; Pair pairs[CH];
+            for (int i0 = lo; i0 < hi; i0 += CH) {
+                const int n = std::min(CH, hi - i0);
+                for (int k = 0; k < n; k++) { prep[k] = prepare_g2(Bs[i0 + k]); pairs[k] = {affine_neg(xyzz_to_affine_gcd(gout[i0 + k])), &prep[k]}; }
+                f = f * multi_miller(pairs, (size_t)n);
+            }
+            part[t] = f;
+        };
+        std::vector<std::thread> th; for (unsigned t = 1; t < nthr; t++) th.emplace_back(work, t);
+        work(0); for (auto& x : th) x.join();
+        root = one12(); for (const Fq12& x : part) root = root * x;
+    }
+    G1XYZZ csum_all = G1XYZZ::inf(); for (uint32_t g = 0; g < ncg; g++) csum_all = xyzz_add(csum_all, gout[(size_t)N + g]);
+    auto result = [&] { for (int i = 0; i < N; i++) if (verdict[i] != ZKC_PROOF_VALID) return 0; return 1; };
+    if (each_tail_ok(*V, root, rsum, xsum.data(), csum_all)) return result();
+
+    // ---- the batch holds a bad member ----
+    std::vector<uint32_t> singles;                                       // proofs to verify singly, once the descent is over
+    auto add_singles = [&](uint32_t lo, uint32_t hi) { for (uint32_t i = lo; i < hi; i++) if (verdict[i] == ZKC_PROOF_VALID) singles.push_back(i); };
+    auto run_singles = [&] {
+        each_parallel(singles.size(), [&](size_t k) { const size_t i = singles[k];
+            verdict[i] = zkc_verify_bin(vk, nPublic, pubs + 32 * i * (size_t)nPublic, proofs + 256 * i) == 1 ? ZKC_PROOF_VALID : ZKC_PROOF_INVALID; });
+        st[1] = singles.size();
+        return result();
+    };
+    if (!on_gpu) { add_singles(0, (uint32_t)N); return run_singles(); }
+
+    const uint32_t nlines = verify_n_lines(), CHUNK = verify_chunk(), nch = ((uint32_t)N + CHUNK - 1) / CHUNK;
+    const uint64_t budget = std::max<uint64_t>(16, (uint64_t)N / 4);
+    // prefix sums in Fr: PR[i] = sum of rho over the live members below i, PX[i][j] the same of rho x_j
+    std::vector<Fr> PR((size_t)N + 1, Fr::zero()), PX(((size_t)N + 1) * nPublic, Fr::zero());
+    for (int i = 0; i < N; i++) {
+        Fr r = Fr::zero(); std::vector<Fr> x(nPublic, Fr::zero());
+        sums_range(i, i + 1, x, r);
+        PR[i + 1] = PR[i] + r;
+        for (int j = 0; j < nPublic; j++) PX[((size_t)i + 1) * nPublic + j] = PX[(size_t)i * nPublic + j] + x[j];
+    }
+    std::vector<G1XYZZ> hC;                                              // the G1 sum trees of all rounds
+    if ((rc = miller_sum_trees(ctx, (const G1XYZZ*)ctx->vws[zkc_ctx::VWS_FOLD_TMP] + N, (uint32_t)N, hC))) return dev_error(rc);
+    const size_t per = TreeShape(std::min((uint32_t)N, CHUNK)).nodes;
+    auto round_n = [&](uint32_t c) { return std::min(CHUNK, (uint32_t)N - c * CHUNK); };
+
+    // range checks of a list of nodes of one tree: pass[i]
+    auto check_nodes = [&](const EachTree& T, const std::vector<EachNode>& nodes, std::vector<char>& pass) -> int {
+        std::vector<Fq12> prod;
+        if (const int e = T.products(nodes, prod)) return e;
+        pass.assign(nodes.size(), 0);
+        each_parallel(nodes.size(), [&](size_t i) {
+            uint32_t lo, hi; T.range(nodes[i], lo, hi);
+            std::vector<Fr> xs(nPublic);
+            for (int j = 0; j < nPublic; j++) xs[j] = PX[(size_t)hi * nPublic + j] - PX[(size_t)lo * nPublic + j];
+            pass[i] = each_tail_ok(*V, miller_walk(prod.data() + i * nlines), PR[hi] - PR[lo], xs.data(), T.csum(nodes[i]));
+        });
+        st[0] += nodes.size();
+        return ZKC_OK;
+    };
+    // from a node known to be bad down to the bottom of its tree: test the left child; if it passes the right one is bad without a test, otherwise the right one is tested
+    // too.  Bad ranges of at most two proofs go to the singles, and so does everything still undecided once the call's range checks reach the budget.
+    auto descend = [&](const EachTree& T, EachNode top, std::vector<EachNode>& bottoms) -> int {
+        std::vector<EachNode> frontier{top};
+        while (!frontier.empty()) {
+            std::vector<EachNode> work, next;
+            for (EachNode x : frontier)
+                for (;;) {
+                    uint32_t lo, hi; T.range(x, lo, hi);
+                    if (hi - lo <= 2) { add_singles(lo, hi); break; }
+                    if (x.level == 0) { bottoms.push_back(x); break; }
+                    if (2 * x.t + 1 >= T.width(x.level - 1)) { x = {x.level - 1, 2 * x.t}; continue; }      // an only child: the same product
+                    work.push_back(x); break;
+                }
+            auto give_up = [&](EachNode x) { uint32_t lo, hi; T.range(x, lo, hi); add_singles(lo, hi); st[3] = 1; };
+            std::vector<EachNode> lefts, rights; std::vector<char> pass;
+            for (size_t i = 0; i < work.size(); i++) {
+                if (st[0] + lefts.size() < budget) lefts.push_back({work[i].level - 1, 2 * work[i].t}); else give_up(work[i]);
+            }
+            if (const int e = check_nodes(T, lefts, pass)) return e;
+            for (size_t i = 0; i < lefts.size(); i++) {
+                const EachNode right{lefts[i].level, lefts[i].t + 1};
+                if (pass[i]) { next.push_back(right); continue; }
+                next.push_back(lefts[i]);
+                if (st[0] + rights.size() < budget) rights.push_back(right); else give_up(right);
+            }
+            if (const int e = check_nodes(T, rights, pass)) return e;
+            for (size_t i = 0; i < rights.size(); i++) if (!pass[i]) next.push_back(rights[i]);
+            frontier.swap(next);
+        }
+        return ZKC_OK;
+    };
+
+    // the tree over the rounds: level 0 holds the tops the first pass downloaded, the levels above their products (host)
+    std::vector<std::vector<Fq12>> up_prod{tops}; std::vector<std::vector<G1XYZZ>> up_sum(1);
+    for (uint32_t c = 0; c < nch; c++) up_sum[0].push_back(hC[per * c + TreeShape(round_n(c)).nodes - 1]);
+    while (up_sum.back().size() > 1) {
+        const std::vector<Fq12>& a = up_prod.back(); const std::vector<G1XYZZ>& b = up_sum.back();
+        const size_t m = b.size(), h = (m + 1) / 2;
+        std::vector<Fq12> p(h * nlines); std::vector<G1XYZZ> q(h);
+        for (size_t t = 0; t < h; t++) {
+            const bool two = 2 * t + 1 < m;
+            q[t] = two ? xyzz_add(b[2 * t], b[2 * t + 1]) : b[2 * t];
+            for (uint32_t s = 0; s < nlines; s++) p[t * nlines + s] = two ? a[2 * t * nlines + s] * a[(2 * t + 1) * nlines + s] : a[2 * t * nlines + s];
+        }
+        up_prod.push_back(std::move(p)); up_sum.push_back(std::move(q));
+    }
+    EachTree rounds;
+    rounds.width = [&](uint32_t level) { return (uint32_t)up_sum[level].size(); };
+    rounds.range = [&](EachNode x, uint32_t& lo, uint32_t& hi) { lo = (uint32_t)std::min<uint64_t>((uint64_t)N, ((uint64_t)x.t << x.level) * CHUNK); hi = (uint32_t)std::min<uint64_t>((uint64_t)N, (((uint64_t)x.t + 1) << x.level) * CHUNK); };
+    rounds.products = [&](const std::vector<EachNode>& nodes, std::vector<Fq12>& out) {
+        out.resize(nodes.size() * nlines);
+        for (size_t i = 0; i < nodes.size(); i++) std::copy_n(up_prod[nodes[i].level].begin() + (size_t)nodes[i].t * nlines, nlines, out.begin() + i * nlines);
+        return ZKC_OK;
+    };
+    rounds.csum = [&](EachNode x) { return up_sum[x.level][x.t]; };
+    std::vector<EachNode> bad_rounds;
+    if ((rc = descend(rounds, {(uint32_t)up_sum.size() - 1, 0}, bad_rounds))) return dev_error(rc);
+
+    // each bad round: its tree again with every level kept, and the descent inside it
+    for (const EachNode& br : bad_rounds) {
+        const uint32_t c = br.t, base = c * CHUNK; const TreeShape sh(round_n(c));
+        if (st[0] >= budget) { add_singles(base, base + sh.n); st[3] = 1; continue; }
+        if ((rc = miller_round_levels(ctx, (const G1XYZZ*)ctx->vws[zkc_ctx::VWS_FOLD_OUT], (uint32_t)N, c))) return dev_error(rc);
+        st[2]++;
+        EachTree in;
+        in.width = [&](uint32_t level) { return sh.m[level]; };
+        in.range = [&](EachNode x, uint32_t& lo, uint32_t& hi) { lo = base + (uint32_t)std::min<uint64_t>(sh.n, (uint64_t)x.t << (x.level + 1)); hi = base + (uint32_t)std::min<uint64_t>(sh.n, ((uint64_t)x.t + 1) << (x.level + 1)); };
+        in.products = [&](const std::vector<EachNode>& nodes, std::vector<Fq12>& out) {
+            out.resize(nodes.size() * nlines);
+            static_assert(sizeof(EachNode) == 2 * sizeof(uint32_t), "EachNode is (level, index)");
+            return nodes.empty() ? (int)ZKC_OK : miller_nodes_fetch(ctx, sh.n, (const uint32_t (*)[2])nodes.data(), nodes.size(), out.data());
+        };
+        in.csum = [&](EachNode x) { return hC[per * c + sh.off[x.level] + x.t]; };
+        std::vector<EachNode> pairs_left;                               // none: a pair is a range of two and goes to the singles
+        if ((rc = descend(in, {(uint32_t)sh.m.size() - 1, 0}, pairs_left))) return dev_error(rc);
+    }
+    const int res = run_singles();
+    if (sw::on<sw::ZKC_VERIFY_TRACE>()) {
+        size_t ws = 0; for (size_t b : ctx->vws_sz) ws += b;
+        fprintf(stderr, "zkc_verify_batch_each N=%d: %llu range checks, %llu singles, %llu rounds rebuilt, budget %s, work space %.1f MB\n", N, (unsigned long long)st[0],
+                (unsigned long long)st[1], (unsigned long long)st[2], st[3] ? "hit" : "not hit", ws / 1048576.0);
+    }
+    return res;
+}
+extern "C" int zkc_verify_each_stats(zkc_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return ZKC_ERR_BAD_ARG;
+    ZKC_LOCK(ctx);
+    for (int i = 0; i < 4; i++) out[i] = ctx->each_stats[i];
+    return ZKC_OK;
 }
 
 // JSON surface: the three artifact files of the reference (verification_key.json, signals.json, proof.json). 1 valid / 0 invalid / <0 error

@@ -219,3 +219,34 @@ def verify_batch(ctx, vk, publics, proofs, seed=None):
     if rc < 0:
         raise _native.ZkcError(-rc, (lib.zkc_verify_last_error() or b'').decode())
     return rc == 1
+
+
+PROOF_VALID, PROOF_INVALID, PROOF_MALFORMED, PROOF_PUBLIC_RANGE = 0, 1, 2, 3      # ZKC_PROOF_* (include/zkcensus_verify_each.h)
+
+
+def verify_each(ctx, vk, publics, proofs, seed=None):
+    """verify_batch with a verdict per proof (zkc_verify_batch_each): the list of N PROOF_* values.  A batch that verify_batch accepts costs the same here; in one it
+    refuses, the bad members are found by bisecting the product tree of the batch check.  verify_batch(...) is all(v == PROOF_VALID for v in verify_each(...))."""
+    lib = _native.load()
+    vkb = vk if isinstance(vk, (bytes, bytearray)) else vk_to_bytes(vk)
+    n = len(proofs) // 256
+    npub = (len(vkb) - 448) // 64 - 1
+    if n == 0 or len(proofs) != 256 * n or len(publics) != 32 * npub * n:
+        raise ValueError('verify_each: proofs must be N x 256 bytes and publics N x nPublic x 32 bytes')
+    verdict = (ctypes.c_int32 * n)()
+    rc = lib.zkc_verify_batch_each(ctx._h, bytes(vkb), npub, bytes(publics), bytes(proofs), n, seed, verdict)
+    if rc < 0:
+        raise _native.ZkcError(-rc, (lib.zkc_verify_last_error() or b'').decode())
+    out = list(verdict)
+    assert (rc == 1) == all(v == PROOF_VALID for v in out)
+    return out
+
+
+def verify_each_stats(ctx):
+    """(range checks beyond the whole-batch check, proofs verified singly, rounds whose tree was rebuilt with its levels kept, 1 if the budget ended the descent) of the
+    context's last verify_each"""
+    out = (ctypes.c_uint64 * 4)()
+    rc = _native.load().zkc_verify_each_stats(ctx._h, out)
+    if rc != 0:
+        raise _native.ZkcError(rc, 'zkc_verify_each_stats')
+    return tuple(out)
