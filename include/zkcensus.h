@@ -387,7 +387,8 @@ int zkc_profile_read(zkc_ctx* ctx, int category, double* total_ms, uint64_t* lau
 
 /* ---- f3: TEST-ONLY trusted setup with known toxic waste (stand-in for circuit/circuit-compiler.sh:99-136, whose
  * output proving_key.zkey is a missing blob).  Reads an iden3 .r1cs, writes a snarkjs-format Groth16 .zkey and a
- * verification_key.json.  Host only; never use the result outside tests and benchmarks. */
+ * verification_key.json.  Host only (zkc_setup_from_r1cs_dev, zkcensus_setup.h, writes the same bytes with the points computed on the GPU); never use the result
+ * outside tests and benchmarks. */
 int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_path, const char* vkey_json_path,
                         char* err, size_t errlen);
 
@@ -397,4 +398,5 @@ int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_p
 #include "zkcensus_delete.h"   /* census trees that shrink, and non-membership proofs */
 #include "zkcensus_snapshot.h" /* frozen views of a census tree */
 #include "zkcensus_verify_each.h" /* the batch verifier with a verdict per proof */
+#include "zkcensus_setup.h" /* fixed-base batch products in G1 and G2, and keys generated on the GPU */
 #endif

@@ -1,0 +1,25 @@
+// zkc_fixedbase_dev.h -- host-side interface of the device fixed-base batch products (zkc_fixedbase_dev.hip), for the files that build on them (zkc_setup.hip).
+// The kernels themselves are launched only from their own file, so zkc_kernels.h does not list them.
+#pragma once
+#include "zkc_internal.h"
+#include "zkc_curve.h"
+
+namespace zkc {
+
+constexpr int FIXED_W = 8;                                          // window width: the host table's (zkc_fixedbase.h), which is uploaded as it is
+constexpr int FIXED_NWIN = 256 / FIXED_W;                           // 32 windows
+constexpr int FIXED_ROWS = FIXED_NWIN * ((1 << FIXED_W) - 1);       // 8160 table rows: T[j][d - 1] = d 2^(8 j) P, d = 1 .. 255
+
+// The window table of one base, built on the host (FixedBase<F>, 32 x 255 affine points) and uploaded: G1 as 64-byte Montgomery points (522 240 B), G2 in the
+// radix-2^29 row format of the G2 MSM (zkc_g2_table29: 60 words = 240 B per row, 1 958 400 B).  Global memory; both tables stay in the L2 during a launch.
+// host_ms (may be NULL): milliseconds of the host build.  Free with hipFree.  The context's lock is held by the caller; `base` is finite and on its curve.
+int fixed_table_g1(zkc_ctx* ctx, const G1Affine& base, G1Affine** d_table, double* host_ms);
+int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, double* host_ms);
+
+// d_out[i] = k_i * P for n scalars on the device, P given by its table.  scalars_mont: the scalars are Fr elements in Montgomery form (what the setup holds) instead of
+// 32-byte standard form; out_mont: coordinates are written in Montgomery form (what a .zkey stores) instead of standard form.  Scalars are below r (see zkcensus_setup.h).
+// Launches on ctx->stream, synchronises and frees its work space before it returns.
+int fixed_mul_g1(zkc_ctx* ctx, const G1Affine* d_table, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont);
+int fixed_mul_g2(zkc_ctx* ctx, const uint32_t* d_table29, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont);
+
+}  // namespace zkc

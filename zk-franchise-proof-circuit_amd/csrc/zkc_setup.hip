@@ -1,10 +1,16 @@
-// zkc_setup.hip -- TEST-ONLY Groth16 trusted setup with KNOWN toxic waste (product host code, no GPU work).
+// zkc_setup.hip -- TEST-ONLY Groth16 trusted setup with KNOWN toxic waste (product host code; the device entry point hands its points to zkc_fixedbase_dev.hip).
 //
 // Stand-in for the reference's ceremony `snarkjs groth16 setup / zkey contribute / beacon`
 // (circuit/circuit-compiler.sh:99-136), needed because proving_key.zkey is a missing blob and unreproducible.
 // Reads an iden3 .r1cs (written by r1cs.py), derives tau, alpha, beta, gamma, delta from a seed and writes a
 // snarkjs-format Groth16 .zkey plus verification_key.json.  NOT for production keys: whoever knows
 // the seed can forge proofs.  Knowing the waste also gives tests an exponent-space closed form for every MSM.
+//
+// Three stages.  1 (host): read the file, derive the waste, compute every scalar the key needs -- linear in the constraint matrix.  2: scalars -> points, fixed-base
+// products of the two generators, on host threads (zkc_setup_from_r1cs: zkc_fixedbase.h) or on the GPU (zkc_setup_from_r1cs_dev: zkc_fixedbase_dev.hip).  3 (host):
+// write the .zkey and the JSON.  Field elements are canonical and the affine form of a point is unique, so the two entry points write the same bytes.
+#include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -13,7 +19,9 @@
 #include <functional>
 #include "zkc_curve.h"
 #include "zkc_fixedbase.h"
+#include "zkc_fixedbase_dev.h"
 #include "../../include/zkcensus.h"
+#include "../../include/zkcensus_setup.h"
 
 #include "zkc_hostparse.h"
 extern "C" int zkc_pairing_bin(const uint8_t g1[64], const uint8_t g2[128], uint8_t out[384]);
@@ -85,36 +93,77 @@ int fail(char* err, size_t errlen, const std::string& m) { if (err && errlen) { 
 
 }  // namespace
 
-extern "C" int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_path, const char* vkey_json_path,
-                                   char* err, size_t errlen) {
+
+namespace {
+
+// what stage 1 leaves: the circuit, and every scalar of the key (Montgomery form)
+struct SetupScalars {
+    uint32_t nWires = 0, nPub = 0, nCons = 0, n = 0;             // n: the domain size
+    std::vector<Cons> cons;
+    std::vector<Fr> u, v, kc;                                    // per wire: A(tau), B(tau), (beta A + alpha B + C)(tau) / gamma (public wires) or / delta
+    std::vector<Fr> h;                                           // per domain point: L'_i(tau) Z(tau) / (-2 delta)
+    Fr alpha, beta, gamma, delta;
+};
+// what stage 2 leaves: the same, times the generators
+struct SetupPoints {
+    std::vector<G1Affine> pA, pB1, pC, pH; std::vector<G2Affine> pB2;
+    G1Affine alpha1, beta1, delta1; G2Affine beta2, gamma2, delta2;
+};
+
+thread_local double g_setup_ms[4] = {0, 0, 0, 0};
+typedef std::chrono::steady_clock::time_point tick;
+tick now() { return std::chrono::steady_clock::now(); }
+double ms_between(tick a, tick b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+G1Affine g1_generator() { return {Fq::one(), fp_from_u32<FqParams>(2)}; }
+G2Affine g2_generator() { return {{fp_from_std<FqParams>(G2X0), fp_from_std<FqParams>(G2X1)}, {fp_from_std<FqParams>(G2Y0), fp_from_std<FqParams>(G2Y1)}}; }
+
+// ---- stage 1: .r1cs -> scalars ----
+int setup_scalars(const char* r1cs_path, uint64_t seed, SetupScalars& S, char* err, size_t errlen) {
     // ---- read .r1cs ----
     FILE* f = fopen(r1cs_path, "rb"); if (!f) return fail(err, errlen, std::string("cannot open ") + r1cs_path);
     fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);
     std::vector<uint8_t> buf((size_t)sz); if (fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) { fclose(f); return fail(err, errlen, "short read"); } fclose(f);
     if (sz < 12 || memcmp(buf.data(), "r1cs", 4)) return fail(err, errlen, "not an r1cs file");
     uint32_t nsec = rd32(&buf[8]); size_t p = 12; const uint8_t *s1 = nullptr, *s2 = nullptr; uint64_t s2sz = 0;
-    for (uint32_t i = 0; i < nsec; i++) { uint32_t id = rd32(&buf[p]); uint64_t n = rd64(&buf[p + 4]); p += 12; if (id == 1) s1 = &buf[p]; if (id == 2) { s2 = &buf[p]; s2sz = n; } p += n; }
+    for (uint32_t i = 0; i < nsec; i++) {
+        if (p + 12 > buf.size()) return fail(err, errlen, "r1cs sections truncated");
+        uint32_t id = rd32(&buf[p]); uint64_t n = rd64(&buf[p + 4]); p += 12;
+        const uint64_t have = std::min<uint64_t>(n, buf.size() - p);       // a file cut inside a section: what is there (the constraint walk below says where it ends)
+        if (id == 1) { if (have < 64) return fail(err, errlen, "bad r1cs header"); s1 = &buf[p]; }
+        if (id == 2) { s2 = &buf[p]; s2sz = have; }
+        if (have < n) break;
+        p += n;
+    }
     if (!s1 || !s2 || rd32(s1) != 32) return fail(err, errlen, "bad r1cs header");
     for (int i = 0; i < 8; i++) if (rd32(s1 + 4 + 4 * i) != FrParams::p[i]) return fail(err, errlen, "r1cs prime is not BN254 r");
     const uint32_t nWires = rd32(s1 + 36), nPubOut = rd32(s1 + 40), nPubIn = rd32(s1 + 44), nCons = rd32(s1 + 60);
     const uint32_t nPub = nPubOut + nPubIn;
-    std::vector<Cons> cons(nCons);
+    if (nPub >= nWires) return fail(err, errlen, "bad r1cs header");
+    std::vector<Cons>& cons = S.cons; cons.resize(nCons);
     {
         const uint8_t* q = s2; const uint8_t* end = s2 + s2sz;
         for (uint32_t k = 0; k < nCons; k++) {
             std::vector<Term>* v[3] = {&cons[k].a, &cons[k].b, &cons[k].c};
             for (int m = 0; m < 3; m++) {
                 if (q + 4 > end) return fail(err, errlen, "r1cs constraints truncated");
-                uint32_t n = rd32(q); q += 4; v[m]->resize(n);
-                for (uint32_t t = 0; t < n; t++) { uint32_t s[8]; (*v[m])[t].wire = rd32(q); memcpy(s, q + 4, 32); (*v[m])[t].coef = fp_from_std<FrParams>(s); q += 36; }
+                uint32_t n = rd32(q); q += 4;
+                if ((uint64_t)n * 36 > (uint64_t)(end - q)) return fail(err, errlen, "r1cs constraints truncated");
+                v[m]->resize(n);
+                for (uint32_t t = 0; t < n; t++) {
+                    uint32_t s[8]; (*v[m])[t].wire = rd32(q); memcpy(s, q + 4, 32); (*v[m])[t].coef = fp_from_std<FrParams>(s); q += 36;
+                    if ((*v[m])[t].wire >= nWires) return fail(err, errlen, "r1cs wire index out of range");
+                }
             }
         }
     }
     uint32_t logn = 0; while ((1u << logn) < nCons + nPub + 1) logn++;
     const uint32_t n = 1u << logn;
+    S.nWires = nWires; S.nPub = nPub; S.nCons = nCons; S.n = n;
     // ---- toxic waste ----
     Rng rng{seed};
     const Fr tau = rng.fr(), alpha = rng.fr(), beta = rng.fr(), gamma = rng.fr(), delta = rng.fr();
+    S.alpha = alpha; S.beta = beta; S.gamma = gamma; S.delta = delta;
     const Fr w = fr_root_of_unity((int)logn), g = fr_root_of_unity((int)logn + 1);
     const Fr ninv = fp_inv<FrParams>(fp_from_u32<FrParams>(n));
     const Fr tn = fr_pow(tau, n), zt = tn - Fr::one();                     // Z(tau) = tau^n - 1
@@ -127,30 +176,86 @@ extern "C" int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const c
     const Fr zc = Fr::zero() - tn - Fr::one();
     for (uint32_t i = 0; i < n; i++) { lag[i] = lag[i] * wp[i] * zt * ninv; lagc[i] = lagc[i] * wp[i] * zc * ninv; }
     // ---- QAP polynomials at tau ----
-    std::vector<Fr> u(nWires, Fr::zero()), v(nWires, Fr::zero()), ww(nWires, Fr::zero());
+    std::vector<Fr>& u = S.u; std::vector<Fr>& v = S.v; std::vector<Fr> ww(nWires, Fr::zero());
+    u.assign(nWires, Fr::zero()); v.assign(nWires, Fr::zero());
     for (uint32_t k = 0; k < nCons; k++) {
         for (auto& t : cons[k].a) u[t.wire] = u[t.wire] + t.coef * lag[k];
         for (auto& t : cons[k].b) v[t.wire] = v[t.wire] + t.coef * lag[k];
         for (auto& t : cons[k].c) ww[t.wire] = ww[t.wire] + t.coef * lag[k];
     }
     for (uint32_t i = 0; i <= nPub; i++) u[i] = u[i] + lag[nCons + i];     // snarkjs' extra rows A[nCons+i][i] = 1
-    // ---- points ----
-    G1Affine G1{Fq::one(), fp_from_u32<FqParams>(2)};
-    G2Affine G2{{fp_from_std<FqParams>(G2X0), fp_from_std<FqParams>(G2X1)}, {fp_from_std<FqParams>(G2Y0), fp_from_std<FqParams>(G2Y1)}};
-    FixedBase<Fq> fb1(G1); FixedBase<Fq2> fb2(G2);
+    // ---- the scalars of the C and H points ----
     const Fr dinv = fp_inv<FrParams>(delta), ginv = fp_inv<FrParams>(gamma);
-    std::vector<G1Affine> pA(nWires), pB1(nWires), pC(nWires), pH(n); std::vector<G2Affine> pB2(nWires);
-    parallel_for(nWires, [&](size_t a, size_t b) {
-        for (size_t i = a; i < b; i++) {
-            pA[i] = fb1.mul(u[i]); pB1[i] = fb1.mul(v[i]); pB2[i] = fb2.mul(v[i]);
-            Fr k = (beta * u[i] + alpha * v[i] + ww[i]) * (i <= nPub ? ginv : dinv);
-            pC[i] = fb1.mul(k);
-        }
-    });
+    S.kc.resize(nWires); S.h.resize(n);
+    parallel_for(nWires, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) S.kc[i] = (beta * u[i] + alpha * v[i] + ww[i]) * (i <= nPub ? ginv : dinv); });
     const Fr hk = zt * dinv * fp_inv<FrParams>(Fr::zero() - fp_from_u32<FrParams>(2));   // Z(tau) / (-2 delta)
-    parallel_for(n, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) pH[i] = fb1.mul(lagc[i] * hk); });
-    const G1Affine alpha1 = fb1.mul(alpha), beta1 = fb1.mul(beta), delta1 = fb1.mul(delta);
-    const G2Affine beta2 = fb2.mul(beta), gamma2 = fb2.mul(gamma), delta2 = fb2.mul(delta);
+    parallel_for(n, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) S.h[i] = lagc[i] * hk; });
+    return ZKC_OK;
+}
+
+// ---- stage 2 on the host: fixed-base products on host threads ----
+void setup_points_host(const SetupScalars& S, SetupPoints& P) {
+    const tick t0 = now();
+    FixedBase<Fq> fb1(g1_generator()); FixedBase<Fq2> fb2(g2_generator());
+    const tick t1 = now();
+    const uint32_t nWires = S.nWires, n = S.n;
+    P.pA.resize(nWires); P.pB1.resize(nWires); P.pC.resize(nWires); P.pH.resize(n); P.pB2.resize(nWires);
+    parallel_for(nWires, [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; i++) { P.pA[i] = fb1.mul(S.u[i]); P.pB1[i] = fb1.mul(S.v[i]); P.pB2[i] = fb2.mul(S.v[i]); P.pC[i] = fb1.mul(S.kc[i]); }
+    });
+    parallel_for(n, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) P.pH[i] = fb1.mul(S.h[i]); });
+    P.alpha1 = fb1.mul(S.alpha); P.beta1 = fb1.mul(S.beta); P.delta1 = fb1.mul(S.delta);
+    P.beta2 = fb2.mul(S.beta); P.gamma2 = fb2.mul(S.gamma); P.delta2 = fb2.mul(S.delta);
+    g_setup_ms[1] = ms_between(t0, t1); g_setup_ms[2] = ms_between(t1, now());
+}
+
+// ---- stage 2 on the device: one batch per group.  G1: u | v | kc | h | alpha, beta, delta; G2: v | beta, gamma, delta.  The scalars go up as they are (Montgomery form)
+// and the points come back in Montgomery form, which is what the vectors hold. ----
+struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
+int setup_points_dev(zkc_ctx* ctx, const SetupScalars& S, SetupPoints& P) {
+    ZKC_LOCK(ctx);
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t nWires = S.nWires, n = S.n, N1 = 3 * nWires + n + 3, N2 = nWires + 3;
+    if (N1 > 0xffffffffull) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_setup_from_r1cs_dev: circuit too large");
+    P.pA.resize(nWires); P.pB1.resize(nWires); P.pC.resize(nWires); P.pH.resize(n); P.pB2.resize(nWires);
+    DevBuf k, out, t1, t2; int rc;
+    const tick t0 = now();
+    if ((rc = fixed_table_g1(ctx, g1_generator(), (G1Affine**)&t1.p, nullptr)) || (rc = fixed_table_g2(ctx, g2_generator(), (uint32_t**)&t2.p, nullptr))) return rc;
+    const tick t1e = now();
+    ZKC_HIP_CHECK(ctx, hipMalloc(&k.p, N1 * sizeof(Fr)));
+    ZKC_HIP_CHECK(ctx, hipMalloc(&out.p, std::max(N1 * sizeof(G1Affine), N2 * sizeof(G2Affine))));
+    Fr* dk = (Fr*)k.p;
+    const Fr tail1[3] = {S.alpha, S.beta, S.delta}, tail2[3] = {S.beta, S.gamma, S.delta};
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dk, S.u.data(), nWires * sizeof(Fr), hipMemcpyHostToDevice));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dk + nWires, S.v.data(), nWires * sizeof(Fr), hipMemcpyHostToDevice));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dk + 2 * nWires, S.kc.data(), nWires * sizeof(Fr), hipMemcpyHostToDevice));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dk + 3 * nWires, S.h.data(), n * sizeof(Fr), hipMemcpyHostToDevice));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dk + 3 * nWires + n, tail1, sizeof(tail1), hipMemcpyHostToDevice));
+    if ((rc = fixed_mul_g1(ctx, (const G1Affine*)t1.p, dk, true, (uint32_t)N1, out.p, true))) return rc;
+    const G1Affine* o1 = (const G1Affine*)out.p; G1Affine got1[3];
+    ZKC_HIP_CHECK(ctx, hipMemcpy(P.pA.data(), o1, nWires * sizeof(G1Affine), hipMemcpyDeviceToHost));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(P.pB1.data(), o1 + nWires, nWires * sizeof(G1Affine), hipMemcpyDeviceToHost));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(P.pC.data(), o1 + 2 * nWires, nWires * sizeof(G1Affine), hipMemcpyDeviceToHost));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(P.pH.data(), o1 + 3 * nWires, n * sizeof(G1Affine), hipMemcpyDeviceToHost));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(got1, o1 + 3 * nWires + n, sizeof(got1), hipMemcpyDeviceToHost));
+    P.alpha1 = got1[0]; P.beta1 = got1[1]; P.delta1 = got1[2];
+    // G2: v is on the device already; its three key scalars follow it in place of kc's first three
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dk + 2 * nWires, tail2, sizeof(tail2), hipMemcpyHostToDevice));
+    if ((rc = fixed_mul_g2(ctx, (const uint32_t*)t2.p, dk + nWires, true, (uint32_t)N2, out.p, true))) return rc;
+    const G2Affine* o2 = (const G2Affine*)out.p; G2Affine got2[3];
+    ZKC_HIP_CHECK(ctx, hipMemcpy(P.pB2.data(), o2, nWires * sizeof(G2Affine), hipMemcpyDeviceToHost));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(got2, o2 + nWires, sizeof(got2), hipMemcpyDeviceToHost));
+    P.beta2 = got2[0]; P.gamma2 = got2[1]; P.delta2 = got2[2];
+    g_setup_ms[1] = ms_between(t0, t1e); g_setup_ms[2] = ms_between(t1e, now());
+    return ZKC_OK;
+}
+
+// ---- stage 3: points -> .zkey and verification_key.json ----
+int setup_write(const SetupScalars& S, const SetupPoints& P, const char* zkey_path, const char* vkey_json_path, char* err, size_t errlen) {
+    const uint32_t nWires = S.nWires, nPub = S.nPub, nCons = S.nCons, n = S.n;
+    const std::vector<Cons>& cons = S.cons;
+    const std::vector<G1Affine>&pA = P.pA, &pB1 = P.pB1, &pC = P.pC, &pH = P.pH; const std::vector<G2Affine>& pB2 = P.pB2;
+    const G1Affine &alpha1 = P.alpha1, &beta1 = P.beta1, &delta1 = P.delta1; const G2Affine &beta2 = P.beta2, &gamma2 = P.gamma2, &delta2 = P.delta2;
     // ---- .zkey ----
     std::vector<std::vector<uint8_t>> sec(11);
     put32(sec[1], 1);
@@ -199,5 +304,41 @@ extern "C" int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const c
         FILE* v = fopen(vkey_json_path, "wb"); if (!v) return fail(err, errlen, std::string("cannot write ") + vkey_json_path);
         fwrite(j.data(), 1, j.size(), v); fclose(v);
     }
+    return ZKC_OK;
+}
+
+}  // namespace
+
+extern "C" int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_path, const char* vkey_json_path,
+                                   char* err, size_t errlen) {
+    SetupScalars S; SetupPoints P;
+    const tick t0 = now();
+    int rc = setup_scalars(r1cs_path, seed, S, err, errlen); if (rc) return rc;
+    const tick t1 = now(); g_setup_ms[0] = ms_between(t0, t1);
+    setup_points_host(S, P);
+    const tick t2 = now();
+    rc = setup_write(S, P, zkey_path, vkey_json_path, err, errlen);
+    g_setup_ms[3] = ms_between(t2, now());
+    return rc;
+}
+
+// The same key with stage 2 on ctx's GPU (zkcensus_setup.h).
+extern "C" int zkc_setup_from_r1cs_dev(zkc_ctx* ctx, const char* r1cs_path, uint64_t seed, const char* zkey_path, const char* vkey_json_path,
+                                       char* err, size_t errlen) {
+    if (!ctx) { if (err && errlen) snprintf(err, errlen, "zkc_setup_from_r1cs_dev: no context"); return ZKC_ERR_BAD_ARG; }
+    SetupScalars S; SetupPoints P;
+    const tick t0 = now();
+    int rc = setup_scalars(r1cs_path, seed, S, err, errlen); if (rc) return rc;
+    const tick t1 = now(); g_setup_ms[0] = ms_between(t0, t1);
+    if ((rc = setup_points_dev(ctx, S, P))) { if (err && errlen) snprintf(err, errlen, "%s", zkc_last_error(ctx)); return rc; }
+    const tick t2 = now();
+    rc = setup_write(S, P, zkey_path, vkey_json_path, err, errlen);
+    g_setup_ms[3] = ms_between(t2, now());
+    return rc;
+}
+
+extern "C" int zkc_setup_stats(double ms[4]) {
+    if (!ms) return ZKC_ERR_BAD_ARG;
+    for (int i = 0; i < 4; i++) ms[i] = g_setup_ms[i];
     return ZKC_OK;
 }

@@ -1,10 +1,14 @@
 """The NTT and G1 MSM engines on their own -- the ffjavascript calls under snarkjs' groth16.prove (`Fr.fft`, `Fr.ifft`,
 `G1.multiExpAffine`; ts_inputs/src/example.ts:358) over device buffers.  Thin ctypes wrappers of include/zkcensus.h
-zkc_ntt_dev / zkc_g1_mul_batch_dev / zkc_msm_g1_*; used by SURVEY.md 8(d) config 5 (ii) (tools/stress.py) and its parity tests."""
+zkc_ntt_dev / zkc_g1_mul_batch_dev / zkc_msm_g1_*; used by SURVEY.md 8(d) config 5 (ii) (tools/stress.py) and its parity tests.
+g1_fixed_mul / g2_fixed_mul (include/zkcensus_setup.h) are the windowed fixed-base batch products the device key generator is built from."""
 import ctypes
 
 R_MONT = 1 << 256
 G1_GENERATOR = (1).to_bytes(32, 'little') + (2).to_bytes(32, 'little')
+G2_GENERATOR = b''.join(c.to_bytes(32, 'little') for c in (       # x.c0 | x.c1 | y.c0 | y.c1
+    0x1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed, 0x198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2,
+    0x12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa, 0x090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b))
 
 
 def fft(ctx, d_src_ptr, d_dst_ptr, logn, nvec=1):
@@ -19,6 +23,23 @@ def ifft(ctx, d_src_ptr, d_dst_ptr, logn, nvec=1):
 def g1_mul_batch(ctx, base64, d_scalars_ptr, n, d_out_ptr):
     """d_out[i] = k_i * base; scalars 32 B standard form, points affine standard form (64 B)."""
     ctx._check(ctx._lib.zkc_g1_mul_batch_dev(ctx._h, bytes(base64), d_scalars_ptr, n, d_out_ptr))
+
+
+def g1_fixed_mul(ctx, base64, d_scalars_ptr, n, d_out_ptr):
+    """d_out[i] = k_i * base through a window table of the base: one mixed addition per non-zero byte of k_i.  Scalars 32 B standard form BELOW r,
+    points affine standard form (64 B); the base must be on the curve."""
+    ctx._check(ctx._lib.zkc_g1_fixed_mul_dev(ctx._h, bytes(base64), d_scalars_ptr, n, d_out_ptr))
+
+
+def g2_fixed_mul(ctx, base128, d_scalars_ptr, n, d_out_ptr):
+    """The same in G2: base and outputs 128 B (x.c0 | x.c1 | y.c0 | y.c1), the base on the twist."""
+    ctx._check(ctx._lib.zkc_g2_fixed_mul_dev(ctx._h, bytes(base128), d_scalars_ptr, n, d_out_ptr))
+
+
+def fixed_mul_window():
+    """The window width w of the fixed-base tables (256 / w windows of 2^w - 1 rows)."""
+    from . import _native
+    return _native.load().zkc_fixed_mul_window()
 
 
 class G1Bases:

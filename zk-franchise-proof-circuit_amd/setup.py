@@ -1,4 +1,4 @@
-"""Test-only key generation: r1cs.build() -> .r1cs -> zkc_setup_from_r1cs -> .zkey + verification_key.json.
+"""Test-only key generation: r1cs.build() -> .r1cs -> zkc_setup_from_r1cs[_dev] -> .zkey + verification_key.json.
 Stand-in for `make compile` (circuit/circuit-compiler.sh:80-136) whose outputs are missing blobs."""
 import ctypes
 import hashlib
@@ -19,15 +19,18 @@ def artifact_paths(nLevels=160, seed=DEFAULT_SEED, directory=None):
 def _generator_stamp():
     """sha256 over the sources that decide the artifacts' bytes: a key written by an older generator is regenerated, never reused."""
     h = hashlib.sha256()
-    for f in (os.path.join(_HERE, 'r1cs.py'), os.path.join(_HERE, 'csrc', 'zkc_setup.hip'), os.path.join(_HERE, 'csrc', 'zkc_fixedbase.h')):
+    for f in (os.path.join(_HERE, 'r1cs.py'), os.path.join(_HERE, 'csrc', 'zkc_setup.hip'), os.path.join(_HERE, 'csrc', 'zkc_fixedbase.h'),
+              os.path.join(_HERE, 'csrc', 'zkc_fixedbase_dev.hip')):
         with open(f, 'rb') as fh:
             h.update(fh.read())
     return h.hexdigest()
 
 
-def ensure_test_artifacts(nLevels=160, seed=DEFAULT_SEED, directory=None, force=False):
-    """Returns (r1cs_path, zkey_path, vkey_json_path), generating them on first use (about 20-40 s of host time) and again whenever
-    r1cs.py or zkc_setup.hip changed since they were written (stamp file next to them)."""
+def ensure_test_artifacts(nLevels=160, seed=DEFAULT_SEED, directory=None, force=False, ctx=None):
+    """Returns (r1cs_path, zkey_path, vkey_json_path), generating them on first use and again whenever r1cs.py or the generator's sources changed since
+    they were written (stamp file next to them).  With a Context the points of the key are computed on its GPU (zkc_setup_from_r1cs_dev); the bytes, the
+    paths and the stamp are the same either way.  Where the time goes at nLevels 160 (tools/setup_bench.py, profiles/setup_device.json, one MI355X box): r1cs.build + write 1.8 s of Python; the host generator 0.55 s
+    (0.36 s of it the points); the device generator 0.19 s (5 ms the points, the rest reading the file, the scalars, the tables and writing the outputs)."""
     r, z, v = artifact_paths(nLevels, seed, directory)
     stamp_path, stamp = z + '.stamp', _generator_stamp()
     fresh = os.path.exists(stamp_path) and open(stamp_path).read().strip() == stamp
@@ -38,7 +41,10 @@ def ensure_test_artifacts(nLevels=160, seed=DEFAULT_SEED, directory=None, force=
     cs.write(r)
     err = ctypes.create_string_buffer(512)
     tmpz, tmpv = z + '.tmp%d' % os.getpid(), v + '.tmp%d' % os.getpid()
-    rc = _native.load().zkc_setup_from_r1cs(r.encode(), seed, tmpz.encode(), tmpv.encode(), err, 512)
+    if ctx is None:
+        rc = _native.load().zkc_setup_from_r1cs(r.encode(), seed, tmpz.encode(), tmpv.encode(), err, 512)
+    else:
+        rc = ctx._lib.zkc_setup_from_r1cs_dev(ctx._h, r.encode(), seed, tmpz.encode(), tmpv.encode(), err, 512)
     if rc != 0:
         raise _native.ZkcError(rc, err.value.decode())
     os.replace(tmpz, z); os.replace(tmpv, v)
