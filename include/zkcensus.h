@@ -281,10 +281,24 @@ void zkc_msm_g1_free(zkc_msm* m);
  * zkc_debug_stage: stage 0 -> A_w | B_w | C_w after buildABC (3 x domainSize x 32 B, Montgomery form);
  *                  stage 1 -> joinABC output (A'B' - C') on the odd coset (domainSize x 32 B, standard form).
  * zkc_msm_debug  : one MSM over zkey section which (0=A 1=B1 2=B2 3=C 4=H) with caller scalars (device, standard form, below r);
- *                  host_out = affine point in standard form (64 B, or 128 B for B2). */
+ *                  host_out = affine point in standard form (64 B, or 128 B for B2).
+ * zkc_debug_pairing_dev: the device side of zkc_verify_batch / zkc_verify_batch_each (csrc/zkc_pairing_dev.hip and the fold kernels of csrc/zkc_msm.hip) on N pairs and
+ *                  weights of the caller's, whatever N: the same calls in the same order, in the context's verifier work space and under its lock, $ZKC_VERIFY_CHUNK
+ *                  honoured.  g1: N x 64 B, g2: N x 128 B, affine standard form, zero = infinity; every point must be on its curve.  weights: N x 32 B, ANY 256-bit
+ *                  little-endian integers (the verifiers draw 128 bits; the fold kernel walks from the scalar's own top bit), NULL = all 1.
+ *                  product_out = final_exp(prod_i f_{Q_i}(-w_i P_i)) = prod_i e(-w_i P_i, Q_i) in zkc_pairing_bin's layout;
+ *                  folded_out (N x 64 B, may be NULL) = w_i P_i, affine standard form, zero = infinity;
+ *                  member_out (N, may be NULL) = the flag per point of the per-proof membership kernel, 1 = Q_i on the twist but outside G2, infinity 0;
+ *                  *bad_out = the aggregate flag of the batch membership kernel.  Membership is reported, not enforced: the product is written whatever *bad_out.
+ *                  nodes: count x (round, level, t), node t of level `level` of the product tree of round `round` (rounds of $ZKC_VERIFY_CHUNK pairs; level k of a round
+ *                  of n pairs has m[k] nodes, m[0] = ceil(n / 2), m[k + 1] = ceil(m[k] / 2); node t covers the round's pairs [t << (k + 1), min(n, (t + 1) << (k + 1))));
+ *                  node_out (count x 384 B, may be NULL: no nodes) = each node's value, walked and raised like product_out.
+ *                  ZKC_ERR_BAD_ARG: a bad handle, a missing pointer, N <= 0, a coordinate >= q, a point off its curve, a node that does not exist. */
 int zkc_debug_stage(zkc_zkey* zk, const void* d_wtns, int stage, void* host_out);
 unsigned long long zkc_debug_early_retries(void);      /* calls of given witnesses that were laid out from their sibling wires, refused by the fold check and proved again from their fold flags (process-wide) */
 int zkc_msm_debug(zkc_zkey* zk, int which, const void* d_scalars, uint32_t count, void* host_out);
+int zkc_debug_pairing_dev(zkc_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint8_t* weights, int N, uint8_t product_out[384], uint8_t* folded_out,
+                          int32_t* member_out, int* bad_out, const uint32_t* nodes, size_t count, uint8_t* node_out);
 
 /* ---- f1: the census / voter generator (internal/helpers.go:36-85 GenTree -- arbo.NewTree{Poseidon}, Add, GenProof, zero padding -- and internal/inputs.go:33-98
  * MockInputs; ts_inputs/src/inputs.ts:38-88).  arbo tree semantics: leaf = H(key, value, 1), node = H(left, right), path bit i = bit i (LSB first) of the key, an empty

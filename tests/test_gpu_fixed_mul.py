@@ -1,73 +1,16 @@
 """GPU: the windowed fixed-base batch products zkc_g1_fixed_mul_dev / zkc_g2_fixed_mul_dev (include/zkcensus_setup.h), byte for byte.
 G1 against the oracle's scalar multiplication and against the double-and-add engine zkc_g1_mul_batch_dev on the same inputs.  G2 against an affine double-and-add over
-Fq2 in Python integers written here (the oracle exports no G2 product), itself pinned on 2 G2 (a constant, and the oracle's one-term G2 MSM), r G2 = infinity and
+Fq2 in Python integers (tests/g2_py.py; the oracle exports no G2 product), itself pinned on 2 G2 (a constant, and the oracle's one-term G2 MSM), r G2 = infinity and
 (a + b) P = a P + b P (the 257 expected points of a base share its doublings: g2_mul_many, checked against g2_mul).  One list of 257 scalars serves every size: the edge values sit at its END and a batch of n takes the last n, so every batch but n = 1 holds all
 of them at lanes that change with n (wave and block edges: 63, 64, 65, 257); the expected points are computed once per base."""
 import random
 import pytest
 import oracle_lib as ol
+from g2_py import f2sub, g2_add, g2_mul, g2_mul_many, g2_bytes, g2_point, G2_TWICE
 
 pytestmark = pytest.mark.gpu
 R, Q = ol.R, ol.Q
 SIZES = [1, 63, 64, 65, 257]
-
-# ---- Fq2 = Fq[u] / (u^2 + 1) and the twist y^2 = x^3 + 3 / (9 + u), affine, None = infinity ----
-f2add = lambda a, b: ((a[0] + b[0]) % Q, (a[1] + b[1]) % Q)
-f2sub = lambda a, b: ((a[0] - b[0]) % Q, (a[1] - b[1]) % Q)
-f2mul = lambda a, b: ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
-
-
-def f2inv(a):
-    n = pow(a[0] * a[0] + a[1] * a[1], -1, Q)
-    return (a[0] * n % Q, -a[1] * n % Q)
-
-
-def g2_add(p, q):
-    if p is None: return q
-    if q is None: return p
-    (x1, y1), (x2, y2) = p, q
-    if x1 == x2:
-        if f2add(y1, y2) == (0, 0): return None
-        lam = f2mul(f2mul((3, 0), f2mul(x1, x1)), f2inv(f2add(y1, y1)))
-    else:
-        lam = f2mul(f2sub(y2, y1), f2inv(f2sub(x2, x1)))
-    x3 = f2sub(f2sub(f2mul(lam, lam), x1), x2)
-    return (x3, f2sub(f2mul(lam, f2sub(x1, x3)), y1))
-
-
-def g2_mul(p, k):
-    acc = None
-    for bit in bin(k)[2:]:
-        acc = g2_add(acc, acc)
-        if bit == '1': acc = g2_add(acc, p)
-    return acc
-
-
-def g2_mul_many(p, ks):
-    """g2_mul for many scalars of one base: the doublings 2^i p are made once, a product is the sum of those its bits select (right to left)"""
-    dbl = [p]
-    for _ in range(max(ks).bit_length() - 1):
-        dbl.append(g2_add(dbl[-1], dbl[-1]))
-    out = []
-    for k in ks:
-        acc = None
-        for i in range(k.bit_length()):
-            if (k >> i) & 1: acc = g2_add(acc, dbl[i])
-        out.append(acc)
-    return out
-
-
-def g2_bytes(p):
-    return bytes(128) if p is None else b''.join(c.to_bytes(32, 'little') for c in (p[0][0], p[0][1], p[1][0], p[1][1]))
-
-
-def g2_point(b):
-    c = [int.from_bytes(b[32 * i:32 * i + 32], 'little') for i in range(4)]
-    return ((c[0], c[1]), (c[2], c[3]))
-
-
-G2_TWICE = ((18029695676650738226693292988307914797657423701064905010927197838374790804409, 14583779054894525174450323658765874724019480979794335525732096752006891875705),
-            (2140229616977736810657479771656733941598412651537078903776637920509952744750, 11474861747383700316476719153975578001603231366361248090558603872215261634898))
 
 
 def edge_scalars(w):

@@ -37,6 +37,12 @@ bool rd_fq_std(Fq& o, const uint8_t* p) { uint32_t s[8]; memcpy(s, p, 32); if (!
 bool rd_g1_std(G1Affine& o, const uint8_t* p) { return rd_fq_std(o.x, p) && rd_fq_std(o.y, p + 32); }
 bool rd_g2_std(G2Affine& o, const uint8_t* p) { return rd_fq_std(o.x.c0, p) && rd_fq_std(o.x.c1, p + 32) && rd_fq_std(o.y.c0, p + 64) && rd_fq_std(o.y.c1, p + 96); }
 
+// an element of Fq12 as zkc_pairing_bin writes it: 12 x 32 B standard form, c0.a0.(c0, c1) c0.a1 c0.a2 c1.a0 c1.a1 c1.a2
+void fq12_to_std(const Fq12& e, uint8_t out[384]) {
+    const Fq2* c[6] = {&e.a.a0, &e.a.a1, &e.a.a2, &e.b.a0, &e.b.a1, &e.b.a2};
+    for (int i = 0; i < 6; i++) { uint32_t t[8]; fp_to_std<FqParams>(t, c[i]->c0); memcpy(out + 64 * i, t, 32); fp_to_std<FqParams>(t, c[i]->c1); memcpy(out + 64 * i + 32, t, 32); }
+}
+
 using parse::dec_of;
 
 thread_local std::string g_err;
@@ -50,9 +56,7 @@ extern "C" const char* zkc_verify_last_error(void) { return g_err.c_str(); }
 extern "C" int zkc_pairing_bin(const uint8_t g1[64], const uint8_t g2[128], uint8_t out[384]) {
     G1Affine P; G2Affine Q;
     if (!g1 || !g2 || !out || !rd_g1_std(P, g1) || !rd_g2_std(Q, g2) || !g1_on_curve(P) || !g2_on_curve(Q)) return ZKC_ERR_BAD_ARG;
-    const Fq12 e = pairing_snarkjs(P, Q);
-    const Fq2* c[6] = {&e.a.a0, &e.a.a1, &e.a.a2, &e.b.a0, &e.b.a1, &e.b.a2};
-    for (int i = 0; i < 6; i++) { uint32_t t[8]; fp_to_std<FqParams>(t, c[i]->c0); memcpy(out + 64 * i, t, 32); fp_to_std<FqParams>(t, c[i]->c1); memcpy(out + 64 * i + 32, t, 32); }
+    fq12_to_std(pairing_snarkjs(P, Q), out);
     return ZKC_OK;
 }
 extern "C" void zkc_sha256(const void* data, size_t len, uint8_t out[32]) { parse::sha256(data, len, out); }
@@ -692,6 +696,77 @@ extern "C" int zkc_verify_each_stats(zkc_ctx* ctx, uint64_t out[4]) {
     if (!ctx || !out) return ZKC_ERR_BAD_ARG;
     ZKC_LOCK(ctx);
     for (int i = 0; i < 4; i++) out[i] = ctx->each_stats[i];
+    return ZKC_OK;
+}
+
+// ---- test hook (include/zkcensus.h): the device side of the two batch verifiers by value.  N pairs (P_i, Q_i) and weights w_i of the caller's go through what
+// zkc_verify_batch / zkc_verify_batch_each drive, in their order, under the context's lock and in their work-space slots: the Q_i up with their membership tests and first
+// lines (miller_membership_begin), w_i P_i as N singleton groups (fold_group_sums_g1_ws), prod_i f_{Q_i}(-w_i P_i) (miller_product_dev), the flag per point
+// (miller_membership_each), and, for the nodes asked for, a round's tree with every level kept (miller_round_levels, miller_nodes_fetch), each node walked and raised as the
+// descent does it.  Membership is reported, not enforced. ----
+extern "C" int zkc_debug_pairing_dev(zkc_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint8_t* weights, int N, uint8_t product_out[384], uint8_t* folded_out,
+                                     int32_t* member_out, int* bad_out, const uint32_t* nodes, size_t count, uint8_t* node_out) {
+    if (!ctx) return ZKC_ERR_BAD_ARG;
+    ZKC_LOCK(ctx);
+    if (!g1 || !g2 || !product_out || !bad_out || N <= 0 || (count && node_out && !nodes)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_debug_pairing_dev: bad argument");
+    if (!node_out) count = 0;
+    std::vector<G1Affine> pts(N); std::vector<G2Affine> Qs(N); std::vector<uint32_t> rho(8 * (size_t)N, 0);
+    for (int i = 0; i < N; i++) {
+        if (!rd_g1_std(pts[i], g1 + 64 * (size_t)i) || !rd_g2_std(Qs[i], g2 + 128 * (size_t)i) || !g1_on_curve(pts[i]) || !g2_on_curve(Qs[i]))
+            return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_debug_pairing_dev: pair " + std::to_string(i) + " is no pair of curve points");
+        if (weights) memcpy(rho.data() + 8 * (size_t)i, weights + 32 * (size_t)i, 32); else rho[8 * (size_t)i] = 1;
+    }
+    const uint32_t nlines = verify_n_lines(), CHUNK = verify_chunk(), nch = ((uint32_t)N + CHUNK - 1) / CHUNK;
+    auto round_n = [&](uint32_t c) { return std::min(CHUNK, (uint32_t)N - c * CHUNK); };
+    for (size_t i = 0; i < count; i++) {
+        const uint32_t c = nodes[3 * i], lev = nodes[3 * i + 1], t = nodes[3 * i + 2];
+        if (c >= nch) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_debug_pairing_dev: no such round");
+        const TreeShape sh(round_n(c));
+        if (lev >= sh.m.size() || t >= sh.m[lev]) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_debug_pairing_dev: no such node");
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_debug_pairing_dev: hipSetDevice failed");
+    std::vector<uint32_t> idx(N), gs((size_t)N + 1);
+    for (int i = 0; i < N; i++) idx[i] = (uint32_t)i;
+    for (int i = 0; i <= N; i++) gs[i] = (uint32_t)i;
+    std::vector<G1XYZZ> gout(N); Fq12 product = one12(); int bad = 0;
+    struct Trim { zkc_ctx* c; ~Trim() { zkc_verify_ws_trim(c, (size_t)256 << 20); } } trim{ctx};
+    const int rc = [&]() -> int {
+        void *d_pts, *d_rho, *d_idx, *d_gs, *d_tmp, *d_gout; int e;
+        if ((e = zkc_vws(ctx, zkc_ctx::VWS_PTS, pts.size() * sizeof(G1Affine), &d_pts)) || (e = zkc_vws(ctx, zkc_ctx::VWS_RHO, rho.size() * 4, &d_rho)) ||
+            (e = zkc_vws(ctx, zkc_ctx::VWS_IDX, idx.size() * 4, &d_idx)) || (e = zkc_vws(ctx, zkc_ctx::VWS_GS, gs.size() * 4, &d_gs)) ||
+            (e = zkc_vws(ctx, zkc_ctx::VWS_FOLD_TMP, (size_t)N * sizeof(G1XYZZ), &d_tmp)) || (e = zkc_vws(ctx, zkc_ctx::VWS_FOLD_OUT, (size_t)N * sizeof(G1XYZZ), &d_gout))) return e;
+        if ((e = miller_membership_begin(ctx, Qs.data(), (uint32_t)N))) return e;
+        struct Join { zkc_ctx* c; ~Join() { miller_join(c); } } join{ctx};
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_pts, pts.data(), pts.size() * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_rho, rho.data(), rho.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_gs, gs.data(), gs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if ((e = fold_group_sums_g1_ws(ctx, (const G1Affine*)d_pts, (const uint32_t*)d_rho, (const uint32_t*)d_idx, (uint32_t)N, (const uint32_t*)d_gs, (uint32_t)N,
+                                       (G1XYZZ*)d_tmp, (G1XYZZ*)d_gout, gout.data()))) return e;
+        if ((e = miller_product_dev(ctx, (const G1XYZZ*)d_gout, (uint32_t)N, &product, &bad))) return e;
+        if (member_out && (e = miller_membership_each(ctx, (uint32_t)N, member_out))) return e;
+        // the nodes, round by round: that round's tree with every level kept, the nodes' nlines products, the walk and the final exponentiation of a range check
+        std::vector<char> done(count, 0);
+        for (size_t i0 = 0; i0 < count; i0++) {
+            if (done[i0]) continue;
+            const uint32_t c = nodes[3 * i0];
+            std::vector<std::array<uint32_t, 2>> want; std::vector<size_t> at;
+            for (size_t i = i0; i < count; i++) if (nodes[3 * i] == c) { want.push_back({nodes[3 * i + 1], nodes[3 * i + 2]}); at.push_back(i); done[i] = 1; }
+            std::vector<Fq12> prod(want.size() * nlines);
+            if ((e = miller_round_levels(ctx, (const G1XYZZ*)d_gout, (uint32_t)N, c)) ||
+                (e = miller_nodes_fetch(ctx, round_n(c), (const uint32_t (*)[2])want.data(), want.size(), prod.data()))) return e;
+            each_parallel(want.size(), [&](size_t k) { fq12_to_std(final_exp(miller_walk(prod.data() + k * nlines)), node_out + 384 * at[k]); });
+        }
+        return ZKC_OK;
+    }();
+    if (rc) return rc;
+    fq12_to_std(final_exp(product), product_out);
+    *bad_out = bad;
+    if (folded_out)
+        for (int i = 0; i < N; i++) {
+            const G1Affine a = xyzz_to_affine_gcd(gout[i]); uint32_t t[8];
+            fp_to_std<FqParams>(t, a.x); memcpy(folded_out + 64 * (size_t)i, t, 32); fp_to_std<FqParams>(t, a.y); memcpy(folded_out + 64 * (size_t)i + 32, t, 32);
+        }
     return ZKC_OK;
 }
 

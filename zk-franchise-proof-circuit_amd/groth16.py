@@ -250,3 +250,21 @@ def verify_each_stats(ctx):
     if rc != 0:
         raise _native.ZkcError(rc, 'zkc_verify_each_stats')
     return tuple(out)
+
+
+def debug_pairing_dev(ctx, g1, g2, weights=None, folded=False, members=False, nodes=None):
+    """Test hook (zkc_debug_pairing_dev, not part of the snarkjs-shaped surface): the device side of verify_batch / verify_each on N pairs of the caller's.  g1: N x 64
+    bytes, g2: N x 128 bytes, weights: N x 32 bytes (any 256-bit integers) or None = all 1; nodes: list of (round, level, t).  Returns (product, bad, folded, members,
+    node values): 384 bytes, the aggregate membership flag, N x 64 bytes or None, a list of N flags or None, a list of 384-byte values or None."""
+    n = len(g2) // 128
+    fo = ctypes.create_string_buffer(64 * n) if folded else None
+    mo = (ctypes.c_int32 * n)() if members else None
+    cnt = len(nodes) if nodes else 0
+    nd = (ctypes.c_uint32 * (3 * cnt))(*[v for node in nodes for v in node]) if cnt else None
+    no = ctypes.create_string_buffer(384 * cnt) if cnt else None
+    prod, bad = ctypes.create_string_buffer(384), ctypes.c_int(0)
+    rc = _native.load().zkc_debug_pairing_dev(ctx._h, bytes(g1), bytes(g2), None if weights is None else bytes(weights), n, prod, fo, mo, ctypes.byref(bad), nd, cnt, no)
+    if rc != 0:
+        ctx._check(rc)
+    return (prod.raw, bad.value, fo.raw if folded else None, list(mo) if members else None,
+            [no.raw[384 * i:384 * (i + 1)] for i in range(cnt)] if cnt else None)
