@@ -135,7 +135,7 @@ def test_zkey_fingerprint_identifies_keys(tmp_path):
 
 
 def test_verifier_from_many_threads_with_the_key_cache():
-    """[r5] zkc_verify keeps the latest verification keys ready by their bytes (csrc/zkc_verify.hip vk_ready): eight threads verify the reference's triple, a triple with a
+    """[r5] zkc_verify keeps the latest verification keys ready by their bytes (csrc/zkc_verify.hip vk_ready, which the batch verifiers of csrc/zkc_verify_batch.hip reach through csrc/zkc_verify_host.h): eight threads verify the reference's triple, a triple with a
     changed signal and triples under nine OTHER keys (the reference's with IC points permuted: well-formed keys under which the proof is invalid -- more keys than the cache
     holds, so entries are evicted while others use them) and every verdict is the sequential one."""
     from concurrent.futures import ThreadPoolExecutor

@@ -1,4 +1,4 @@
-"""The batch verifier with a verdict per proof where no GPU is needed (zkc_verify_batch_each / zkc_verify_each_stats, csrc/zkc_verify.hip): the entry points are exported
+"""The batch verifier with a verdict per proof where no GPU is needed (zkc_verify_batch_each / zkc_verify_each_stats, csrc/zkc_verify_batch.hip): the entry points are exported
 and are what include/zkcensus_verify_each.h declares, zkcensus.h includes that header and still compiles as C, the Python surface exists, and the argument checks come
 before any device work, with their text in zkc_verify_last_error()."""
 import ctypes
@@ -59,3 +59,20 @@ def test_refusals_come_before_any_device_work():
         assert verdict[0] == 77
     out = (ctypes.c_uint64 * 4)(1, 2, 3, 4)
     assert lib.zkc_verify_each_stats(None, out) == ZKC_ERR_BAD_ARG and list(out) == [1, 2, 3, 4]
+
+
+def test_verify_batch_refuses_under_its_own_name():
+    """zkc_verify_batch and zkc_verify_batch_each share their first pass (csrc/zkc_verify_batch.hip); each keeps its own name in its texts.  The same never-followed context."""
+    lib = _native.load()
+    vk = ol.load_json('ref/verification_key.json'); pr = ol.load_json('ref/proof.json'); sig = ol.load_json('ref/signals.json')
+    vkb, pubs, proof = ol.vk_bytes(vk), b''.join(ol.le32(x) for x in sig), ol.proof_bytes(pr)
+    never = ctypes.c_void_p(8)
+    for args in ((never, None, 8, pubs, proof, 1, None),                 # vk == NULL
+                 (never, vkb, 8, None, proof, 1, None),                  # pubs == NULL
+                 (never, vkb, 8, pubs, None, 1, None),                   # proofs == NULL
+                 (never, vkb, 8, pubs, proof, 0, None),                  # N <= 0
+                 (never, vkb, 8, pubs, proof, -3, None),
+                 (never, vkb, -1, pubs, proof, 1, None)):                # nPublic < 0
+        assert lib.zkc_verify_batch(*args) == -ZKC_ERR_BAD_ARG, args[2:6]
+        text = lib.zkc_verify_last_error()
+        assert b'zkc_verify_batch:' in text and b'zkc_verify_batch_each' not in text

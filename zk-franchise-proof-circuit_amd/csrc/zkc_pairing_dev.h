@@ -1,4 +1,4 @@
-// zkc_pairing_dev.h -- the batch verifiers' device side (zkc_pairing_dev.hip) as csrc/zkc_verify.hip calls it.  Host code; the caller holds the context's lock.
+// zkc_pairing_dev.h -- the batch verifiers' device side (zkc_pairing_dev.hip) as csrc/zkc_verify_batch.hip calls it.  Host code; the caller holds the context's lock.
 #pragma once
 #include <vector>
 #include "zkc_prover.h"

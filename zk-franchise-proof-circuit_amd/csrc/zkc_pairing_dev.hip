@@ -1,4 +1,4 @@
-// zkc_pairing_dev.hip -- f4 on the GPU: the Miller loops of the batch verifier (zkc_verify_batch, csrc/zkc_verify.hip).
+// zkc_pairing_dev.hip -- f4 on the GPU: the Miller loops of the batch verifier (zkc_verify_batch, csrc/zkc_verify_batch.hip).
 //
 // A batch of N proofs needs prod_i f_{6x+2, B_i}(-rho_i A_i).  On one shared accumulator that product is
 //     F <- F^2 * prod_i line_{i, step}          for each of the 87 steps of the loop,
@@ -219,7 +219,7 @@ int miller_product_dev(zkc_ctx* ctx, const G1XYZZ* d_P, uint32_t N, Fq12* produc
     return ZKC_OK;
 }
 
-// ---- zkc_verify_batch_each: what a failing batch needs to find its bad members (csrc/zkc_verify.hip drives the descent).  The caller holds the context's lock, a pass of
+// ---- zkc_verify_batch_each: what a failing batch needs to find its bad members (csrc/zkc_verify_batch.hip drives the descent).  The caller holds the context's lock, a pass of
 // miller_membership_begin / miller_product_dev over the same N pairs has just ended, and the work space still holds its points, weights and fold results. ----
 // flag[i] = 1 where B_i (as uploaded by miller_membership_begin) is outside G2
 int miller_membership_each(zkc_ctx* ctx, uint32_t N, int32_t* h_flag) {
