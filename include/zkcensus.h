@@ -413,4 +413,5 @@ int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_p
 #include "zkcensus_snapshot.h" /* frozen views of a census tree */
 #include "zkcensus_verify_each.h" /* the batch verifier with a verdict per proof */
 #include "zkcensus_setup.h" /* fixed-base batch products in G1 and G2, and keys generated on the GPU */
+#include "zkcensus_r1cs.h" /* witnesses checked against an .r1cs on the GPU (snarkjs wtns check) */
 #endif

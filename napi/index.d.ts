@@ -17,5 +17,7 @@ export declare const groth16: {
 };
 export declare const wtns: {
   calculate(input: CircuitInput, wasmFile: Artifact | null, wtnsFile?: Artifact | null, opts?: ProveOptions): Promise<Buffer>;
+  /** snarkjs wtns.check: true iff the .wtns satisfies every constraint of the .r1cs (checked on the GPU); on false, logger.warn names the first violated constraint and the count */
+  check(r1csFile: Artifact, wtnsFile: Artifact, logger?: { info?(msg: string): void; warn?(msg: string): void }): Promise<boolean>;
 };
 export declare function flatten(input: CircuitInput, nLevels: number): Buffer;

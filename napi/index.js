@@ -1,6 +1,6 @@
 // zkcensus (N-API): drop-in for the snarkjs calls the reference makes (ts_inputs/src/example.ts:1,358-362):
 //     const { groth16 } = require("zkcensus");   await groth16.fullProve(inputs, wasmFile, zkeyFile)
-// plus groth16.prove(zkeyFile, wtnsFile), groth16.verify(vk, publicSignals, proof) and wtns.calculate(input, wasmFile, wtnsFile).
+// plus groth16.prove(zkeyFile, wtnsFile), groth16.verify(vk, publicSignals, proof), wtns.calculate(input, wasmFile, wtnsFile) and wtns.check(r1csFile, wtnsFile).
 // Host code stays JavaScript/TypeScript; the arithmetic runs in libzkcensus.so's HIP kernels.  CommonJS, Node >= 12.
 //
 // wasmFile names the circuit, as it does for snarkjs: its SHA-256 selects the native (HIP) witness generator (80a73567...c139 = the reference's
@@ -106,6 +106,18 @@ const wtns = {
     if (typeof wtnsFile === "string") fs.writeFileSync(wtnsFile, image);
     else if (wtnsFile && wtnsFile.type === "mem") wtnsFile.data = new Uint8Array(image);
     return image;
+  },
+  // snarkjs wtns.check(r1csFile, wtnsFile, logger): does the witness satisfy every constraint?  Checked on the GPU (zkc_r1cs_check).  On false the logger, if there is one,
+  // is told the first violated constraint (its index in the .r1cs) and how many are violated, or which wire rule failed before any constraint was looked at.
+  async check(r1csFile, wtnsFile, logger) {
+    const out = await native.wtnsCheckRaw(readArtifact(r1csFile), readArtifact(wtnsFile), LIB);
+    if (out.firstBad === -1) { if (logger && logger.info) logger.info("WITNESS IS CORRECT"); return true; }
+    if (logger && logger.warn) {
+      if (out.firstBad === -3) logger.warn("WITNESS CHECKING FAILED: wire 0 is not 1");
+      else if (out.firstBad === -2) logger.warn("WITNESS CHECKING FAILED: a wire is not below the field's prime");
+      else logger.warn(`WITNESS CHECKING FAILED: constraint ${out.firstBad} is not satisfied (${out.nBad} violated in all)`);
+    }
+    return false;
   },
 };
 const groth16 = {

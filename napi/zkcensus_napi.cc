@@ -2,13 +2,13 @@
 //
 // Keeps the snarkjs surface the reference imports at ts_inputs/src/example.ts:1 and calls at :358-362:
 //     groth16.fullProve(input, wasmFile, zkeyFile) -> Promise<{proof, publicSignals}>
-//     groth16.prove(zkeyFile, wtnsFile), groth16.verify(vk, publicSignals, proof), wtns.calculate(input, wasmFile, wtnsFile)
+//     groth16.prove(zkeyFile, wtnsFile), groth16.verify(vk, publicSignals, proof), wtns.calculate(input, wasmFile, wtnsFile), wtns.check(r1csFile, wtnsFile)
 // The JS wrapper (index.js) flattens the input object, reads artifact files and formats decimal strings; this file only moves buffers
 // across the ABI.  The event loop is never blocked: fullProve / prove hand their request to the library's proving service (zkc_service_*,
 // csrc/zkc_service.hip) from the main thread and return a promise at once; the service coalesces whatever is pending -- Promise.all over 64
 // fullProve calls is a handful of pipeline passes, not 64 serialised proofs -- and its completion callback comes back to JavaScript through a
 // thread-safe function.  (libuv's pool has four threads: blocking one per proof, as round 2 did, capped a burst at four requests in flight.)
-// wtns.calculate and fullProveBatch run in napi_create_async_work behind one mutex.  libzkcensus.so is dlopen'ed at first use
+// wtns.calculate, wtns.check and fullProveBatch run in napi_create_async_work behind one mutex.  libzkcensus.so is dlopen'ed at first use
 // (path: $ZKCENSUS_LIB or next to the package), so the addon itself builds with plain g++ and N-API >= 4 headers:
 //     g++ -std=c++17 -shared -fPIC -I/usr/include/node napi/zkcensus_napi.cc -o napi/zkcensus.node -ldl
 #include <node_api.h>
@@ -44,6 +44,8 @@ struct Api {
     int (*header_info)(const void*, size_t, uint32_t*, uint32_t*, uint32_t*) = nullptr;
     const char* (*status_text)(int, int32_t) = nullptr;
     int (*inputs_from_json)(const char*, size_t, int, void*, char*, size_t) = nullptr;
+    int (*r1cs_load)(void*, const void*, size_t, void**) = nullptr; void (*r1cs_free)(void*) = nullptr;
+    int (*r1cs_check)(void*, const void*, uint32_t, int, int64_t*, uint32_t*) = nullptr;
     std::string err;
 } g;
 std::mutex g_mu;                       // guards everything below and every use of the shared context / key
@@ -65,6 +67,7 @@ bool load_api(const std::string& hint) {               // caller holds g_mu
     SYM(pool_zkey, "zkc_pool_zkey") SYM(pool_fullprove, "zkc_pool_fullprove_batch")
     SYM(service_default, "zkc_service_default") SYM(service_err, "zkc_service_last_error") SYM(submit_fullprove, "zkc_service_submit_fullprove")
     SYM(submit_prove, "zkc_service_submit_prove") SYM(header_info, "zkc_zkey_header_info") SYM(status_text, "zkc_witness_status_text") SYM(inputs_from_json, "zkc_inputs_from_json")
+    SYM(r1cs_load, "zkc_r1cs_load") SYM(r1cs_free, "zkc_r1cs_free") SYM(r1cs_check, "zkc_r1cs_check")
 #undef SYM
     g.h = h;
     return true;
@@ -81,11 +84,12 @@ std::string assert_text(int nLevels, int32_t status) {
     return t ? std::string(t) : "Assert Failed.\n(witness status " + std::to_string(status) + ")";
 }
 
-enum Kind { FULLPROVE, PROVE, WITNESS, BATCH };
+enum Kind { FULLPROVE, PROVE, WITNESS, BATCH, CHECK };
 struct Work {
     napi_async_work work = nullptr; napi_deferred deferred = nullptr; Kind kind = FULLPROVE;
     std::vector<uint8_t> inputs, zkey, wtns_file, r, s, proof, pub, out; int nLevels = 160; std::string err; std::string libhint;
     std::vector<int> devices; std::vector<uint8_t> rs; std::vector<int32_t> status;      // BATCH
+    std::vector<uint8_t> r1cs; int64_t first_bad = -1; uint32_t n_bad = 0;                // CHECK
     uint8_t rs64[64]; bool has_rs = false;                                                // FULLPROVE / PROVE through the service
     // the .zkey image is NOT copied (tens of MB per call): the JS Buffer is pinned by a reference until complete() and read in place by the worker
     napi_ref zkey_ref = nullptr; const uint8_t* zkey_p = nullptr; size_t zkey_n = 0;
@@ -123,12 +127,24 @@ bool run_batch(Work* w) {
     if (rc && rc != 7 /* ZKC_ERR_WITNESS: per-voter status says which */) { w->err = g.pool_err(g_pool); return false; }
     return true;
 }
+// one .wtns image against one .r1cs image on the shared context (zkc_r1cs_load / zkc_r1cs_check); caller holds g_mu
+bool run_check(Work* w) {
+    const uint8_t* payload = nullptr; uint32_t nw = 0;
+    if (g.wtns_parse(w->wtns_file.data(), w->wtns_file.size(), &payload, &nw)) { w->err = "Invalid witness file"; return false; }
+    void* cs = nullptr;
+    if (g.r1cs_load(g_ctx, w->r1cs.data(), w->r1cs.size(), &cs)) { w->err = g.last_error(g_ctx); return false; }
+    const int rc = g.r1cs_check(cs, payload, nw, 1, &w->first_bad, &w->n_bad);
+    if (rc) w->err = g.last_error(g_ctx);
+    g.r1cs_free(cs);
+    return rc == 0;
+}
 void execute(napi_env, void* data) {
     Work* w = (Work*)data;
     std::lock_guard<std::mutex> guard(g_mu);
     if (!load_api(w->libhint)) { w->err = g.err; return; }
     if (w->kind == BATCH) { run_batch(w); return; }
     if (!ensure_ctx(w->err)) return;
+    if (w->kind == CHECK) { run_check(w); return; }
     std::vector<uint8_t> wtns;                                        // WITNESS: inputs -> .wtns file image
     if (!run_witness(w, wtns)) return;
     const uint32_t nw = (uint32_t)(wtns.size() / 32);
@@ -142,6 +158,11 @@ void settle(napi_env env, Work* w) {                                  // main th
     } else if (w->kind == WITNESS) {
         napi_value b; void* dst; napi_create_buffer_copy(env, w->out.size(), w->out.data(), &dst, &b);
         napi_resolve_deferred(env, w->deferred, b);
+    } else if (w->kind == CHECK) {
+        napi_value obj, f, c;
+        napi_create_object(env, &obj); napi_create_int64(env, w->first_bad, &f); napi_create_uint32(env, w->n_bad, &c);
+        napi_set_named_property(env, obj, "firstBad", f); napi_set_named_property(env, obj, "nBad", c);
+        napi_resolve_deferred(env, w->deferred, obj);
     } else if (w->kind == BATCH) {
         napi_value obj, p, q, st; void* dst;
         napi_create_object(env, &obj);
@@ -248,6 +269,13 @@ napi_value WitnessRaw(napi_env env, napi_callback_info info) {
     w->inputs = buf_arg(env, a[0]); napi_get_value_int32(env, a[1], &w->nLevels); w->libhint = str_arg(env, a[2]);
     return queue(env, w, "zkcensus.wtns.calculate");
 }
+// wtnsCheckRaw(r1cs: Buffer, wtnsFileImage: Buffer, libPath) -> Promise<{firstBad: number (ZKC_R1CS_*: -1 satisfied, or the lowest violated constraint), nBad: number}>
+napi_value WtnsCheckRaw(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value a[3]; napi_get_cb_info(env, info, &argc, a, nullptr, nullptr);
+    Work* w = new Work(); w->kind = CHECK;
+    w->r1cs = buf_arg(env, a[0]); w->wtns_file = buf_arg(env, a[1]); w->libhint = str_arg(env, a[2]);
+    return queue(env, w, "zkcensus.wtns.check");
+}
 // circuitFromWasm(wasm: Buffer, libPath) -> {nLevels: number (-1 = unknown circuit), sha256: string}     (host only)
 napi_value CircuitFromWasm(napi_env env, napi_callback_info info) {
     size_t argc = 2; napi_value a[2]; napi_get_cb_info(env, info, &argc, a, nullptr, nullptr);
@@ -337,7 +365,7 @@ napi_value Init(napi_env env, napi_value exports) {
     napi_create_threadsafe_function(env, nullptr, nullptr, name, 0, 1, nullptr, nullptr, nullptr, settle_js, &g_tsfn);
     napi_unref_threadsafe_function(env, g_tsfn);
 #define EXPORT(name, fn) napi_create_function(env, name, NAPI_AUTO_LENGTH, fn, nullptr, &f); napi_set_named_property(env, exports, name, f);
-    EXPORT("flattenJson", FlattenJson) EXPORT("fullProveRaw", FullProveRaw) EXPORT("fullProveBatchRaw", FullProveBatchRaw) EXPORT("proveRaw", ProveRaw) EXPORT("witnessRaw", WitnessRaw) EXPORT("circuitFromWasm", CircuitFromWasm) EXPORT("verifyJson", VerifyJson) EXPORT("statusText", StatusText) EXPORT("zkeyInfo", ZkeyInfo) EXPORT("decimals", Decimals)
+    EXPORT("flattenJson", FlattenJson) EXPORT("fullProveRaw", FullProveRaw) EXPORT("fullProveBatchRaw", FullProveBatchRaw) EXPORT("proveRaw", ProveRaw) EXPORT("witnessRaw", WitnessRaw) EXPORT("wtnsCheckRaw", WtnsCheckRaw) EXPORT("circuitFromWasm", CircuitFromWasm) EXPORT("verifyJson", VerifyJson) EXPORT("statusText", StatusText) EXPORT("zkeyInfo", ZkeyInfo) EXPORT("decimals", Decimals)
 #undef EXPORT
     return exports;
 }

@@ -128,13 +128,22 @@ def load():
     L.groth16_fullprove.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p, ulp, ctypes.c_char_p, ulp, ctypes.c_char_p, ctypes.c_ulong]
     L.zkc_service_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.zkc_service_submit_fullprove.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, vp, vp]
+    u32p_, i64p = u32p, ctypes.POINTER(ctypes.c_int64)
+    L.zkc_r1cs_header_info.argtypes = [ctypes.c_char_p, sz, u32p_, u32p_, u32p_]
+    L.zkc_r1cs_load.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(vp)]
+    L.zkc_r1cs_free.argtypes = [vp]; L.zkc_r1cs_free.restype = None
+    L.zkc_r1cs_info.argtypes = [vp, u32p_, u32p_, u32p_]
+    L.zkc_r1cs_check.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, i64p, u32p_]
+    L.zkc_r1cs_check_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int, i64p, u32p_]
+    L.zkc_r1cs_check_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     _lib = L
     return L
 
 
-def declared_symbols():
-    """Every `zkc_*` / `groth16_*` function name declared in include/zkcensus.h (used by the CPU export test)."""
+def declared_symbols(header='zkcensus.h'):
+    """Every `zkc_*` / `groth16_*` function name declared in include/zkcensus.h, or in the part of the ABI it includes that `header` names, such as
+    'zkcensus_r1cs.h' (used by the CPU export tests)."""
     import re
-    hdr = open(os.path.join(_HERE, '..', 'include', 'zkcensus.h')).read()
+    hdr = open(os.path.join(_HERE, '..', 'include', header)).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     return sorted(set(re.findall(r'\b((?:zkc|groth16)_[a-z0-9_]+)\s*\(', hdr)))

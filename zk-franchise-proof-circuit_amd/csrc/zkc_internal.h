@@ -71,6 +71,7 @@ struct zkc_ctx {
     // last upload; ms of the last call (host, H2D, kernels)
     void* chk_h[2] = {nullptr, nullptr}; void* chk_d[2] = {nullptr, nullptr}; size_t chk_sz = 0; hipEvent_t chk_ev[2] = {nullptr, nullptr};
     double chk_ms[3] = {0, 0, 0};
+    double r1cs_ms[3] = {0, 0, 0};                     // zkc_r1cs_check_stats (zkc_r1cs.hip): ms of the last load or check (host, H2D, kernels)
     zkc_prof prof;
     unsigned long long* d_prof_entries = nullptr;      // device counter: (digit, point) entries = group additions of the G1 passes while profiling is on
 };

@@ -10,6 +10,22 @@
 
 namespace zkc {
 
+// ---- device helpers the sparse-row kernels of zkc_ntt.hip and zkc_r1cs.hip share: 32-byte loads and stores of a field element, and one term of a row whose coefficients
+// are stored as val R^2 with +1 / -1 marked in the two top bits of the column word (the term is then the wire's Montgomery form from wm, or its negation) ----
+__device__ __forceinline__ Fr ld_fr(const Fr* p) {
+    const uint4* d = reinterpret_cast<const uint4*>(p); uint4 a = d[0], b = d[1];
+    Fr r; r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w; return r;
+}
+__device__ __forceinline__ void st_fr(Fr* p, const Fr& r) {
+    uint4* d = reinterpret_cast<uint4*>(p);
+    d[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]); d[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+}
+constexpr uint32_t MV_UNIT = 0x80000000u, MV_NEG = 0x40000000u, MV_COL = 0x3fffffffu;
+__device__ __forceinline__ Fr mv_term(const Fr* __restrict__ val, const Fr* __restrict__ w, const Fr* __restrict__ wm, uint32_t idx, uint32_t c) {
+    if (wm && (c & MV_UNIT)) { const Fr x = ld_fr(wm + (c & MV_COL)); return (c & MV_NEG) ? fp_neg(x) : x; }
+    return ld_fr(val + idx) * ld_fr(w + (c & MV_COL));
+}
+
 // ---- zkc_ntt.hip (launched from zkc_prove.hip) ----
 extern "C" __global__ void zkc_wtns_mont(const Fr* wtns_std, size_t wtns_stride, Fr* wm, size_t wm_stride, uint32_t nv);
 extern "C" __global__ void zkc_matvec_jds(const uint32_t* perm, const uint32_t* rowlen, const uint32_t* jdptr, const uint32_t* col, const Fr* val, const Fr* wtns_std,
@@ -43,5 +59,10 @@ extern "C" __global__ void zkc_smt_check_absent(PoseidonTable tab, const uint32_
                                                 const uint32_t* roots, uint32_t root_stride, const uint32_t* off, const uint32_t* sib, uint32_t count, int32_t* status);
 extern "C" __global__ void zkc_smt_check_absent_wave(PoseidonTable tab, const uint32_t* keys, const uint32_t* old_keys, const uint32_t* values, const uint32_t* old0,
                                                      const uint32_t* roots, uint32_t root_stride, const uint32_t* off, const uint32_t* sib, uint32_t count, int32_t* status);
+
+// ---- zkc_r1cs.hip: witnesses checked against a resident constraint system ----
+extern "C" __global__ void zkc_r1cs_range(const Fr* wtns_std, size_t wtns_stride, uint32_t nWires, uint32_t* flag);
+extern "C" __global__ void zkc_r1cs_check_rows(const uint4* rows, const uint32_t* jdptr, const uint32_t* col, const Fr* val, const Fr* wtns_std, size_t wtns_stride,
+                                               const Fr* wm_all, size_t wm_stride, uint32_t nCons, uint32_t nlong, uint32_t* first, uint32_t* count, const uint32_t* flag);
 
 }  // namespace zkc

@@ -15,15 +15,6 @@
 
 namespace zkc {
 
-__device__ __forceinline__ Fr ld_fr(const Fr* p) {
-    const uint4* d = reinterpret_cast<const uint4*>(p); uint4 a = d[0], b = d[1];
-    Fr r; r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w; return r;
-}
-__device__ __forceinline__ void st_fr(Fr* p, const Fr& r) {
-    uint4* d = reinterpret_cast<uint4*>(p);
-    d[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]); d[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-
 // ---- buildABC1: rows [0,n) = A, [n,2n) = B ; out = sum coef * w[signal].  coef is stored as val*R^2 (the .zkey
 // convention) so one Montgomery product with the standard-form witness lands in Montgomery form. ----
 // The matrix is kept in jagged-diagonal order (zkc_zkey_load): rows sorted by length, the k-th coefficients of all rows that have one
@@ -38,7 +29,7 @@ __device__ __forceinline__ void st_fr(Fr* p, const Fr& r) {
 // [r4] Coefficients that are +1 or -1 (276 k of the census circuit's 463 k; 84 % of its non-empty rows hold nothing else) are marked in the two top bits of `col` at key load
 // and cost an addition of the wire's MONTGOMERY form, which zkc_wtns_mont makes once per wire (82 754 products per proof) -- the product by the stored val R^2 was doing
 // nothing for them but that conversion, once per TERM.  wm == nullptr: no such buffer (more wires than 3 n), every term is a product as before.
-constexpr uint32_t MV_UNIT = 0x80000000u, MV_NEG = 0x40000000u, MV_COL = 0x3fffffffu;
+// (MV_UNIT / MV_NEG / MV_COL, ld_fr / st_fr and mv_term are in zkc_kernels.h: zkc_r1cs.hip walks its rows with the same term)
 extern "C" __global__ void __launch_bounds__(256)
 zkc_wtns_mont(const Fr* __restrict__ wtns_std, size_t wtns_stride, Fr* __restrict__ wm, size_t wm_stride, uint32_t nv) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,10 +38,6 @@ zkc_wtns_mont(const Fr* __restrict__ wtns_std, size_t wtns_stride, Fr* __restric
 #pragma unroll
     for (int k = 0; k < 8; k++) r2.v[k] = FrParams::r2[k];
     st_fr(wm + (size_t)blockIdx.y * wm_stride + i, ld_fr(wtns_std + (size_t)blockIdx.y * wtns_stride + i) * r2);
-}
-__device__ __forceinline__ Fr mv_term(const Fr* __restrict__ val, const Fr* __restrict__ w, const Fr* __restrict__ wm, uint32_t idx, uint32_t c) {
-    if (wm && (c & MV_UNIT)) { const Fr x = ld_fr(wm + (c & MV_COL)); return (c & MV_NEG) ? fp_neg(x) : x; }
-    return ld_fr(val + idx) * ld_fr(w + (c & MV_COL));
 }
 extern "C" __global__ void __launch_bounds__(256)
 zkc_matvec_jds(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ rowlen, const uint32_t* __restrict__ jdptr,

@@ -24,6 +24,7 @@
 #include "../../include/zkcensus_setup.h"
 
 #include "zkc_hostparse.h"
+#include "zkc_r1cs_parse.h"
 extern "C" int zkc_pairing_bin(const uint8_t g1[64], const uint8_t g2[128], uint8_t out[384]);
 using namespace zkc;
 
@@ -64,8 +65,6 @@ void batch_inverse(std::vector<Fr>& v) {  // in place; zeros stay zero
 struct Term { uint32_t wire; Fr coef; };
 struct Cons { std::vector<Term> a, b, c; };
 
-uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
 void put32(std::vector<uint8_t>& o, uint32_t v) { uint8_t b[4]; memcpy(b, &v, 4); o.insert(o.end(), b, b + 4); }
 void put_raw(std::vector<uint8_t>& o, const void* p, size_t n) { o.insert(o.end(), (const uint8_t*)p, (const uint8_t*)p + n); }
 void put_fq(std::vector<uint8_t>& o, const Fq& a) { put_raw(o, a.v, 32); }                     // Montgomery, as .zkey stores points
@@ -124,37 +123,17 @@ int setup_scalars(const char* r1cs_path, uint64_t seed, SetupScalars& S, char* e
     FILE* f = fopen(r1cs_path, "rb"); if (!f) return fail(err, errlen, std::string("cannot open ") + r1cs_path);
     fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);
     std::vector<uint8_t> buf((size_t)sz); if (fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) { fclose(f); return fail(err, errlen, "short read"); } fclose(f);
-    if (sz < 12 || memcmp(buf.data(), "r1cs", 4)) return fail(err, errlen, "not an r1cs file");
-    uint32_t nsec = rd32(&buf[8]); size_t p = 12; const uint8_t *s1 = nullptr, *s2 = nullptr; uint64_t s2sz = 0;
-    for (uint32_t i = 0; i < nsec; i++) {
-        if (p + 12 > buf.size()) return fail(err, errlen, "r1cs sections truncated");
-        uint32_t id = rd32(&buf[p]); uint64_t n = rd64(&buf[p + 4]); p += 12;
-        const uint64_t have = std::min<uint64_t>(n, buf.size() - p);       // a file cut inside a section: what is there (the constraint walk below says where it ends)
-        if (id == 1) { if (have < 64) return fail(err, errlen, "bad r1cs header"); s1 = &buf[p]; }
-        if (id == 2) { s2 = &buf[p]; s2sz = have; }
-        if (have < n) break;
-        p += n;
-    }
-    if (!s1 || !s2 || rd32(s1) != 32) return fail(err, errlen, "bad r1cs header");
-    for (int i = 0; i < 8; i++) if (rd32(s1 + 4 + 4 * i) != FrParams::p[i]) return fail(err, errlen, "r1cs prime is not BN254 r");
-    const uint32_t nWires = rd32(s1 + 36), nPubOut = rd32(s1 + 40), nPubIn = rd32(s1 + 44), nCons = rd32(s1 + 60);
-    const uint32_t nPub = nPubOut + nPubIn;
-    if (nPub >= nWires) return fail(err, errlen, "bad r1cs header");
+    // ---- parse it (zkc_r1cs_parse.h: the host-only reader, with every check and its text) ----
+    parse::R1cs cs; std::string perr;
+    if (!parse::r1cs_parse(buf.data(), buf.size(), cs, perr)) return fail(err, errlen, perr);
+    const uint32_t nWires = cs.h.nWires, nPub = cs.h.nPub, nCons = cs.h.nCons;
     std::vector<Cons>& cons = S.cons; cons.resize(nCons);
-    {
-        const uint8_t* q = s2; const uint8_t* end = s2 + s2sz;
-        for (uint32_t k = 0; k < nCons; k++) {
-            std::vector<Term>* v[3] = {&cons[k].a, &cons[k].b, &cons[k].c};
-            for (int m = 0; m < 3; m++) {
-                if (q + 4 > end) return fail(err, errlen, "r1cs constraints truncated");
-                uint32_t n = rd32(q); q += 4;
-                if ((uint64_t)n * 36 > (uint64_t)(end - q)) return fail(err, errlen, "r1cs constraints truncated");
-                v[m]->resize(n);
-                for (uint32_t t = 0; t < n; t++) {
-                    uint32_t s[8]; (*v[m])[t].wire = rd32(q); memcpy(s, q + 4, 32); (*v[m])[t].coef = fp_from_std<FrParams>(s); q += 36;
-                    if ((*v[m])[t].wire >= nWires) return fail(err, errlen, "r1cs wire index out of range");
-                }
-            }
+    for (uint32_t k = 0; k < nCons; k++) {
+        std::vector<Term>* v[3] = {&cons[k].a, &cons[k].b, &cons[k].c};
+        for (int m = 0; m < 3; m++) {
+            const uint64_t t0 = cs.ptr[m][k], t1 = cs.ptr[m][k + 1];
+            v[m]->resize((size_t)(t1 - t0));
+            for (uint64_t t = t0; t < t1; t++) { uint32_t s[8]; memcpy(s, cs.terms[m][t].coef, 32); (*v[m])[t - t0] = Term{cs.terms[m][t].wire, fp_from_std<FrParams>(s)}; }
         }
     }
     uint32_t logn = 0; while ((1u << logn) < nCons + nPub + 1) logn++;

@@ -137,6 +137,18 @@ def _wtns_payload(wtns_file):
     return raw[off:off + 32 * n.value]
 
 
+def wtns_check(ctx, r1cs_src, wtns_file):
+    """snarkjs.wtns.check for one witness: does the .wtns image (path, bytes or {type: 'mem'}) satisfy every constraint of the .r1cs (path or bytes)?  Checked on ctx's
+    GPU (r1cs.Device); a batch, or the index of the violated constraint, is Device.check's business."""
+    from . import r1cs
+    payload = _wtns_payload(wtns_file)
+    with r1cs.Device(ctx, r1cs_src if isinstance(r1cs_src, str) else _read(r1cs_src)) as dev:
+        if len(payload) != 32 * dev.info[0]:
+            raise ValueError('Invalid witness length. Circuit: %d, witness: %d' % (dev.info[0], len(payload) // 32))
+        first, _ = dev.check(payload, 1)
+    return first[0] == r1cs.SATISFIED
+
+
 def prove(zkey_file, wtns_file, rs=None):
     pk = _key(zkey_file)
     r, s = rs if rs is not None else (secrets.randbelow(R_MOD), secrets.randbelow(R_MOD))

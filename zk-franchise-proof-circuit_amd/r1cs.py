@@ -8,7 +8,11 @@ is this build's own -- equivalent in meaning, not claimed identical to circom's 
 (a) A.w * B.w == C.w on reference-wasm witnesses and (b) rejection of mutated witnesses (tests/test_r1cs.py).
 
 A linear combination is a dict {wire: coef mod r}; wire 0 is the constant one.
+
+`Device` is the other direction: any iden3 .r1cs image made resident on the GPU (include/zkcensus_r1cs.h), against which witnesses are checked in batches --
+`snarkjs wtns check`.  `R1CS.check` below stays the restatement the tests hold it to.
 """
+import ctypes
 import json
 import os
 import struct
@@ -448,3 +452,85 @@ def build(nLevels=160):
     smt_verifier(cs, L, L.off_sikver, 10, W(L.off_sik), 6, 13 + nLevels)
     # voteHash (wires 4,5) is deliberately unconstrained (census.circom:54-57)
     return L, cs
+
+
+# ---------------- the device-resident checker (include/zkcensus_r1cs.h) ----------------
+SATISFIED, WIRE_RANGE, NOT_ONE = -1, -2, -3      # ZKC_R1CS_*: verdicts below zero; any other verdict is the lowest violated constraint, in file order
+
+
+def _image(src):
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytes(src)
+    with open(src, 'rb') as f:
+        return f.read()
+
+
+def header_info(src):
+    """(nWires, nPublic, nConstraints) of an .r1cs given as a path or bytes, from the image alone: host only (zkc_r1cs_header_info)."""
+    from . import _native
+    lib = _native.load()
+    raw = _image(src)
+    a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    rc = lib.zkc_r1cs_header_info(raw, len(raw), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+    if rc != 0:
+        raise _native.ZkcError(rc, (lib.zkc_last_error(None) or b'').decode())
+    return a.value, b.value, c.value
+
+
+class Device:
+    """An .r1cs (path or bytes) with its A, B and C matrices resident on ctx's GPU.  A context manager; `info` = (nWires, nPublic, nConstraints)."""
+
+    def __init__(self, ctx, src):
+        self.ctx, self._lib = ctx, ctx._lib
+        raw = _image(src)
+        h = ctypes.c_void_p()
+        ctx._check(self._lib.zkc_r1cs_load(ctx._h, raw, len(raw), ctypes.byref(h)))
+        self._h = h
+        a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._lib.zkc_r1cs_info(h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        self.info = (a.value, b.value, c.value)
+
+    def close(self):
+        if getattr(self, '_h', None):
+            if getattr(self.ctx, '_h', None):
+                self._lib.zkc_r1cs_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _run(self, fn, buf, B):
+        first, count = (ctypes.c_int64 * B)(), (ctypes.c_uint32 * B)()
+        self.ctx._check(fn(self._h, buf, self.info[0], B, first, count))
+        return list(first), list(count)
+
+    def check(self, wtns, B=None):
+        """wtns: B witnesses of nWires x 32 bytes each, contiguous (what Context.witness returns, joined).  Returns (first_bad, n_bad): per witness SATISFIED, WIRE_RANGE,
+        NOT_ONE or the lowest violated constraint, and the number of violated constraints."""
+        wtns = bytes(wtns)
+        size = 32 * self.info[0]
+        if B is None:
+            B = len(wtns) // size
+        if B <= 0 or len(wtns) != B * size:
+            raise ValueError('check: the witnesses must be B x %d x 32 bytes' % self.info[0])
+        return self._run(self._lib.zkc_r1cs_check, wtns, B)
+
+    def check_dev(self, wtns, B):
+        """The same on a device buffer of B witnesses: a torch tensor (anything with data_ptr()) or a raw device pointer."""
+        ptr = wtns.data_ptr() if hasattr(wtns, 'data_ptr') else int(wtns)
+        return self._run(self._lib.zkc_r1cs_check_dev, ctypes.c_void_p(ptr), int(B))
+
+    def stats(self):
+        """ms of the context's last load or check: (host, host-to-device copies, kernels)"""
+        ms = (ctypes.c_double * 3)()
+        self.ctx._check(self._lib.zkc_r1cs_check_stats(self.ctx._h, ms))
+        return tuple(ms)
