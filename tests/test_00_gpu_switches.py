@@ -17,16 +17,69 @@ CONFIGS = [
 ]
 
 
+_failed = []                                             # the configuration of a child that failed or ran out of time (a fault, a hang): no test of this file starts a further child
+
+
+def _child(script, cfg):
+    """one configuration in a child process: its own time limit, and its exit status looked at before anything it printed"""
+    if _failed:
+        pytest.fail('no child started: an earlier one failed under %r' % (_failed[0],))
+    env = {k: v for k, v in os.environ.items() if not k.startswith('ZKC_')}
+    env.update(cfg)
+    try:                                                 # (a box that refuses to start a child program from this process raises OSError: a failure, not a skip)
+        r = subprocess.run([sys.executable, os.path.join(ol.ROOT, 'tests', 'host', script)], env=env, capture_output=True, text=True, timeout=300)
+    except subprocess.TimeoutExpired:
+        _failed.append(cfg)
+        raise
+    if r.returncode != 0:
+        _failed.append(cfg)
+    assert r.returncode == 0, (cfg, r.returncode, r.stderr[-1500:])
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
 def test_switches_do_not_change_a_byte():
-    script = os.path.join(ol.ROOT, 'tests', 'host', 'prove_digest.py')
-    digests = []
-    for cfg in CONFIGS:
-        env = {k: v for k, v in os.environ.items() if not k.startswith('ZKC_')}
-        env.update(cfg)
-        try:
-            r = subprocess.run([sys.executable, script], env=env, capture_output=True, text=True, timeout=300)
-        except OSError as e:                             # the box refused to start a child program from this process
-            pytest.skip('cannot start a child process here: %s' % e)
-        assert r.returncode == 0, (cfg, r.stderr[-1500:])
-        digests.append(json.loads(r.stdout.strip().splitlines()[-1])['sha256'])
+    digests = [_child('prove_digest.py', cfg)['sha256'] for cfg in CONFIGS]
     assert len(set(digests)) == 1, [(c, d[:12]) for c, d in zip(CONFIGS, digests)]
+
+
+# Switches that no configuration above runs: the one-wave-per-task blinding for every pass, the lane-per-segment G2 accumulation of small passes, a key without the
+# lone-proof G2 table, the G2 MSM behind the G1 sort, the G2 accumulation never held, unchained G1 accumulations over two lanes, fold flags awaited instead of the early
+# layout, other window bits for the H section and for the second section tables (taken by every pass: ZKC_DEEP_WIRES=1), every stage on one stream.
+UNVISITED = [
+    {'ZKC_FINALIZE_WAVES': '1'}, {'ZKC_G2_BUCKET_WAVE': '0'}, {'ZKC_G2_LONE_TABLE': '0'}, {'ZKC_G2_LATE': '1'}, {'ZKC_G2_ACC_EARLY': '1'},
+    {'ZKC_ACC_CHAIN': '0', 'ZKC_LANES': '2', 'ZKC_INFLIGHT': '40'}, {'ZKC_EARLY_LAYOUT': '0'}, {'ZKC_C_H': '13'},
+    {'ZKC_C_DEEP': '13', 'ZKC_DEEP_TABLES': '2', 'ZKC_DEEP_WIRES': '1', 'ZKC_INFLIGHT': '40'}, {'ZKC_SERIAL_STREAMS': '1'},
+]
+
+
+@pytest.fixture(scope='module')
+def default_digest():
+    return _child('prove_digest.py', {})['sha256']
+
+
+@pytest.mark.parametrize('cfg', UNVISITED, ids=lambda c: ','.join('%s=%s' % kv for kv in c.items()))
+def test_unvisited_switches_do_not_change_a_byte(default_digest, cfg):
+    assert _child('prove_digest.py', cfg)['sha256'] == default_digest, cfg          # (a digest that differs is a finding, not a reason to stop: the child ended well)
+
+
+def test_blinding_forms_agree_at_scalar_edges():
+    """Passes of 5 and of 65 proofs (one pass each: ZKC_INFLIGHT=128 in tests/host/blind_digest.py) with the edge (r, s) pairs of tests/blinding_cases.py, each unfolded
+    (with the foreign witness) and folded (voters only), through the lane-per-product kernels (default) and through zkc_finalize (ZKC_FINALIZE_WAVES, 65 workgroups):
+    the same bytes, and the CPU oracle's, computed here in the parent."""
+    import blinding_cases as bc
+    from zkcensus_amd import setup
+    outs = [_child('blind_digest.py', cfg) for cfg in ({}, {'ZKC_FINALIZE_WAVES': '1'})]
+    zk = open(setup.artifact_paths(bc.NL)[1], 'rb').read()                # the children made sure of the key; this process reads the file and never loads the library
+    want, cache = {}, {}
+    for n, foreign in ((5, True), (65, True), (5, False), (65, False)):
+        jobs = list(zip(*bc.batch(n, with_foreign=foreign)[:2]))
+        todo = [j for j in dict.fromkeys(jobs) if j not in cache]
+        for j, (rc, proof, _) in zip(todo, ol.pmap(lambda j: ol.prove(zk, j[0], *j[1]), todo)):
+            assert rc == 0
+            cache[j] = proof
+        want[str(n) + ('' if foreign else 'f')] = b''.join(cache[j] for j in jobs).hex()
+    assert all(set(o) == set(want) for o in outs)
+    for n in want:
+        bad = [[q for q in range(len(want[n]) // 512) if o[n][512 * q:512 * q + 512] != want[n][512 * q:512 * q + 512]] for o in outs]
+        assert bad == [[], []], (n, 'proofs that differ from the oracle (lane per product, wave per task)', bad)
+    assert outs[0] == outs[1]
