@@ -136,6 +136,16 @@ def load():
     L.zkc_r1cs_check.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, i64p, u32p_]
     L.zkc_r1cs_check_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int, i64p, u32p_]
     L.zkc_r1cs_check_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    szp = ctypes.POINTER(sz)
+    L.zkc_g1_scale_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int, vp]
+    L.zkc_blake2b512.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p]; L.zkc_blake2b512.restype = None
+    L.zkc_zkey_contributions.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, u32p, ctypes.c_char_p, szp, ctypes.c_char_p, sz]
+    L.zkc_zkey_contribute.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, szp, ctypes.c_char_p]
+    L.zkc_zkey_verify_contributions.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_char_p, u32p, ctypes.c_char_p, sz]
+    L.zkc_phase2_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.zkc_debug_phase2_challenge_g2.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+    L.zkc_debug_phase2_host_scale.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]
     _lib = L
     return L
 

@@ -83,6 +83,31 @@ ZKC_HD void f29_pt_dbl(Acc29& r, const Acc29& a) {
 #pragma unroll
     for (int k = 0; k < 9; k++) { r.X[k] = X3[k]; r.Y[k] = Y3[k]; r.ZZ[k] = T[k]; r.ZZZ[k] = S[k]; }
 }
+// doubling INSIDE the accumulator invariant of f29_madd (in and out: X, Y < 10.5 p carried, ZZ, ZZZ < 4 p), for chains that alternate doublings and mixed
+// additions on one accumulator (zkc_phase2.hip).  f29_pt_dbl returns X < 25.9 p, which f29_madd's D25 does not dominate; here the subtractions ride on the
+// reductions as in f29_madd and the dominators are sized for the tighter inputs.  a finite.
+//   U = 2Y < 21 p (limbs < 2^30) ; V = U^2 < 3.7 p ; W = U V < 1.5 p ; S = X V < 1.3 p ; M = 3 X^2 < 5 p (carried)
+//   X3 = M^2 / 2^261 + (D24x2 - 2S) < 0.2 + 6.3 + 1 = 7.5 p ; T = S - X3 + D25 < 13 p (limbs < 1.5 * 2^30)
+//   Y3 = (M T + (D25 - Y) W) / 2^261 + p < 1.6 p (columns: 2^29 * 1.5 * 2^30 + 2^30 * 2^29 = 2^60.33) ; ZZ3 = V ZZ < 1.1 p ; ZZZ3 = W ZZZ < 1.1 p
+ZKC_HD void f29_acc_dbl(Acc29& a) {
+    typedef FqParams P;
+    constexpr L9 D24x2 = f29_dominator<FqParams>(2u << 29, 1u << 24);      // dominates 2S: limbs < 2^30, top limb < 2 * 1.3 p / 2^232 < 2^24
+    uint32_t U[9], V[9], W[9], S[9], M[9], T[9], nY[9];
+    f29_add(U, a.Y, a.Y);
+    f29_mul<P>(V, U, U); f29_mul<P>(W, U, V); f29_mul<P>(S, a.X, V);
+    f29_sqr<P>(T, a.X);
+#pragma unroll
+    for (int k = 0; k < 9; k++) M[k] = 3 * T[k];
+    f29_carry(M);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { T[k] = D24x2.l[k] - 2 * S[k]; nY[k] = Dom29::D25.l[k] - a.Y[k]; }
+    f29_sqr_addhi<P>(a.X, M, T);
+    f29_sub(T, S, a.X, Dom29::D25);
+    f29_mul2sum<P>(a.Y, M, T, nY, W);
+    f29_mul<P>(T, V, a.ZZ); f29_mul<P>(S, W, a.ZZZ);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { a.ZZ[k] = T[k]; a.ZZZ[k] = S[k]; }
+}
 // full addition (add-2008-s), complete.  U1, U2, S1, S2 < 7.1 p ; P, R (+ D25) < 18.7 p ; PP, RR < 3.1 p ; PPP < 1.4 p ; Q < 1.2 p ;
 // X3 = RR - PPP - 2Q + D24x3 < 9.4 p ; W = Q - X3 + D25 < 12.8 p ; Y3 = R W - S1 PPP + D24 < 8.7 p ; ZZ3, ZZZ3 < 1.2 p
 ZKC_HD void f29_pt_add(Acc29& r, const Acc29& a, const Acc29& b) {

@@ -160,6 +160,14 @@ zkc_fixed_affine(const XYZZ<F>* __restrict__ in, F* __restrict__ pre, uint32_t n
 
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
+// the second launch of a batch: d_sum (n XYZZ points) -> d_out (n affine points), d_pre = n x F of work space; enqueued on ctx->stream, not waited for
+template <class F>
+hipError_t launch_affine(zkc_ctx* ctx, const XYZZ<F>* d_sum, F* d_pre, uint32_t n, bool out_mont, void* d_out) {
+    const uint32_t nlanes = (n + FIXED_INV_CHUNK - 1) / FIXED_INV_CHUNK;
+    hipLaunchKernelGGL(zkc_fixed_affine<F>, dim3((nlanes + 63) / 64), dim3(64), 0, ctx->stream, d_sum, d_pre, n, nlanes, out_mont ? 1 : 0, (uint32_t*)d_out);
+    return hipGetLastError();
+}
+
 template <class F, class Launch>
 int fixed_mul(zkc_ctx* ctx, const char* what, uint32_t n, void* d_out, bool out_mont, Launch launch_acc) {
     XYZZ<F>* d_sum = nullptr; F* d_pre = nullptr;
@@ -167,9 +175,7 @@ int fixed_mul(zkc_ctx* ctx, const char* what, uint32_t n, void* d_out, bool out_
     if (e == hipSuccess) e = hipMalloc((void**)&d_pre, (size_t)n * sizeof(F));
     if (e == hipSuccess) {
         launch_acc(d_sum);
-        const uint32_t nlanes = (n + FIXED_INV_CHUNK - 1) / FIXED_INV_CHUNK;
-        hipLaunchKernelGGL(zkc_fixed_affine<F>, dim3((nlanes + 63) / 64), dim3(64), 0, ctx->stream, d_sum, d_pre, n, nlanes, out_mont ? 1 : 0, (uint32_t*)d_out);
-        e = hipGetLastError();
+        e = launch_affine<F>(ctx, d_sum, d_pre, n, out_mont, d_out);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
     if (d_sum) (void)hipFree(d_sum);
@@ -220,6 +226,16 @@ int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, dou
         *d_table29 = nullptr;
         return rc ? rc : zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_table_g2: ") + hipGetErrorString(e));
     }
+    return ZKC_OK;
+}
+
+int fixed_affine_g1(zkc_ctx* ctx, const G1XYZZ* d_in, uint32_t n, void* d_out, bool out_mont) {
+    Fq* d_pre = nullptr;
+    hipError_t e = hipMalloc((void**)&d_pre, (size_t)n * sizeof(Fq));
+    if (e == hipSuccess) e = launch_affine<Fq>(ctx, d_in, d_pre, n, out_mont, d_out);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (d_pre) (void)hipFree(d_pre);
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_affine_g1: ") + hipGetErrorString(e));
     return ZKC_OK;
 }
 

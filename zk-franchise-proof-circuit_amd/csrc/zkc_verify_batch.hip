@@ -32,17 +32,25 @@ using namespace zkc::pairing;
 namespace {
 struct Xoshiro { uint64_t s[4]; uint64_t next() { auto rotl = [](uint64_t x, int k) { return (x << k) | (x >> (64 - k)); };
     const uint64_t r = rotl(s[1] * 5, 7) * 9, t = s[1] << 17; s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = rotl(s[3], 45); return r; } };
-// the weights of a call, all from the one generator before anything is parsed (the same whatever the number of parsing threads): rho[i] for A_i and again at rho[N + i] for C_i
-std::vector<uint32_t> draw_weights(const uint8_t* seed32, int N) {
+}  // namespace
+// n weights of 128 bits (n x 8 words, the top four zero) from the one generator: what every batch check of the library draws its weights with (zkc_verify_host.h)
+std::vector<uint32_t> zkc::verify_weights(const uint8_t* seed32, size_t n) {
     Xoshiro rng;
     if (seed32) memcpy(rng.s, seed32, 32); else { std::random_device rd; for (auto& x : rng.s) x = ((uint64_t)rd() << 32) | rd(); }
     if (!(rng.s[0] | rng.s[1] | rng.s[2] | rng.s[3])) rng.s[0] = 1;
-    std::vector<uint32_t> rho(8 * 2 * (size_t)N, 0);
-    for (int i = 0; i < N; i++) {
-        uint32_t* r = rho.data() + 8 * (size_t)i;
+    std::vector<uint32_t> rho(8 * n, 0);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t* r = rho.data() + 8 * i;
         const uint64_t lo = rng.next(), hi = rng.next(); r[0] = (uint32_t)lo; r[1] = (uint32_t)(lo >> 32); r[2] = (uint32_t)hi; r[3] = (uint32_t)(hi >> 32);
-        memcpy(rho.data() + 8 * ((size_t)N + i), r, 32);
     }
+    return rho;
+}
+namespace {
+// the weights of a call, all from the one generator before anything is parsed (the same whatever the number of parsing threads): rho[i] for A_i and again at rho[N + i] for C_i
+std::vector<uint32_t> draw_weights(const uint8_t* seed32, int N) {
+    std::vector<uint32_t> rho = verify_weights(seed32, (size_t)N);
+    rho.resize(8 * 2 * (size_t)N);
+    std::copy(rho.begin(), rho.begin() + 8 * (size_t)N, rho.begin() + 8 * (size_t)N);
     return rho;
 }
 

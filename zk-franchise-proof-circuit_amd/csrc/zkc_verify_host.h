@@ -27,6 +27,9 @@ std::shared_ptr<const VkReady> vk_ready(const uint8_t* vk, int nPublic, int* cod
 // sum_j k_j P_j over a handful of points (the public-input combination vk_x): one doubling chain shared by all scalars, mixed additions
 G1XYZZ g1_sum_of_products(const G1Affine* pts, const uint32_t (*k)[8], int n);
 
+// n weights of 128 bits as n x 8 little-endian words, from the verifiers' generator: seeded by seed32 (reproducible: tests) or, NULL, from the OS (zkc_verify_batch.hip)
+std::vector<uint32_t> verify_weights(const uint8_t* seed32, size_t n);
+
 std::string& verify_error();                       // the calling thread's text behind zkc_verify_last_error
 int vfail(int code, const std::string& m);         // sets that text, returns code
 }  // namespace zkc

@@ -1,7 +1,8 @@
 """The NTT and G1 MSM engines on their own -- the ffjavascript calls under snarkjs' groth16.prove (`Fr.fft`, `Fr.ifft`,
 `G1.multiExpAffine`; ts_inputs/src/example.ts:358) over device buffers.  Thin ctypes wrappers of include/zkcensus.h
 zkc_ntt_dev / zkc_g1_mul_batch_dev / zkc_msm_g1_*; used by SURVEY.md 8(d) config 5 (ii) (tools/stress.py) and its parity tests.
-g1_fixed_mul / g2_fixed_mul (include/zkcensus_setup.h) are the windowed fixed-base batch products the device key generator is built from."""
+g1_fixed_mul / g2_fixed_mul (include/zkcensus_setup.h) are the windowed fixed-base batch products the device key generator is built from; g1_scale
+(include/zkcensus_phase2.h) is the opposite shape, many points times one scalar, which a phase-2 contribution is made of."""
 import ctypes
 
 R_MONT = 1 << 256
@@ -34,6 +35,14 @@ def g1_fixed_mul(ctx, base64, d_scalars_ptr, n, d_out_ptr):
 def g2_fixed_mul(ctx, base128, d_scalars_ptr, n, d_out_ptr):
     """The same in G2: base and outputs 128 B (x.c0 | x.c1 | y.c0 | y.c1), the base on the twist."""
     ctx._check(ctx._lib.zkc_g2_fixed_mul_dev(ctx._h, bytes(base128), d_scalars_ptr, n, d_out_ptr))
+
+
+def g1_scale(ctx, d_points_ptr, n, k, d_out_ptr, mont=False):
+    """d_out[i] = k * d_points[i]: n affine points (64 B, all zero = infinity) times ONE scalar k (an int below r, or its 32 little-endian bytes); include/zkcensus_phase2.h.
+    mont: the coordinates are in Montgomery form on both sides, as a .zkey stores them.  d_out may equal d_points.  A point off the curve raises (ZKC_ERR_FORMAT, the index in
+    the text)."""
+    kb = k.to_bytes(32, 'little') if isinstance(k, int) else bytes(k)
+    ctx._check(ctx._lib.zkc_g1_scale_dev(ctx._h, d_points_ptr, n, kb, 1 if mont else 0, d_out_ptr))
 
 
 def fixed_mul_window():
