@@ -23,3 +23,31 @@ def test_kernel_declarations_live_in_the_header_only():
         text = open(p).read()
         if any(re.search(r'\b%s\b' % k, text) for k in declared):
             assert '#include "zkc_kernels.h"' in text, os.path.basename(p)
+
+
+def test_host_helpers_are_defined_once_and_declared_in_headers():
+    """The host-side helpers that several files used to carry private copies of exist once in csrc (zkc_host_util.h, zkc_internal.h), and no .hip file declares a function of
+    another file by hand: those declarations live in zkc_internal.h, zkc_prover.h and the public header, where the defining file sees them too."""
+    files = sorted(glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, '*.h')))
+    assert len(files) >= 30
+    text = {os.path.basename(p): open(p).read() for p in files}
+
+    def definitions(pattern):
+        return [(f, m.group(0)) for f, t in text.items() for m in re.finditer(pattern, t)]
+    body = r'\s*\([^;{}]*\)\s*(?:const\s*)?\{'                                      # a parameter list followed by a body
+    assert [f for f, _ in definitions(r'\b\w*root_of_unity' + body)] == ['zkc_host_util.h']
+    assert [m.split('(')[0].split()[-1] for _, m in definitions(r'\b\w*root_of_unity' + body)] == ['fr_root_of_unity']
+    assert [f for f, _ in definitions(r'\bg2_generator' + body)] == ['zkc_host_util.h']
+    assert [f for f, _ in definitions(r'\bg1_generator' + body)] == ['zkc_host_util.h']
+    assert [f for f, _ in definitions(r'\bstruct\s+DevBuf\b[^;{]*\{')] == ['zkc_internal.h']
+    assert [f for f, _ in definitions(r'\berr_out' + body)] == ['zkc_host_util.h']
+    # the millisecond timer: one function, and one place that turns a clock difference into milliseconds
+    assert [f for f, _ in definitions(r'\bdouble\s+ms_\w+' + body)] == ['zkc_host_util.h']
+    assert [f for f, _ in definitions(r'duration\s*<\s*double\s*,\s*std::milli\s*>')] == ['zkc_host_util.h']
+    assert [f for f, _ in definitions(r'0xd992f6edu')] == ['zkc_host_util.h']       # first word of the G2 generator
+    # body-less declarations of cross-file functions: in headers only
+    # a type, then the name, a parameter list and a semicolon (a call has no type in front of it)
+    for name in ('zkc_lane_streams', 'zkc_get_template', 'zkc_witness_chunk_async', 'zkc_ctx_lanes_destroy', 'zkc_pairing_bin'):
+        decl = re.compile(r'^[ \t]*(?:extern\s+"C"\s+)?(?!return\b|else\b)(?:[A-Za-z_][\w:]*(?:\s*[\*&]+\s*|\s+))+%s\s*\([^;{}]*\)\s*;' % name, re.M)
+        assert [f for f, t in text.items() if f.endswith('.hip') and decl.search(t)] == [], name
+        assert sum(len(decl.findall(t)) for f, t in text.items() if f.endswith('.h')) <= 1, name

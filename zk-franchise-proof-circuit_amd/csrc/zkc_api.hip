@@ -38,7 +38,6 @@ hipError_t zkc_wait_stream(hipStream_t st, hipEvent_t scratch_ev) {
     const hipError_t e = hipEventRecord(scratch_ev, st);
     return e != hipSuccess ? e : zkc_wait_event(scratch_ev);
 }
-void zkc_ctx_lanes_destroy(zkc_ctx* ctx);      // zkc_prove.hip
 int zkc_ensure(zkc_ctx* ctx, void** p, size_t* cur, size_t need) {
     if (*cur >= need) return ZKC_OK;
     if (*p) { ZKC_HIP_CHECK(ctx, hipFree(*p)); *p = nullptr; *cur = 0; }
@@ -256,23 +255,15 @@ extern "C" int zkc_circuit_n_wires(int nLevels) { return nLevels < 3 ? 0 : Witne
 static int get_template(zkc_ctx* ctx, const WitnessLayout& L, uint32_t** out) {
     auto it = ctx->tmpl.find(L.nL);
     if (it != ctx->tmpl.end()) { *out = it->second; return ZKC_OK; }
-    uint32_t *d_t = nullptr, *d_in = nullptr; int32_t* d_st = nullptr;
-    const int rc = [&]() -> int {
-        ZKC_HIP_CHECK(ctx, hipMalloc(&d_t, (size_t)L.nWires * 32));
-        ZKC_HIP_CHECK(ctx, hipMalloc(&d_in, (size_t)L.nInputs * 32));
-        ZKC_HIP_CHECK(ctx, hipMalloc(&d_st, 3 * sizeof(int32_t)));
-        ZKC_HIP_CHECK(ctx, hipMemsetAsync(d_t, 0, (size_t)L.nWires * 32, ctx->stream));
-        ZKC_HIP_CHECK(ctx, hipMemsetAsync(d_in, 0, (size_t)L.nInputs * 32, ctx->stream));
-        hipLaunchKernelGGL(zkc_witness_chains_wave, dim3(3), dim3(64), 0, ctx->stream, L, ctx->ptab, d_in, d_t, d_st, 1, 1);
-        hipLaunchKernelGGL(zkc_witness_tostd, dim3((L.nWires + 255) / 256), dim3(256), 0, ctx->stream, d_t, (size_t)L.nWires);
-        ZKC_HIP_CHECK(ctx, hipGetLastError());
-        ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        return ZKC_OK;
-    }();
-    if (d_in) (void)hipFree(d_in);
-    if (d_st) (void)hipFree(d_st);
-    if (rc) { if (d_t) (void)hipFree(d_t); return rc; }                  // a failed build leaves nothing behind
-    ctx->tmpl[L.nL] = d_t; *out = d_t;
+    DevBuf t, in, st; int rc;                                            // a failed build leaves nothing behind
+    if ((rc = t.alloc(ctx, (size_t)L.nWires * 32)) || (rc = in.alloc(ctx, (size_t)L.nInputs * 32)) || (rc = st.alloc(ctx, 3 * sizeof(int32_t)))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(t.p, 0, (size_t)L.nWires * 32, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(in.p, 0, (size_t)L.nInputs * 32, ctx->stream));
+    hipLaunchKernelGGL(zkc_witness_chains_wave, dim3(3), dim3(64), 0, ctx->stream, L, ctx->ptab, in.as<uint32_t>(), t.as<uint32_t>(), st.as<int32_t>(), 1, 1);
+    hipLaunchKernelGGL(zkc_witness_tostd, dim3((L.nWires + 255) / 256), dim3(256), 0, ctx->stream, t.as<uint32_t>(), (size_t)L.nWires);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tmpl[L.nL] = *out = (uint32_t*)t.release();
     return ZKC_OK;
 }
 

@@ -88,12 +88,6 @@ bool trie_build(const uint8_t* keys, size_t n, int max_levels, Trie& t, std::str
     }
     return true;
 }
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(zkc_ctx* ctx, size_t bytes) { ZKC_HIP_CHECK(ctx, hipMalloc(&p, bytes ? bytes : 4)); return ZKC_OK; }
-    template <class T> T* as() { return (T*)p; }
-};
 // `bytes` of host memory into a fresh device buffer, on ctx->stream (the source stays alive until the stream is next synchronised)
 int upload(zkc_ctx* ctx, DevBuf& d, const void* src, size_t bytes) {
     int rc; if ((rc = d.alloc(ctx, bytes))) return rc;

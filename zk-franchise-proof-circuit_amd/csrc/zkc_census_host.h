@@ -3,7 +3,7 @@
 // from (node, left, right) triples, and assembling voters' input blocks.  Product code, host only.
 #pragma once
 #include "zkc_internal.h"      // brings zkc_device.h and zkc_field.h
-#include <chrono>
+#include "zkc_host_util.h"     // clk, ms_since
 #include <cstring>
 
 namespace zkc {
@@ -16,8 +16,6 @@ inline bool all_below_r(const void* v, size_t count) {
 inline bool is_zero(const uint8_t* v) { uint64_t w[4]; memcpy(w, v, 32); return (w[0] | w[1] | w[2] | w[3]) == 0; }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int key_bit(const uint8_t* key, int d) { return (key[d >> 3] >> (d & 7)) & 1; }          // path bit d of a 32-byte key (LSB first)
-using clk = std::chrono::steady_clock;
-inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
 // A voter's block of circuit inputs in 32-byte slots, census.circom:51-67 order: the twelve scalars, then the census and the SIK sibling list, nLevels + 1 slots each
 // (zkc_circuit_n_inputs(nLevels) slots in all).  zkc_census_scalars and the witness kernels (zkc_witness.hip) read the same order on the device.

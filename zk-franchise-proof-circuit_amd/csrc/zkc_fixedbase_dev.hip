@@ -8,7 +8,6 @@
 //   zkc_fixed_affine<F>      XYZZ -> affine without an inversion per point: a lane takes FIXED_INV_CHUNK points (strided, so that the lanes of a wave read neighbours),
 //                            multiplies their ZZZ up (Montgomery's trick), inverts the product once and walks back: 3 products per point plus 1 / 8 of an inversion
 // The tables live in global memory (G1: 8160 x 64 B = 510 KB; G2: 8160 x 240 B = 1.9 MB in the row format of zkc_g2_table29) and are built on the host.
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -18,6 +17,8 @@
 #include "zkc_f29.h"
 #include "zkc_f29_g1.h"
 #include "zkc_f29_g2.h"
+#include "zkc_host_util.h"
+#include "zkc_pairing.h"
 #include "../../include/zkcensus_setup.h"
 
 using namespace zkc;
@@ -158,8 +159,6 @@ zkc_fixed_affine(const XYZZ<F>* __restrict__ in, F* __restrict__ pre, uint32_t n
     }
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
 // the second launch of a batch: d_sum (n XYZZ points) -> d_out (n affine points), d_pre = n x F of work space; enqueued on ctx->stream, not waited for
 template <class F>
 hipError_t launch_affine(zkc_ctx* ctx, const XYZZ<F>* d_sum, F* d_pre, uint32_t n, bool out_mont, void* d_out) {
@@ -170,27 +169,13 @@ hipError_t launch_affine(zkc_ctx* ctx, const XYZZ<F>* d_sum, F* d_pre, uint32_t 
 
 template <class F, class Launch>
 int fixed_mul(zkc_ctx* ctx, const char* what, uint32_t n, void* d_out, bool out_mont, Launch launch_acc) {
-    XYZZ<F>* d_sum = nullptr; F* d_pre = nullptr;
-    hipError_t e = hipMalloc((void**)&d_sum, (size_t)n * sizeof(XYZZ<F>));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_pre, (size_t)n * sizeof(F));
-    if (e == hipSuccess) {
-        launch_acc(d_sum);
-        e = launch_affine<F>(ctx, d_sum, d_pre, n, out_mont, d_out);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    if (d_sum) (void)hipFree(d_sum);
-    if (d_pre) (void)hipFree(d_pre);
+    DevBuf sum, pre; int rc;
+    if ((rc = sum.alloc(ctx, (size_t)n * sizeof(XYZZ<F>))) || (rc = pre.alloc(ctx, (size_t)n * sizeof(F)))) return rc;
+    launch_acc(sum.as<XYZZ<F>>());
+    hipError_t e = launch_affine<F>(ctx, sum.as<XYZZ<F>>(), pre.as<F>(), n, out_mont, d_out);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return ZKC_OK;
-}
-
-bool coords_below_q(const uint8_t* b, int ncoord, Fq* out) {
-    for (int i = 0; i < ncoord; i++) {
-        uint32_t s[8]; memcpy(s, b + 32 * i, 32);
-        if (!fp_std_lt_p<FqParams>(s)) return false;
-        out[i] = fp_from_std<FqParams>(s);
-    }
-    return true;
 }
 
 }  // namespace
@@ -198,43 +183,35 @@ bool coords_below_q(const uint8_t* b, int ncoord, Fq* out) {
 namespace zkc {
 
 int fixed_table_g1(zkc_ctx* ctx, const G1Affine& base, G1Affine** d_table, double* host_ms) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const clk::time_point t0 = clk::now();
     const FixedBase<Fq> fb(base);
     if (host_ms) *host_ms = ms_since(t0);
     *d_table = nullptr;
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)d_table, fb.tab.size() * sizeof(G1Affine)));
-    const hipError_t e = hipMemcpy(*d_table, fb.tab.data(), fb.tab.size() * sizeof(G1Affine), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(*d_table); *d_table = nullptr; return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_table_g1: ") + hipGetErrorString(e)); }
+    DevBuf tab; int rc;
+    if ((rc = tab.alloc(ctx, fb.tab.size() * sizeof(G1Affine)))) return rc;
+    const hipError_t e = hipMemcpy(tab.p, fb.tab.data(), fb.tab.size() * sizeof(G1Affine), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_table_g1: ") + hipGetErrorString(e));
+    *d_table = (G1Affine*)tab.release();
     return ZKC_OK;
 }
 
 int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, double* host_ms) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const clk::time_point t0 = clk::now();
     const FixedBase<Fq2> fb(base);
     if (host_ms) *host_ms = ms_since(t0);
     *d_table29 = nullptr;
-    G2Affine* d_tmp = nullptr;
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&d_tmp, fb.tab.size() * sizeof(G2Affine)));
-    hipError_t e = hipMalloc((void**)d_table29, fb.tab.size() * G2ROW * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(d_tmp, fb.tab.data(), fb.tab.size() * sizeof(G2Affine), hipMemcpyHostToDevice);
-    int rc = ZKC_OK;
-    if (e == hipSuccess) rc = msm_g2_table29(ctx, d_tmp, *d_table29, fb.tab.size());      // the row format of the G2 MSM, made by its kernel
-    if (e == hipSuccess && !rc) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_tmp);
-    if (e != hipSuccess || rc) {
-        if (*d_table29) (void)hipFree(*d_table29);
-        *d_table29 = nullptr;
-        return rc ? rc : zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_table_g2: ") + hipGetErrorString(e));
-    }
-    return ZKC_OK;
+    DevBuf tmp; int rc;
+    if ((rc = tmp.alloc(ctx, fb.tab.size() * sizeof(G2Affine)))) return rc;
+    const hipError_t e = hipMemcpy(tmp.p, fb.tab.data(), fb.tab.size() * sizeof(G2Affine), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_table_g2: ") + hipGetErrorString(e));
+    return msm_g2_rows29(ctx, tmp.as<G2Affine>(), fb.tab.size(), "fixed_table_g2", d_table29);      // the row format of the G2 MSM, made by its kernel
 }
 
 int fixed_affine_g1(zkc_ctx* ctx, const G1XYZZ* d_in, uint32_t n, void* d_out, bool out_mont) {
-    Fq* d_pre = nullptr;
-    hipError_t e = hipMalloc((void**)&d_pre, (size_t)n * sizeof(Fq));
-    if (e == hipSuccess) e = launch_affine<Fq>(ctx, d_in, d_pre, n, out_mont, d_out);
+    DevBuf pre; int rc;
+    if ((rc = pre.alloc(ctx, (size_t)n * sizeof(Fq)))) return rc;
+    hipError_t e = launch_affine<Fq>(ctx, d_in, pre.as<Fq>(), n, out_mont, d_out);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_pre) (void)hipFree(d_pre);
     if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_affine_g1: ") + hipGetErrorString(e));
     return ZKC_OK;
 }
@@ -259,41 +236,32 @@ extern "C" int zkc_g1_fixed_mul_dev(zkc_ctx* ctx, const uint8_t base_std[64], co
     if (!ctx || !base_std || !d_scalars || !d_out || n == 0) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_fixed_mul_dev: bad argument");
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    Fq c[2];
-    if (!coords_below_q(base_std, 2, c)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_fixed_mul_dev: base coordinate >= q");
-    const G1Affine p{c[0], c[1]};
+    G1Affine p;
+    if (!rd_g1_std(p, base_std)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_fixed_mul_dev: base coordinate >= q");
     if (p.is_inf()) {                                          // k * infinity
         ZKC_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, (size_t)n * 64, ctx->stream));
         ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         return ZKC_OK;
     }
-    if (!(fp_sqr(p.y) == fp_sqr(p.x) * p.x + fp_from_u32<FqParams>(3))) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_fixed_mul_dev: base not on the curve");
-    G1Affine* d_table = nullptr;
-    int rc = fixed_table_g1(ctx, p, &d_table, nullptr); if (rc) return rc;
-    rc = fixed_mul_g1(ctx, d_table, d_scalars, false, n, d_out, false);
-    (void)hipFree(d_table);
-    return rc;
+    if (!pairing::g1_on_curve(p)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_fixed_mul_dev: base not on the curve");
+    DevBuf table;
+    int rc = fixed_table_g1(ctx, p, (G1Affine**)&table.p, nullptr); if (rc) return rc;
+    return fixed_mul_g1(ctx, table.as<G1Affine>(), d_scalars, false, n, d_out, false);
 }
 
 extern "C" int zkc_g2_fixed_mul_dev(zkc_ctx* ctx, const uint8_t base_std[128], const void* d_scalars, uint32_t n, void* d_out) {
     if (!ctx || !base_std || !d_scalars || !d_out || n == 0) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g2_fixed_mul_dev: bad argument");
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    Fq c[4];
-    if (!coords_below_q(base_std, 4, c)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g2_fixed_mul_dev: base coordinate >= q");
-    const G2Affine p{{c[0], c[1]}, {c[2], c[3]}};
+    G2Affine p;
+    if (!rd_g2_std(p, base_std)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g2_fixed_mul_dev: base coordinate >= q");
     if (p.is_inf()) {
         ZKC_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, (size_t)n * 128, ctx->stream));
         ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         return ZKC_OK;
     }
-    // the twist y^2 = x^3 + 3 / (9 + u)
-    const Fq2 xi{fp_from_u32<FqParams>(9), Fq::one()}, three{fp_from_u32<FqParams>(3), Fq::zero()};
-    const Fq2 b2 = three * fp_inv_gcd(xi);
-    if (!(fp_sqr(p.y) == fp_sqr(p.x) * p.x + b2)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g2_fixed_mul_dev: base not on the twist");
-    uint32_t* d_table = nullptr;
-    int rc = fixed_table_g2(ctx, p, &d_table, nullptr); if (rc) return rc;
-    rc = fixed_mul_g2(ctx, d_table, d_scalars, false, n, d_out, false);
-    (void)hipFree(d_table);
-    return rc;
+    if (!pairing::g2_on_curve(p)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g2_fixed_mul_dev: base not on the twist");      // y^2 = x^3 + 3 / (9 + u)
+    DevBuf table;
+    int rc = fixed_table_g2(ctx, p, (uint32_t**)&table.p, nullptr); if (rc) return rc;
+    return fixed_mul_g2(ctx, table.as<uint32_t>(), d_scalars, false, n, d_out, false);
 }

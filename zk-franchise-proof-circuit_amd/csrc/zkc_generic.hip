@@ -6,20 +6,13 @@
 #include <string>
 #include <vector>
 #include <map>
+#include <memory>
 #include "zkc_prover.h"
+#include "zkc_host_util.h"
 
 using namespace zkc;
 
 namespace {
-Fr root_of_unity(int logn) {            // 5^((r-1)/2^28) squared down to order 2^logn
-    uint32_t e[8]; for (int i = 0; i < 8; i++) e[i] = FrParams::p[i]; e[0] -= 1;
-    for (int i = 0; i < 8; i++) e[i] = (e[i] >> 28) | (i < 7 ? e[i + 1] << 4 : 0);
-    Fr g = fp_from_u32<FrParams>(5), w = Fr::one();
-    for (int i = 255; i >= 0; i--) { w = w * w; if ((e[i >> 5] >> (i & 31)) & 1) w = w * g; }
-    for (int i = 28; i > logn; i--) w = w * w;
-    return w;
-}
-
 __global__ void __launch_bounds__(256) zkc_fill_fr(Fr* __restrict__ dst, Fr v, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = v;
@@ -81,20 +74,13 @@ extern "C" int zkc_ntt_dev(zkc_ctx* ctx, const void* d_src, void* d_dst, int log
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t n = 1u << logn;
     zkc_ctx::TwiddleSet& t = ctx->ntt_tw[logn];     // owned by the context (its lock is held): released with it, never inherited by another device's context
-    if (!t.fwd) {
-        const Fr w = root_of_unity(logn), wi = fp_inv<FrParams>(w);
-        std::vector<Fr> f(n / 2), b(n / 2);
-        f[0] = b[0] = Fr::one(); for (uint32_t i = 1; i < n / 2; i++) { f[i] = f[i - 1] * w; b[i] = b[i - 1] * wi; }
-        Fr* d_tmp = nullptr; int rc;
-        ZKC_HIP_CHECK(ctx, hipMalloc((void**)&d_tmp, (size_t)(n / 2) * sizeof(Fr)));
-        ZKC_HIP_CHECK(ctx, hipMalloc(&t.ninv, (size_t)n * sizeof(Fr)));
-        ZKC_HIP_CHECK(ctx, hipMemcpy(d_tmp, f.data(), f.size() * sizeof(Fr), hipMemcpyHostToDevice));
-        if ((rc = ntt_make_tw29(ctx, d_tmp, n / 2, &t.fwd))) return rc;
-        ZKC_HIP_CHECK(ctx, hipMemcpy(d_tmp, b.data(), b.size() * sizeof(Fr), hipMemcpyHostToDevice));
-        if ((rc = ntt_make_tw29(ctx, d_tmp, n / 2, &t.inv))) return rc;
-        ZKC_HIP_CHECK(ctx, hipFree(d_tmp));
-        hipLaunchKernelGGL(zkc_fill_fr, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (Fr*)t.ninv, fp_inv<FrParams>(fp_from_u32<FrParams>(n)), n);
+    if (!t.fwd) {              // the set is complete or absent: its three tables are handed over together, once all of them exist
+        DevBuf ninv, fwd, inv; TwiddleTables tw; int rc;
+        if ((rc = ninv.alloc(ctx, (size_t)n * sizeof(Fr))) || (rc = ntt_twiddle_tables(ctx, logn, false, &tw))) return rc;
+        fwd.p = tw.fwd29; inv.p = tw.inv29;
+        hipLaunchKernelGGL(zkc_fill_fr, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ninv.as<Fr>(), fp_inv<FrParams>(fp_from_u32<FrParams>(n)), n);
         ZKC_HIP_CHECK(ctx, hipGetLastError());
+        t.fwd = (uint32_t*)fwd.release(); t.inv = (uint32_t*)inv.release(); t.ninv = ninv.release();
     }
     zkc_prof_scope _pn(ctx, ZKC_PROF_NTT, (uint64_t)nvec * 2ull * n * 32, ctx->stream);
     return ntt_run(ctx, ctx->stream, (const Fr*)d_src, (Fr*)d_dst, inverse ? t.inv : t.fwd, inverse ? (const Fr*)t.ninv : nullptr, logn, nvec);
@@ -105,16 +91,14 @@ extern "C" int zkc_g1_mul_batch_dev(zkc_ctx* ctx, const uint8_t base_std[64], co
     if (!ctx || !base_std || !d_scalars || !d_out || n == 0) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_mul_batch_dev: bad argument");
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    uint32_t x[8], y[8]; memcpy(x, base_std, 32); memcpy(y, base_std + 32, 32);
-    if (!fp_std_lt_p<FqParams>(x) || !fp_std_lt_p<FqParams>(y)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_mul_batch_dev: base coordinate >= q");
-    G1Affine p; p.x = fp_from_std<FqParams>(x); p.y = fp_from_std<FqParams>(y);
-    G1XYZZ* d_tmp = nullptr;
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&d_tmp, (size_t)n * sizeof(G1XYZZ)));
-    hipLaunchKernelGGL(zkc_g1_mul_same_base, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, p, (const uint32_t*)d_scalars, n, d_tmp);
-    hipLaunchKernelGGL(zkc_g1_xyzz_to_std, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d_tmp, (uint32_t*)d_out, n);
+    G1Affine p;
+    if (!rd_g1_std(p, base_std)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_g1_mul_batch_dev: base coordinate >= q");
+    DevBuf tmp; int rc;
+    if ((rc = tmp.alloc(ctx, (size_t)n * sizeof(G1XYZZ)))) return rc;
+    hipLaunchKernelGGL(zkc_g1_mul_same_base, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, p, (const uint32_t*)d_scalars, n, tmp.as<G1XYZZ>());
+    hipLaunchKernelGGL(zkc_g1_xyzz_to_std, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, tmp.as<G1XYZZ>(), (uint32_t*)d_out, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_tmp);
     if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("zkc_g1_mul_batch_dev: ") + hipGetErrorString(e));
     return ZKC_OK;
 }
@@ -124,22 +108,21 @@ extern "C" int zkc_msm_g1_load_dev(zkc_ctx* ctx, const void* d_bases_std, uint32
     if (!ctx || !d_bases_std || !out || n == 0 || n > (1u << 21)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_msm_g1_load_dev: bad argument (1 <= n <= 2^21)");
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    zkc_msm* m = new zkc_msm(); m->zk.ctx = ctx; m->n = n; m->c = msm_c_for(n);
+    std::unique_ptr<zkc_msm, void (*)(zkc_msm*)> m(new zkc_msm(), zkc_msm_g1_free);      // a half-built set goes the way of a finished one
+    m->zk.ctx = ctx; m->n = n; m->c = msm_c_for(n);
     const int nw = msm_nw(m->c);
-    uint32_t* d_bad = nullptr; uint32_t bad = 0; int rc = ZKC_OK;
-    auto bail = [&](int code) { if (d_bad) (void)hipFree(d_bad); if (m->zk.d_g1) (void)hipFree(m->zk.d_g1); if (m->d_red) (void)hipFree(m->d_red); m->zk.d_g1 = nullptr; msm_work_free(m->w); delete m; return code; };
+    DevBuf d_bad; uint32_t bad = 0; int rc = ZKC_OK;
     if (hipMalloc((void**)&m->zk.d_g1, (size_t)nw * n * sizeof(G1Affine)) != hipSuccess || hipMalloc((void**)&m->d_red, (size_t)n * 32) != hipSuccess ||
-        hipMalloc((void**)&d_bad, 4) != hipSuccess || hipMemset(d_bad, 0, 4) != hipSuccess)
-        return bail(zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: hipMalloc failed"));
-    hipLaunchKernelGGL(zkc_g1_std_to_mont, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)d_bases_std, m->zk.d_g1, n, d_bad);
-    if (hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return bail(zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: base conversion failed"));
-    if (bad) return bail(zkc_fail(ctx, ZKC_ERR_FORMAT, bad & 1 ? "zkc_msm_g1_load_dev: base coordinate >= q" : "zkc_msm_g1_load_dev: base not on the curve"));
-    if ((rc = msm_precompute_g1(ctx, n, m->zk.d_g1, m->c))) return bail(rc);
-    if ((rc = msm_work_alloc(ctx, m->w, (size_t)nw * n, (size_t)msm_half(m->c), 1, false))) return bail(rc);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: table build failed"));
-    (void)hipFree(d_bad);
-    *out = m;
+        hipMalloc(&d_bad.p, 4) != hipSuccess || hipMemset(d_bad.p, 0, 4) != hipSuccess)
+        return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: hipMalloc failed");
+    hipLaunchKernelGGL(zkc_g1_std_to_mont, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)d_bases_std, m->zk.d_g1, n, d_bad.as<uint32_t>());
+    if (hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: base conversion failed");
+    if (bad) return zkc_fail(ctx, ZKC_ERR_FORMAT, bad & 1 ? "zkc_msm_g1_load_dev: base coordinate >= q" : "zkc_msm_g1_load_dev: base not on the curve");
+    if ((rc = msm_precompute_g1(ctx, n, m->zk.d_g1, m->c))) return rc;
+    if ((rc = msm_work_alloc(ctx, m->w, (size_t)nw * n, (size_t)msm_half(m->c), 1, false))) return rc;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, "zkc_msm_g1_load_dev: table build failed");
+    *out = m.release();
     return ZKC_OK;
 }
 // sum_i (s_i mod r) P_i over the resident bases; d_scalars: n x 32 B, any 256-bit integers (device); out: affine standard form (all zero = infinity)
@@ -154,7 +137,7 @@ extern "C" int zkc_msm_g1_dev(zkc_msm* m, const void* d_scalars, uint8_t out[64]
     int rc = msm_pass_g1(&m->zk, m->w, m->jl, 0, true, ctx->stream); if (rc) return rc;
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const G1Affine a = xyzz_to_affine(*(const G1XYZZ*)m->w.h_results);
-    uint32_t s[8]; fp_to_std<FqParams>(s, a.x); memcpy(out, s, 32); fp_to_std<FqParams>(s, a.y); memcpy(out + 32, s, 32);
+    wr_g1_std(out, a);
     return ZKC_OK;
 }
 extern "C" void zkc_msm_g1_free(zkc_msm* m) {

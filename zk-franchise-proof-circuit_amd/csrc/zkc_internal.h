@@ -85,6 +85,27 @@ int zkc_fail(zkc_ctx* ctx, int code, const std::string& msg);
 hipError_t zkc_wait_event(hipEvent_t ev, unsigned spin_us = 0);        // spin_us: keep polling back to back for that long before the naps start (a lone caller's 3 ms proof: the nap would add 2 % to its latency)
 hipError_t zkc_wait_stream(hipStream_t st, hipEvent_t scratch_ev);      // record scratch_ev on st, then zkc_wait_event (scratch_ev: any event of the caller's that is not otherwise in flight)
 int zkc_ensure(zkc_ctx* ctx, void** p, size_t* cur, size_t need);
+namespace zkc {
+// A device allocation owned by a scope and freed on every way out of it.  For the temporaries of load-time and tool code only: hipFree waits for the whole device, so
+// nothing on the proving, service or lane paths owns memory this way, and what lives as long as a key, a context, a lane or a tree stays a raw pointer with its free function.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(zkc_ctx* ctx, size_t bytes) { ZKC_HIP_CHECK(ctx, hipMalloc(&p, bytes ? bytes : 4)); return ZKC_OK; }
+    template <class T> T* as() const { return (T*)p; }
+    void* release() { void* q = p; p = nullptr; return q; }      // the buffer outlives the scope after all: it is the caller's now
+};
+}  // namespace zkc
+// ---- zkc_api.hip ----
+uint32_t* zkc_get_template(zkc_ctx* ctx, int nLevels);      // device template witness of ZkFranchiseProofCircuit(nLevels), made on first use (nullptr on error)
+int zkc_lane_streams(zkc_ctx* ctx, int l, bool with_red, zkc_ctx::LaneStreams* out);      // the stream set of lane l of ctx's device, made on first use
+// witnesses of B voters from their input blocks, enqueued on st (nullptr: ctx->stream) and not waited for
+int zkc_witness_chunk_async(zkc_ctx* ctx, int nLevels, const void* d_inputs, int B, void* d_wtns, int32_t* d_status3, int32_t* d_status, hipStream_t st);
+// ---- zkc_prove.hip ----
+void zkc_ctx_lanes_destroy(zkc_ctx* ctx);      // the context's lanes: work space and events
 inline int zkc_vws(zkc_ctx* ctx, int which, size_t need, void** out) { const int rc = zkc_ensure(ctx, &ctx->vws[which], &ctx->vws_sz[which], need); *out = ctx->vws[which]; return rc; }
 void zkc_verify_ws_trim(zkc_ctx* ctx, size_t keep_bytes);      // free the verifier's buffers when they hold more than keep_bytes (0: always)
 // RAII bracket: records two events around the launches made while it is alive when category `cat` is enabled

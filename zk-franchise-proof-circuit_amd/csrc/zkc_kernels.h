@@ -7,6 +7,7 @@
 #pragma once
 #include "zkc_field.h"
 #include "zkc_device.h"
+#include "zkc_jds.h"
 
 namespace zkc {
 
@@ -20,7 +21,6 @@ __device__ __forceinline__ void st_fr(Fr* p, const Fr& r) {
     uint4* d = reinterpret_cast<uint4*>(p);
     d[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]); d[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
 }
-constexpr uint32_t MV_UNIT = 0x80000000u, MV_NEG = 0x40000000u, MV_COL = 0x3fffffffu;
 __device__ __forceinline__ Fr mv_term(const Fr* __restrict__ val, const Fr* __restrict__ w, const Fr* __restrict__ wm, uint32_t idx, uint32_t c) {
     if (wm && (c & MV_UNIT)) { const Fr x = ld_fr(wm + (c & MV_COL)); return (c & MV_NEG) ? fp_neg(x) : x; }
     return ld_fr(val + idx) * ld_fr(w + (c & MV_COL));

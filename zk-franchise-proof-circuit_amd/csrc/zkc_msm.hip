@@ -517,6 +517,23 @@ static int precompute(zkc_ctx* ctx, uint32_t count, Affine<F>* d_table, int c) {
 }
 int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c) { return precompute<Fq>(ctx, count, d_table, c); }
 int msm_precompute_g2(zkc_ctx* ctx, uint32_t count, G2Affine* d_table, int c) { return precompute<Fq2>(ctx, count, d_table, c); }
+int msm_g2_rows29(zkc_ctx* ctx, const G2Affine* d_points, size_t n, const char* what, uint32_t** out) {
+    DevBuf rows; int rc;
+    if ((rc = rows.alloc(ctx, n * G2T29_WORDS * sizeof(uint32_t))) || (rc = msm_g2_table29(ctx, d_points, rows.as<uint32_t>(), n))) return rc;
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    *out = (uint32_t*)rows.release();
+    return ZKC_OK;
+}
+int msm_g2_window_table29(zkc_ctx* ctx, const G2Affine* d_bases, uint32_t count, int c, const char* what, uint32_t** out) {
+    const size_t n = (size_t)msm_nw(c) * count;
+    DevBuf shifted; int rc;
+    if ((rc = shifted.alloc(ctx, n * sizeof(G2Affine)))) return rc;
+    const hipError_t e = hipMemcpyAsync(shifted.p, d_bases, (size_t)count * sizeof(G2Affine), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    if ((rc = msm_precompute_g2(ctx, count, shifted.as<G2Affine>(), c))) return rc;
+    return msm_g2_rows29(ctx, shifted.as<G2Affine>(), n, what, out);
+}
 
 // ---- constant folding support: out[i] = scalar[wire_i] * P[wire_i - shift] by double-and-add, then per-group sums ----
 __device__ __forceinline__ uint32_t limb_of(const uint32_t k[8], int i) {
@@ -557,21 +574,15 @@ zkc_fold_gsum(const XYZZ<F>* __restrict__ in, const uint32_t* __restrict__ gstar
 template <class F>
 static int fold_group_sums(zkc_ctx* ctx, const Affine<F>* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
                            const uint32_t* d_gstart, uint32_t ngroups, XYZZ<F>* h_out) {
-    XYZZ<F>*d_tmp = nullptr, *d_out = nullptr;
-    const int rc = [&]() -> int {
-        ZKC_HIP_CHECK(ctx, hipMalloc(&d_tmp, (size_t)nw * sizeof(XYZZ<F>)));
-        ZKC_HIP_CHECK(ctx, hipMalloc(&d_out, (size_t)ngroups * sizeof(XYZZ<F>)));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<F>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, d_scalars, d_wires, nw, pt_shift, d_tmp);
-        ZKC_HIP_CHECK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<F>), dim3((ngroups + 63) / 64), dim3(64), 0, ctx->stream, d_tmp, d_gstart, ngroups, d_out);
-        ZKC_HIP_CHECK(ctx, hipGetLastError());
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_out, (size_t)ngroups * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, ctx->stream));
-        ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        return ZKC_OK;
-    }();
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevBuf tmp, out; int rc;
+    if ((rc = tmp.alloc(ctx, (size_t)nw * sizeof(XYZZ<F>))) || (rc = out.alloc(ctx, (size_t)ngroups * sizeof(XYZZ<F>)))) return rc;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<F>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, d_scalars, d_wires, nw, pt_shift, tmp.as<XYZZ<F>>());
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<F>), dim3((ngroups + 63) / 64), dim3(64), 0, ctx->stream, tmp.as<XYZZ<F>>(), d_gstart, ngroups, out.as<XYZZ<F>>());
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, out.p, (size_t)ngroups * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
 }
 int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G1XYZZ* o) {
     return fold_group_sums<Fq>(ctx, tbl, s, w, nw, sh, gs, ng, o);

@@ -11,6 +11,7 @@
 #include "zkc_internal.h"
 #include "zkc_prover.h"
 #include "zkc_f29.h"
+#include "zkc_host_util.h"
 #include "zkc_kernels.h"
 
 namespace zkc {
@@ -428,6 +429,23 @@ int ntt_make_tw29(zkc_ctx* ctx, const Fr* d_tw, uint32_t count, uint32_t** out) 
     hipLaunchKernelGGL(zkc_tw29, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, d_tw, *out, count);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
+}
+
+// The twiddles of a 2^logn transform: w^j and w^-j for j < n / 2, uploaded in Fr form and turned into the limb form.  Every table is built into a local owner and handed
+// over only when all of them exist: a failure leaves *out as it was and nothing allocated.
+int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out) {
+    const uint32_t half = 1u << (logn - 1);
+    const Fr w = fr_root_of_unity(logn), wi = fp_inv<FrParams>(w);
+    std::vector<Fr> f(half), b(half);
+    f[0] = b[0] = Fr::one(); for (uint32_t i = 1; i < half; i++) { f[i] = f[i - 1] * w; b[i] = b[i - 1] * wi; }
+    DevBuf d_f, d_b, d_f29, d_b29; int rc;
+    if ((rc = d_f.alloc(ctx, half * sizeof(Fr))) || (rc = d_b.alloc(ctx, half * sizeof(Fr)))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemcpy(d_f.p, f.data(), half * sizeof(Fr), hipMemcpyHostToDevice));
+    ZKC_HIP_CHECK(ctx, hipMemcpy(d_b.p, b.data(), half * sizeof(Fr), hipMemcpyHostToDevice));
+    if ((rc = ntt_make_tw29(ctx, d_f.as<Fr>(), half, (uint32_t**)&d_f29.p)) || (rc = ntt_make_tw29(ctx, d_b.as<Fr>(), half, (uint32_t**)&d_b29.p))) return rc;
+    out->fwd29 = (uint32_t*)d_f29.release(); out->inv29 = (uint32_t*)d_b29.release();
+    out->fwd = keep_fr ? (Fr*)d_f.release() : nullptr; out->inv = keep_fr ? (Fr*)d_b.release() : nullptr;
     return ZKC_OK;
 }
 

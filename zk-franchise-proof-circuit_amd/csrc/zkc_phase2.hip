@@ -17,7 +17,6 @@
 // the exceptional case, at its last digit, where the accumulator holds (r - 1) P = -P and -P is added: a doubling.  f29_madd's `false` return is handled for every digit
 // (same point: double the accumulator; opposite points: infinity), which covers it; tests/test_gpu_phase2_scale.py has k = r - 2.
 // A doubling never meets infinity: the group has odd order.  Inputs are checked for being on the curve, which on a curve of prime order is all there is to check.
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -104,12 +103,8 @@ zkc_p2_mont_to_std(uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict_
     q[2] = make_uint4(ys[0], ys[1], ys[2], ys[3]); q[3] = make_uint4(ys[4], ys[5], ys[6], ys[7]);
 }
 
-typedef std::chrono::steady_clock::time_point tick;
-tick now() { return std::chrono::steady_clock::now(); }
-double ms_between(tick a, tick b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 thread_local double g_p2_ms[9] = {0};
 
-struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
 // a secret scalar: cleared on every way out of its scope, through a volatile pointer so that the stores are not dropped as dead
 struct Secret {
     uint32_t v[8] = {0};
@@ -145,28 +140,23 @@ int scale_dev(zkc_ctx* ctx, const void* d_points, uint32_t n, const uint32_t k[8
     }
     const ScaleDigits dg = recode_naf(k);
     DevBuf sum, flag;
-    ZKC_HIP_CHECK(ctx, hipMalloc(&sum.p, (size_t)n * sizeof(G1XYZZ)));
-    ZKC_HIP_CHECK(ctx, hipMalloc(&flag.p, 4));
+    int rca;
+    if ((rca = sum.alloc(ctx, (size_t)n * sizeof(G1XYZZ))) || (rca = flag.alloc(ctx, 4))) return rca;
     ZKC_HIP_CHECK(ctx, hipMemsetAsync(flag.p, 0xff, 4, ctx->stream));
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     hipLaunchKernelGGL(zkc_p2_scale_g1, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, (const uint32_t*)d_points, n, dg, mont ? 1 : 0, (G1XYZZ*)sum.p, (uint32_t*)flag.p);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     uint32_t bad = 0;
     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const tick t1 = now();
+    const clk::time_point t1 = clk::now();
     if (bad != 0xffffffffu) return zkc_fail(ctx, ZKC_ERR_FORMAT, "zkc_g1_scale_dev: point " + std::to_string(bad) + " has a coordinate >= q or is not on the curve");
     const int rc = fixed_affine_g1(ctx, (const G1XYZZ*)sum.p, n, d_out, mont);
-    if (ms) { ms[0] = ms_between(t0, t1); ms[1] = ms_between(t1, now()); }
+    if (ms) { ms[0] = ms_since(t0, t1); ms[1] = ms_since(t1); }
     return rc;
 }
 
-// ---- points of a .zkey (Montgomery, little endian) on the host ----
-bool rd_fq_mont(Fq& o, const uint8_t* p) { memcpy(o.v, p, 32); return fp_std_lt_p<FqParams>(o.v); }
-bool rd_g1_mont(G1Affine& o, const uint8_t* p) { return rd_fq_mont(o.x, p) && rd_fq_mont(o.y, p + 32); }
-bool rd_g2_mont(G2Affine& o, const uint8_t* p) { return rd_fq_mont(o.x.c0, p) && rd_fq_mont(o.x.c1, p + 32) && rd_fq_mont(o.y.c0, p + 64) && rd_fq_mont(o.y.c1, p + 96); }
-void wr_g1_mont(uint8_t* p, const G1Affine& a) { memcpy(p, a.x.v, 32); memcpy(p + 32, a.y.v, 32); }
-void wr_g2_mont(uint8_t* p, const G2Affine& a) { memcpy(p, a.x.c0.v, 32); memcpy(p + 32, a.x.c1.v, 32); memcpy(p + 64, a.y.c0.v, 32); memcpy(p + 96, a.y.c1.v, 32); }
+// ---- points of a .zkey on the host: rd_*_mont / wr_*_mont (zkc_host_util.h) ----
 // a coordinate as a hash takes it: big-endian standard form
 void be_fq(uint8_t* o, const Fq& a) { uint32_t s[8]; fp_to_std<FqParams>(s, a); for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) o[4 * (7 - i) + (3 - b)] = (uint8_t)(s[i] >> (8 * b)); }
 // the "uncompressed" form of a point: x || y, G2 components c1 before c0; infinity = zeros with bit 0x40 of the first byte set
@@ -177,21 +167,6 @@ void unc_g2(uint8_t o[128], const G2Affine& a) {
 }
 template <class F> Affine<F> host_mul(const Affine<F>& p, const uint32_t k[8]) { return xyzz_to_affine(xyzz_mul(XYZZ<F>::from_affine(p), k)); }
 
-G1Affine g1_generator() { return {Fq::one(), fp_from_u32<FqParams>(2)}; }
-G2Affine g2_generator() {
-    static const uint32_t X0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
-    static const uint32_t X1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
-    static const uint32_t Y0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
-    static const uint32_t Y1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
-    return {{fp_from_std<FqParams>(X0), fp_from_std<FqParams>(X1)}, {fp_from_std<FqParams>(Y0), fp_from_std<FqParams>(Y1)}};
-}
-
-// a^e in Fq2, e = nwords little-endian words
-Fq2 fq2_pow_words(const Fq2& a, const uint32_t* e, int nwords) {
-    Fq2 r = Fq2::one();
-    for (int i = 32 * nwords - 1; i >= 0; i--) { r = fp_sqr(r); if ((e[i >> 5] >> (i & 31)) & 1) r = r * a; }
-    return r;
-}
 // a square root in Fq2 = Fq[u] / (u^2 + 1), q = 3 mod 4, by the complex method (Adj, Rodriguez-Henriquez, "Square root computation over even extension fields", alg. 9):
 // a1 = a^((q - 3) / 4), alpha = a1^2 a = a^((q - 1) / 2), x0 = a1 a; alpha = -1: the root is u x0; otherwise (1 + alpha)^((q - 1) / 2) x0.  The caller squares the result.
 Fq2 fq2_sqrt_candidate(const Fq2& a) {
@@ -199,10 +174,10 @@ Fq2 fq2_sqrt_candidate(const Fq2& a) {
     for (int i = 0; i < 8; i++) e34[i] = e12[i] = FqParams::p[i];
     e34[0] -= 3; e12[0] -= 1;                                  // q = ...47 hex: no borrow
     for (int i = 0; i < 8; i++) { e34[i] = (e34[i] >> 2) | (i < 7 ? e34[i + 1] << 30 : 0); e12[i] = (e12[i] >> 1) | (i < 7 ? e12[i + 1] << 31 : 0); }
-    const Fq2 a1 = fq2_pow_words(a, e34, 8), x0 = a1 * a, alpha = a1 * x0;
+    const Fq2 a1 = pairing::fq2_pow(a, e34, 256), x0 = a1 * a, alpha = a1 * x0;
     const Fq2 minus1 = fp_neg(Fq2::one());
     if (alpha == minus1) return Fq2{fp_neg(x0.c1), x0.c0};     // u x0
-    return fq2_pow_words(Fq2::one() + alpha, e12, 8) * x0;
+    return pairing::fq2_pow(Fq2::one() + alpha, e12, 256) * x0;
 }
 bool std_less(const uint32_t a[8], const uint32_t b[8]) { for (int i = 7; i >= 0; i--) if (a[i] != b[i]) return a[i] < b[i]; return false; }
 
@@ -261,8 +236,6 @@ bool hash_prefix(parse::Blake2b& h, const parse::P2Section& s, size_t k) {
     return true;
 }
 
-int err_out(char* err, size_t errlen, int code, const std::string& m) { if (err && errlen) snprintf(err, errlen, "%s", m.c_str()); return code; }
-
 // a whole image: sections, header checks (without the coefficient scan: the loader's), section 10
 struct Image { parse::BinSections bs; parse::ZkeyHeader zh; parse::P2Section p2; };
 bool read_image(const void* buf, size_t len, Image& im, std::string& why) {
@@ -301,7 +274,7 @@ extern "C" int zkc_zkey_contributions(const void* zkey, size_t len, uint8_t csHa
 
 extern "C" int zkc_zkey_contribute(zkc_ctx* ctx, const void* zkey, size_t len, const uint8_t delta[32], const char* name, void* out, size_t* out_len, uint8_t hash[64]) {
     if (!ctx || !zkey || !out_len) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_zkey_contribute: bad argument");
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     Image im; std::string why;
     if (!read_image(zkey, len, im, why)) return zkc_fail(ctx, ZKC_ERR_FORMAT, "zkc_zkey_contribute: " + why);
     const size_t name_len = name ? std::min<size_t>(strlen(name), 64) : 0;
@@ -324,7 +297,7 @@ extern "C" int zkc_zkey_contribute(zkc_ctx* ctx, const void* zkey, size_t len, c
     { parse::Blake2b h; if (!hash_prefix(h, im.p2, im.p2.rec.size())) return zkc_fail(ctx, ZKC_ERR_FORMAT, "zkc_zkey_contribute: a recorded point has a coordinate >= q");
       unc_g1(u, g1_s); h.update(u, 64); unc_g1(u, g1_sx); h.update(u, 64); h.final(transcript); }
     const G2Affine g2_spx = host_mul(phase2_challenge_g2(transcript), d);
-    const tick t1 = now();
+    const clk::time_point t1 = clk::now();
     // ---- sections 8 and 9 times 1 / delta on the GPU, as one batch ----
     const size_t n8 = (size_t)(im.bs.ssz[8] / 64), n9 = (size_t)(im.bs.ssz[9] / 64), npts = n8 + n9;
     if (npts > 0xffffffffull) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_zkey_contribute: key too large");
@@ -333,21 +306,21 @@ extern "C" int zkc_zkey_contribute(zkc_ctx* ctx, const void* zkey, size_t len, c
     memcpy(o, in, cut); memcpy(o + cut + rec_len, in + cut, len - cut);
     // whatever follows section 10 in the file moved by rec_len
     auto at = [&](const uint8_t* p) { const size_t off = (size_t)(p - in); return o + (off >= cut ? off + rec_len : off); };
-    double kms[2] = {0, 0}; tick t2 = t1, t3 = t1;
+    double kms[2] = {0, 0}; clk::time_point t2 = t1, t3 = t1;
     {
         ZKC_LOCK(ctx);
         ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        DevBuf pts;
-        ZKC_HIP_CHECK(ctx, hipMalloc(&pts.p, npts * 64));
+        DevBuf pts; int rca;
+        if ((rca = pts.alloc(ctx, npts * 64))) return rca;
         ZKC_HIP_CHECK(ctx, hipMemcpy(pts.p, im.bs.sec[8], n8 * 64, hipMemcpyHostToDevice));
         ZKC_HIP_CHECK(ctx, hipMemcpy((uint8_t*)pts.p + n8 * 64, im.bs.sec[9], n9 * 64, hipMemcpyHostToDevice));
-        t2 = now();
+        t2 = clk::now();
         const int rc = scale_dev(ctx, pts.p, (uint32_t)npts, dinv, true, pts.p, kms); if (rc) return rc;
-        t3 = now();
+        t3 = clk::now();
         ZKC_HIP_CHECK(ctx, hipMemcpy(at(im.bs.sec[8]), pts.p, n8 * 64, hipMemcpyDeviceToHost));
         ZKC_HIP_CHECK(ctx, hipMemcpy(at(im.bs.sec[9]), (uint8_t*)pts.p + n8 * 64, n9 * 64, hipMemcpyDeviceToHost));
     }
-    const tick t4 = now();
+    const clk::time_point t4 = clk::now();
     // ---- header, record, hash ----
     wr_g1_mont(at(hdr + OFF_DELTA1), delta1n); wr_g2_mont(at(hdr + OFF_DELTA2), delta2n);
     uint8_t* sec10 = at(im.bs.sec[10]);
@@ -364,8 +337,8 @@ extern "C" int zkc_zkey_contribute(zkc_ctx* ctx, const void* zkey, size_t len, c
         h.update(pk, 384);
         uint8_t hh[64]; h.final(hh); if (hash) memcpy(hash, hh, 64);
     }
-    const tick t5 = now();
-    g_p2_ms[0] = ms_between(t0, t1); g_p2_ms[1] = ms_between(t1, t2); g_p2_ms[2] = kms[0]; g_p2_ms[3] = kms[1]; g_p2_ms[4] = ms_between(t3, t4); g_p2_ms[5] = ms_between(t4, t5);
+    const clk::time_point t5 = clk::now();
+    g_p2_ms[0] = ms_since(t0, t1); g_p2_ms[1] = ms_since(t1, t2); g_p2_ms[2] = kms[0]; g_p2_ms[3] = kms[1]; g_p2_ms[4] = ms_since(t3, t4); g_p2_ms[5] = ms_since(t4, t5);
     return ZKC_OK;
 }
 
@@ -378,7 +351,7 @@ int section_msm(zkc_ctx* ctx, const uint8_t* sec, uint32_t n, const uint8_t* wei
     if (n == 0) return 0;
     ZKC_LOCK(ctx);
     if (hipSetDevice(ctx->device) != hipSuccess) return -ZKC_ERR_HIP;
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     DevBuf pts, w, flag; uint32_t bad = 0;
     if (hipMalloc(&pts.p, (size_t)n * 64) != hipSuccess || hipMalloc(&w.p, (size_t)n * 32) != hipSuccess || hipMalloc(&flag.p, 4) != hipSuccess ||
         hipMemcpy(pts.p, sec, (size_t)n * 64, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(w.p, weights, (size_t)n * 32, hipMemcpyHostToDevice) != hipSuccess ||
@@ -391,10 +364,10 @@ int section_msm(zkc_ctx* ctx, const uint8_t* sec, uint32_t n, const uint8_t* wei
     int rc = zkc_msm_g1_load_dev(ctx, pts.p, n, &m);
     if (rc == ZKC_ERR_FORMAT) { why = "a point off the curve"; return 1; }
     if (rc) return -rc;
-    const tick t1 = now();
+    const clk::time_point t1 = clk::now();
     rc = zkc_msm_g1_dev(m, w.p, out);
     zkc_msm_g1_free(m);
-    ms[0] += ms_between(t0, t1); ms[1] += ms_between(t1, now());
+    ms[0] += ms_since(t0, t1); ms[1] += ms_since(t1);
     return rc ? -rc : 0;
 }
 
@@ -423,7 +396,7 @@ extern "C" int zkc_zkey_verify_contributions(zkc_ctx* ctx, const void* init, siz
     }
     if (n_new) *n_new = B.p2.n - A.p2.n;
     // ---- (c) ----
-    const tick tp0 = now();
+    const clk::time_point tp0 = clk::now();
     G1Affine delta; G2Affine delta2A, delta2B; G1Affine delta1B;
     if (!rd_g1_mont(delta, A.bs.sec[2] + OFF_DELTA1) || !rd_g2_mont(delta2A, A.bs.sec[2] + OFF_DELTA2) || !pairing::g1_on_curve(delta) || delta.is_inf() ||
         !pairing::g2_in_subgroup(delta2A) || delta2A.is_inf()) return invalid("check (c): the initial key's delta1 / delta2 is no point of its group");
@@ -448,7 +421,7 @@ extern "C" int zkc_zkey_verify_contributions(zkc_ctx* ctx, const void* init, siz
     if (!(delta.x == delta1B.x && delta.y == delta1B.y)) return invalid("check (d): the final key's delta1 is not the last contribution's deltaAfter");
     if (delta2B.is_inf() || !pairing::g2_in_subgroup(delta2B)) return invalid("check (d): the final key's delta2 is not in G2");
     if (!same_ratio(g1_generator(), delta1B, g2_generator(), delta2B)) return invalid("check (d): sameRatio(G1, delta1; G2, delta2) fails");
-    double pair_ms = ms_between(tp0, now());
+    double pair_ms = ms_since(tp0);
     // ---- (e), which is (f) too: with nothing new the sums and the deltas are equal ----
     const uint32_t n8 = (uint32_t)(A.bs.ssz[8] / 64), n9 = (uint32_t)(A.bs.ssz[9] / 64);
     std::vector<uint8_t> w((size_t)(n8 + n9) * 32);
@@ -464,10 +437,10 @@ extern "C" int zkc_zkey_verify_contributions(zkc_ctx* ctx, const void* init, siz
             if (rc < 0) return err_out(err, errlen, rc, std::string("zkc_zkey_verify_contributions: ") + zkc_last_error(ctx));
             if (rc) return invalid(std::string("check (e), section ") + std::to_string(p.sec) + " (" + p.name + ") of the " + sd.which + " key: " + why);
         }
-        const tick tq = now();
+        const clk::time_point tq = clk::now();
         if (!rd_g1_std(SA, sa) || !rd_g1_std(SB, sb)) return err_out(err, errlen, -ZKC_ERR_GENERIC, "zkc_zkey_verify_contributions: MSM result out of range");
         const bool ok = same_ratio(SA, SB, delta2B, delta2A);                       // e(SA, delta2A) == e(SB, delta2B)
-        pair_ms += ms_between(tq, now());
+        pair_ms += ms_since(tq);
         if (!ok) return invalid(std::string("check (e): the ") + p.name + " points (section " + std::to_string(p.sec) + ") are not the initial key's times one scalar 1 / delta");
     }
     g_p2_ms[6] = ms[0]; g_p2_ms[7] = ms[1]; g_p2_ms[8] = pair_ms;
@@ -487,7 +460,7 @@ extern "C" int zkc_debug_phase2_host_scale(const void* points, uint32_t n, const
     uint32_t ks[8]; memcpy(ks, k, 32);
     if (!fp_std_lt_p<FrParams>(ks)) return ZKC_ERR_BAD_ARG;
     const uint8_t* in = (const uint8_t*)points; uint8_t* o = (uint8_t*)out;
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     std::vector<std::thread> pool;
     for (int t = 0; t < threads; t++)
         pool.emplace_back([=] {
@@ -498,14 +471,13 @@ extern "C" int zkc_debug_phase2_host_scale(const void* points, uint32_t n, const
             }
         });
     for (auto& th : pool) th.join();
-    if (ms) *ms = ms_between(t0, now());
+    if (ms) *ms = ms_since(t0);
     return ZKC_OK;
 }
 
 extern "C" int zkc_debug_phase2_challenge_g2(const uint8_t transcript[64], uint8_t out[128]) {
     if (!transcript || !out) return ZKC_ERR_BAD_ARG;
     const G2Affine p = phase2_challenge_g2(transcript);
-    const Fq* c[4] = {&p.x.c0, &p.x.c1, &p.y.c0, &p.y.c1};
-    for (int i = 0; i < 4; i++) { uint32_t t[8]; fp_to_std<FqParams>(t, *c[i]); memcpy(out + 32 * i, t, 32); }
+    wr_g2_std(out, p);
     return ZKC_OK;
 }

@@ -9,6 +9,7 @@
 #include "zkc_prover.h"
 #include "zkc_fixedbase.h"
 #include "zkc_hostparse.h"
+#include "zkc_host_util.h"
 #include "zkc_kernels.h"
 #include <cstring>
 #include <ctime>
@@ -33,26 +34,12 @@ static constexpr uint32_t MATVEC_LONG = 16;      // rows with more coefficients 
 namespace {
 uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
 uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
-G1Affine rd_g1(const uint8_t* p) { G1Affine a; memcpy(a.x.v, p, 32); memcpy(a.y.v, p + 32, 32); return a; }
-G2Affine rd_g2(const uint8_t* p) { G2Affine a; memcpy(a.x.c0.v, p, 32); memcpy(a.x.c1.v, p + 32, 32); memcpy(a.y.c0.v, p + 64, 32); memcpy(a.y.c1.v, p + 96, 32); return a; }
-Fr fr_root_of_unity(int logn) {
-    uint32_t e[8]; for (int i = 0; i < 8; i++) e[i] = FrParams::p[i]; e[0] -= 1;
-    for (int i = 0; i < 8; i++) e[i] = (e[i] >> 28) | (i < 7 ? e[i + 1] << 4 : 0);
-    Fr g = fp_from_u32<FrParams>(5), w = Fr::one();
-    for (int i = 255; i >= 0; i--) { w = w * w; if ((e[i >> 5] >> (i & 31)) & 1) w = w * g; }
-    for (int i = 28; i > logn; i--) w = w * w;
-    return w;
-}
+// the points of a key's header and section 3 as stored: zkey_check has never looked at their coordinates and neither does the load (no key is refused for them)
+G1Affine rd_g1(const uint8_t* p) { G1Affine a; (void)rd_g1_mont(a, p); return a; }
+G2Affine rd_g2(const uint8_t* p) { G2Affine a; (void)rd_g2_mont(a, p); return a; }
 template <class T> int dmalloc(zkc_ctx* ctx, T** p, size_t count) { ZKC_HIP_CHECK(ctx, hipMalloc((void**)p, count * sizeof(T))); return ZKC_OK; }
-void g1_to_std(uint8_t* out, const G1Affine& a) { uint32_t s[8]; fp_to_std<FqParams>(s, a.x); memcpy(out, s, 32); fp_to_std<FqParams>(s, a.y); memcpy(out + 32, s, 32); }
-void g2_to_std(uint8_t* out, const G2Affine& a) {
-    uint32_t s[8]; fp_to_std<FqParams>(s, a.x.c0); memcpy(out, s, 32); fp_to_std<FqParams>(s, a.x.c1); memcpy(out + 32, s, 32);
-    fp_to_std<FqParams>(s, a.y.c0); memcpy(out + 64, s, 32); fp_to_std<FqParams>(s, a.y.c1); memcpy(out + 96, s, 32);
-}
 }  // namespace
 
-uint32_t* zkc_get_template(zkc_ctx* ctx, int nLevels);     // zkc_api.hip: device template witness (nullptr on error)
-int zkc_lane_streams(zkc_ctx* ctx, int l, bool with_red, zkc_ctx::LaneStreams* out);      // zkc_api.hip
 
 // ---- fold check: for every proof and every foldable group, does the witness equal the template there? ----
 // group g of a tree block = level g's non-control wires (g < n-1) ; group n-1 = the n2bOld block
@@ -247,29 +234,19 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
             uint32_t k = fill[(size_t)m * n + cc]++;
             col[k] = s; memcpy(val[k].v, c + 44ull * i + 12, 32);
         }
-        // jagged-diagonal order: rows by decreasing length; slot jdptr[k] + r holds the k-th coefficient of the r-th longest row
+        // jagged-diagonal order (zkc_jds.h): rows by decreasing length; slot jdptr[k] + r holds the k-th coefficient of the r-th longest row
         const size_t nrows = 2 * (size_t)n;
-        std::vector<uint32_t> perm(nrows), rowlen(nrows);
-        for (size_t r = 0; r < nrows; r++) perm[r] = (uint32_t)r;
-        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return rowptr[a + 1] - rowptr[a] > rowptr[b + 1] - rowptr[b]; });
-        for (size_t r = 0; r < nrows; r++) rowlen[r] = rowptr[perm[r] + 1] - rowptr[perm[r]];
-        const uint32_t maxlen = nrows ? rowlen[0] : 0;
-        zk->nlong = 0; while (zk->nlong < nrows && rowlen[zk->nlong] > MATVEC_LONG) zk->nlong++;
-        std::vector<uint32_t> jdptr(maxlen + 1, 0);
-        { size_t live = nrows; for (uint32_t k = 0; k < maxlen; k++) { while (live > 0 && rowlen[live - 1] <= k) live--; jdptr[k + 1] = jdptr[k] + (uint32_t)live; } }
+        const JdsLayout J = jds_layout(nrows, [&](uint32_t r) { return rowptr[r + 1] - rowptr[r]; }, MATVEC_LONG);
+        const std::vector<uint32_t>&perm = J.perm, &rowlen = J.rowlen, &jdptr = J.jdptr;
+        zk->nlong = J.nlong;
         std::vector<uint32_t> jcol(zk->nCoeffs); std::vector<Fr> jval(zk->nCoeffs);
         // [r4] +1 and -1 (stored, like every coefficient, times R^2) are marked in the top bits of the column word: zkc_matvec_jds adds or subtracts the wire's Montgomery form
         // for them instead of multiplying (276 k of the census circuit's 463 k coefficients)
         if (nv >= (1u << 30)) return bail(zkc_fail(ctx, ZKC_ERR_FORMAT, "zkey too large for 30-bit wire indices"));
         Fr one_r2, neg_r2; for (int i = 0; i < 8; i++) one_r2.v[i] = FrParams::r2[i];
         neg_r2 = Fr::zero() - one_r2;
-        zk->n_unit_coeffs = 0;
-        for (size_t r = 0; r < nrows; r++) for (uint32_t k = 0; k < rowlen[r]; k++) {
-            const size_t dst = (size_t)jdptr[k] + r, src = (size_t)rowptr[perm[r]] + k;
-            uint32_t c = col[src];
-            if (val[src] == one_r2) { c |= 0x80000000u; zk->n_unit_coeffs++; } else if (val[src] == neg_r2) { c |= 0xc0000000u; zk->n_unit_coeffs++; }
-            jcol[dst] = c; jval[dst] = val[src];
-        }
+        zk->n_unit_coeffs = (uint32_t)jds_fill(J, [&](uint32_t r, uint32_t k) { const size_t src = (size_t)rowptr[r] + k; return std::pair<uint32_t, Fr>(col[src], val[src]); },
+                                               one_r2, neg_r2, jcol.data(), jval.data());
         if ((rc = dmalloc(ctx, &zk->d_perm, nrows)) || (rc = dmalloc(ctx, &zk->d_rowlen, nrows)) || (rc = dmalloc(ctx, &zk->d_jdptr, jdptr.size())) ||
             (rc = dmalloc(ctx, &zk->d_col, jcol.size() + 1)) || (rc = dmalloc(ctx, &zk->d_val, jval.size() + 1))) return bail(rc);
         ZKC_UP(zk->d_perm, perm.data(), nrows * 4); ZKC_UP(zk->d_rowlen, rowlen.data(), nrows * 4); ZKC_UP(zk->d_jdptr, jdptr.data(), jdptr.size() * 4);
@@ -278,16 +255,14 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     }
     // ---- twiddles and the coset/1-over-n scale ----
     {
-        const Fr w = fr_root_of_unity((int)zk->logn), g = fr_root_of_unity((int)zk->logn + 1);
-        const Fr wi = fp_inv<FrParams>(w), ninv = fp_inv<FrParams>(fp_from_u32<FrParams>(n));
-        std::vector<Fr> f(n / 2), b(n / 2), cs(n);
-        f[0] = b[0] = Fr::one(); for (uint32_t i = 1; i < n / 2; i++) { f[i] = f[i - 1] * w; b[i] = b[i - 1] * wi; }
+        TwiddleTables tw;
+        if ((rc = ntt_twiddle_tables(ctx, (int)zk->logn, true, &tw))) return bail(rc);
+        zk->d_tw_fwd = tw.fwd; zk->d_tw_inv = tw.inv; zk->d_tw_fwd29 = tw.fwd29; zk->d_tw_inv29 = tw.inv29;
+        const Fr g = fr_root_of_unity((int)zk->logn + 1), ninv = fp_inv<FrParams>(fp_from_u32<FrParams>(n));
+        std::vector<Fr> cs(n);
         cs[0] = ninv; for (uint32_t i = 1; i < n; i++) cs[i] = cs[i - 1] * g;
-        if ((rc = dmalloc(ctx, &zk->d_tw_fwd, n / 2)) || (rc = dmalloc(ctx, &zk->d_tw_inv, n / 2)) || (rc = dmalloc(ctx, &zk->d_coset, n))) return bail(rc);
-        ZKC_UP(zk->d_tw_fwd, f.data(), f.size() * sizeof(Fr));
-        ZKC_UP(zk->d_tw_inv, b.data(), b.size() * sizeof(Fr));
+        if ((rc = dmalloc(ctx, &zk->d_coset, n))) return bail(rc);
         ZKC_UP(zk->d_coset, cs.data(), cs.size() * sizeof(Fr));
-        if ((rc = ntt_make_tw29(ctx, zk->d_tw_fwd, n / 2, &zk->d_tw_fwd29)) || (rc = ntt_make_tw29(ctx, zk->d_tw_inv, n / 2, &zk->d_tw_inv29))) return bail(rc);
         if ((rc = ntt_bitrev_table(ctx, zk->d_coset, &zk->d_coset_br, (int)zk->logn))) return bail(rc);
     }
     // ---- bases: one G1 array [A | B1 | C | H] and one G2 array [B2]; window 0 = the zkey points as stored (affine,
@@ -322,30 +297,11 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
         ZKC_UP(zk->d_g1 + zk->offA_deep, sec[5], 64ull * nv); ZKC_UP(zk->d_g1 + zk->offB1_deep, sec[6], 64ull * nv); ZKC_UP(zk->d_g1 + zk->offC_deep, sec[8], 64ull * nc);
         if ((rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offA_deep, zk->c_deep)) || (rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offB1_deep, zk->c_deep)) ||
             (rc = msm_precompute_g1(ctx, nc, zk->d_g1 + zk->offC_deep, zk->c_deep))) return bail(rc);
-        G2Affine* tmp = nullptr;
-        if ((rc = dmalloc(ctx, &tmp, (size_t)NWD * nv))) return bail(rc);
-        hipError_t e2 = hipMemcpyAsync(tmp, zk->d_g2, 128ull * nv, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e2 == hipSuccess) rc = msm_precompute_g2(ctx, nv, tmp, zk->c_deep);
-        if (e2 == hipSuccess && !rc) rc = dmalloc(ctx, &zk->d_g2_29_deep, 60 * (size_t)NWD * nv);
-        if (e2 == hipSuccess && !rc) rc = msm_g2_table29(ctx, tmp, zk->d_g2_29_deep, (size_t)NWD * nv);
-        if (e2 == hipSuccess && !rc) e2 = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-        if (rc) return bail(rc);
-        if (e2 != hipSuccess) return bail(zkc_fail(ctx, ZKC_ERR_HIP, std::string("second section tables: ") + hipGetErrorString(e2)));
+        if ((rc = msm_g2_window_table29(ctx, zk->d_g2, nv, zk->c_deep, "second section tables", &zk->d_g2_29_deep))) return bail(rc);
     }
     {   // [r3] the 8-bit-window G2 table of the lone-proof path (MSM_C_G2_LONE): shifted in a temporary affine table, kept in radix 2^29 only
         if (sw::on<sw::ZKC_G2_LONE_TABLE>() && (zk->nLevels >= 0 || nv < (1u << 16))) {      // (a key of 2^16 wires and more that is not the census circuit: 32 x 240 B per wire for a latency path its proofs are too large to notice)
-            constexpr int NWL = msm_nw(MSM_C_G2_LONE);
-            G2Affine* tmp = nullptr;
-            if ((rc = dmalloc(ctx, &tmp, (size_t)NWL * nv))) return bail(rc);
-            hipError_t e2 = hipMemcpyAsync(tmp, zk->d_g2, 128ull * nv, hipMemcpyDeviceToDevice, ctx->stream);
-            if (e2 == hipSuccess) rc = msm_precompute_g2(ctx, nv, tmp, MSM_C_G2_LONE);
-            if (e2 == hipSuccess && !rc) rc = dmalloc(ctx, &zk->d_g2_29_lone, 60 * (size_t)NWL * nv);
-            if (e2 == hipSuccess && !rc) rc = msm_g2_table29(ctx, tmp, zk->d_g2_29_lone, (size_t)NWL * nv);
-            if (e2 == hipSuccess && !rc) e2 = hipStreamSynchronize(ctx->stream);
-            (void)hipFree(tmp);
-            if (rc) return bail(rc);
-            if (e2 != hipSuccess) return bail(zkc_fail(ctx, ZKC_ERR_HIP, std::string("lone-proof G2 table: ") + hipGetErrorString(e2)));
+            if ((rc = msm_g2_window_table29(ctx, zk->d_g2, nv, MSM_C_G2_LONE, "lone-proof G2 table", &zk->d_g2_29_lone))) return bail(rc);
         }
     }
     // ---- work buffers: up to `max_inflight` proofs share one MSM pipeline pass; the buffers themselves are sized by lanes_ensure() for
@@ -589,14 +545,13 @@ extern "C" int zkc_msm_debug(zkc_zkey* zk, int which, const void* d_scalars, uin
     jl.add((const uint32_t*)d_scalars, nullptr, count, offs[which], full, 0, which == 4 ? zk->c_h : zk->c_sec);
     int rc = which == 2 ? msm_pass_g2(zk, L0.w2, jl, 0, true, st_l0) : msm_pass_g1(zk, L0.w1, jl, 0, true, st_l0); if (rc) return rc;
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st_l0));
-    if (which == 2) g2_to_std((uint8_t*)host_out, xyzz_to_affine(*(G2XYZZ*)L0.w2.h_results));
-    else g1_to_std((uint8_t*)host_out, xyzz_to_affine(*(G1XYZZ*)L0.w1.h_results));
+    if (which == 2) wr_g2_std((uint8_t*)host_out, xyzz_to_affine(*(G2XYZZ*)L0.w2.h_results));
+    else wr_g1_std((uint8_t*)host_out, xyzz_to_affine(*(G1XYZZ*)L0.w1.h_results));
     return ZKC_OK;
 }
 
 // d_inputs != nullptr: the witnesses are computed here as well, a chunk per pass on ctx->stream, so that the (latency-bound, few-wave)
 // witness kernels of pass p+1 run underneath the MSMs of pass p
-int zkc_witness_chunk_async(zkc_ctx* ctx, int nLevels, const void* d_inputs, int B, void* d_wtns, int32_t* d_status3, int32_t* d_status, hipStream_t st);
 int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nWitness, int B, const uint8_t* rs, bool want_publics, const void* d_inputs, int32_t* d_status,
                            int lane0, hipEvent_t wait_first, const uint8_t* host_depths, bool no_early) {
     if (!zk || !d_wtns || !rs || B <= 0 || cs < 0 || cs >= CALL_SLOTS || lane0 >= zk->nlanes) return zkc_fail(zk ? zk->ctx : nullptr, ZKC_ERR_BAD_ARG, "zkc_prove_batch_dev: bad argument");
@@ -928,7 +883,7 @@ int zkc::prove_batch_finish(zkc_zkey* zk, int cs, uint8_t* proofs, uint8_t* publ
     for (int q = 0; q < CS.B; q++) if (CS.as_xyzz[q]) {
         const uint8_t* x = CS.h_xyzz + 512 * (size_t)q; uint8_t* o = proofs + 256 * (size_t)q;
         G1XYZZ a, c; G2XYZZ b; memcpy(&a, x, 128); memcpy(&b, x + 128, 256); memcpy(&c, x + 384, 128);
-        g1_to_std(o, xyzz_to_affine_gcd(a)); g2_to_std(o + 64, xyzz_to_affine_gcd(b)); g1_to_std(o + 192, xyzz_to_affine_gcd(c));
+        wr_g1_std(o, xyzz_to_affine_gcd(a)); wr_g2_std(o + 64, xyzz_to_affine_gcd(b)); wr_g1_std(o + 192, xyzz_to_affine_gcd(c));
     }
     if (publics) memcpy(publics, CS.h_out + 256ull * CS.cap, 32ull * zk->nPub * CS.B);
     return ZKC_OK;

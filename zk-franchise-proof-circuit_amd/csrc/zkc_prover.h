@@ -250,6 +250,14 @@ struct zkc_zkey {
 namespace zkc {
 int ntt_run(zkc_ctx* ctx, hipStream_t st, const Fr* src, Fr* dst, const uint32_t* tw29, const Fr* scale, int logn, int nvec);
 int ntt_make_tw29(zkc_ctx* ctx, const Fr* d_tw, uint32_t count, uint32_t** out);
+// w^j, w^-j (j < 2^(logn - 1)) on the device, in Fr form (keep_fr; else nullptr) and in radix 2^29.  All four or, on failure, none: *out is written on success only
+struct TwiddleTables { Fr *fwd = nullptr, *inv = nullptr; uint32_t *fwd29 = nullptr, *inv29 = nullptr; };
+int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out);
+// the window-c table of `count` G2 bases (device, window 0 = the bases as a .zkey stores them) in the accumulation's row form, 60 words per point: a copy of the bases is
+// shifted to msm_nw(c) windows, converted and dropped.  *out is written on success only; ends with ctx->stream synchronised
+int msm_g2_window_table29(zkc_ctx* ctx, const G2Affine* d_bases, uint32_t count, int c, const char* what, uint32_t** out);
+// n affine G2 points (device) -> a fresh table of their rows; the stream is synchronised, so the caller may drop the points
+int msm_g2_rows29(zkc_ctx* ctx, const G2Affine* d_points, size_t n, const char* what, uint32_t** out);
 // [r2] the prover's pair iNTT -> x scale -> NTT in three HBM round trips without bit reversal (zkc_ntt.hip); scale_br = scale table in bit-reversed order
 int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv29, const uint32_t* tw_fwd29, const Fr* scale_br, int logn, int nvec);
 int ntt_bitrev_table(zkc_ctx* ctx, const Fr* d_src, Fr** out, int logn);      // twiddles in the 12-word radix-2^29 form ntt_run reads

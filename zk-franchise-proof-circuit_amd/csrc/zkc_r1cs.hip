@@ -10,7 +10,7 @@
 // first (stable), and stored in the jagged-diagonal order of zkc_zkey_load: slot jdptr[j] + s holds the j-th term of the s-th longest row, so the loads of a wave's lanes
 // are contiguous and neighbouring lanes have (nearly) equal work.  rows[s] = (end of A, end of B, end of C, index in the file) for the s-th longest: the verdict is a
 // FILE index, the sort is only the device's.  Coefficients are stored as zkc_zkey_load stores the key's: val R^2, so that one Montgomery product with the standard-form
-// wire is the term in Montgomery form, with +1 / -1 marked in the two top bits of the wire word (MV_UNIT / MV_NEG, zkc_kernels.h) and served by the wire's Montgomery form
+// wire is the term in Montgomery form, with +1 / -1 marked in the two top bits of the wire word (MV_UNIT / MV_NEG, zkc_jds.h) and served by the wire's Montgomery form
 // from zkc_wtns_mont.  The three sums are then Montgomery forms, and so are their product and the comparison.
 //
 // Long rows.  The first `nlong` rows (more than R1CS_LONG terms) get a wave each: lane l takes terms l, l + 64, ... and the three sums are reduced by shuffles.  The
@@ -201,38 +201,25 @@ extern "C" int zkc_r1cs_load(zkc_ctx* ctx, const void* r1cs, size_t len, zkc_r1c
     const uint64_t nTerms = P.terms[0].size() + P.terms[1].size() + P.terms[2].size();
     if (P.h.nWires >= (1u << 30) || nCons >= (1u << 31)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_r1cs_load: more than 2^30 - 1 wires or 2^31 - 1 constraints");
     if (nTerms >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_r1cs_load: more than 2^32 - 1 coefficients");
-    // merged rows, longest first; jagged-diagonal slots
-    auto len_of = [&](uint32_t k) { uint64_t l = 0; for (int m = 0; m < 3; m++) l += P.ptr[m][(size_t)k + 1] - P.ptr[m][k]; return l; };
-    std::vector<uint32_t> perm(nCons); for (uint32_t k = 0; k < nCons; k++) perm[k] = k;
-    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return len_of(x) > len_of(y); });
+    // merged rows, longest first; jagged-diagonal slots (zkc_jds.h)
+    auto len_of = [&](uint32_t k, int m) { return (uint32_t)(P.ptr[m][(size_t)k + 1] - P.ptr[m][k]); };
+    const JdsLayout J = jds_layout(nCons, [&](uint32_t k) { return len_of(k, 0) + len_of(k, 1) + len_of(k, 2); }, R1CS_LONG);
+    const uint32_t nlong = J.nlong; const std::vector<uint32_t>& jdptr = J.jdptr;
     std::vector<uint4> rows(nCons);
     for (uint32_t s = 0; s < nCons; s++) {
-        const uint32_t k = perm[s];
-        const uint32_t la = (uint32_t)(P.ptr[0][(size_t)k + 1] - P.ptr[0][k]), lb = (uint32_t)(P.ptr[1][(size_t)k + 1] - P.ptr[1][k]), lc = (uint32_t)(P.ptr[2][(size_t)k + 1] - P.ptr[2][k]);
+        const uint32_t k = J.perm[s], la = len_of(k, 0), lb = len_of(k, 1), lc = len_of(k, 2);
         rows[s] = make_uint4(la, la + lb, la + lb + lc, k);
     }
-    const uint32_t maxlen = nCons ? rows[0].z : 0;
-    uint32_t nlong = 0; while (nlong < nCons && rows[nlong].z > R1CS_LONG) nlong++;
     if ((uint64_t)nCons + 63ull * nlong + 255 >= (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_r1cs_load: too many long constraints");
-    std::vector<uint32_t> jdptr((size_t)maxlen + 1, 0);
-    { size_t live = nCons; for (uint32_t j = 0; j < maxlen; j++) { while (live > 0 && rows[live - 1].z <= j) live--; jdptr[j + 1] = jdptr[j] + (uint32_t)live; } }
     std::vector<uint32_t> jcol((size_t)nTerms + 1, 0); std::vector<Fr> jval((size_t)nTerms + 1, Fr::zero());
     Fr r2, one_r2, neg_r2; for (int i = 0; i < 8; i++) r2.v[i] = FrParams::r2[i];
     one_r2 = r2; neg_r2 = Fr::zero() - one_r2;
-    uint64_t nUnit = 0;
-    for (uint32_t s = 0; s < nCons; s++) {
-        const uint32_t k = perm[s]; uint32_t j = 0;
-        for (int m = 0; m < 3; m++)
-            for (uint64_t t = P.ptr[m][k]; t < P.ptr[m][(size_t)k + 1]; t++, j++) {
-                const parse::R1csTerm& T = P.terms[m][(size_t)t];
-                uint32_t sv[8]; memcpy(sv, T.coef, 32);
-                const Fr v = fp_from_std<FrParams>(sv) * r2;        // val R^2: a coefficient >= r enters as its residue
-                uint32_t cw = T.wire;
-                if (v == one_r2) { cw |= MV_UNIT; nUnit++; } else if (v == neg_r2) { cw |= MV_UNIT | MV_NEG; nUnit++; }
-                const size_t dst = (size_t)jdptr[j] + s;
-                jcol[dst] = cw; jval[dst] = v;
-            }
-    }
+    const uint64_t nUnit = jds_fill(J, [&](uint32_t k, uint32_t j) {      // term j of merged row k: A's terms, then B's, then C's
+        int m = 0; while (j >= len_of(k, m)) j -= len_of(k, m++);
+        const parse::R1csTerm& T = P.terms[m][(size_t)(P.ptr[m][k] + j)];
+        uint32_t sv[8]; memcpy(sv, T.coef, 32);
+        return std::pair<uint32_t, Fr>(T.wire, fp_from_std<FrParams>(sv) * r2);        // val R^2: a coefficient >= r enters as its residue
+    }, one_r2, neg_r2, jcol.data(), jval.data());
     const double host_ms = ms_since(t0);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     zkc_r1cs* cs = new zkc_r1cs(); cs->ctx = ctx;

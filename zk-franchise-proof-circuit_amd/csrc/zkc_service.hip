@@ -40,7 +40,6 @@
 #include <vector>
 
 namespace sw = zkc::sw;
-int zkc_lane_streams(zkc_ctx* ctx, int l, bool with_red, zkc_ctx::LaneStreams* out);      // zkc_api.hip
 namespace {
 enum { KIND_FULLPROVE = 0, KIND_PROVE = 1 };
 struct KeyImage {                                                  // the service's own copy of a .zkey image: outlives the caller's buffer, shared by all devices

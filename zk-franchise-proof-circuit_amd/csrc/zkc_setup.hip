@@ -10,7 +10,6 @@
 // products of the two generators, on host threads (zkc_setup_from_r1cs: zkc_fixedbase.h) or on the GPU (zkc_setup_from_r1cs_dev: zkc_fixedbase_dev.hip).  3 (host):
 // write the .zkey and the JSON.  Field elements are canonical and the affine form of a point is unique, so the two entry points write the same bytes.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -25,15 +24,10 @@
 
 #include "zkc_hostparse.h"
 #include "zkc_r1cs_parse.h"
-extern "C" int zkc_pairing_bin(const uint8_t g1[64], const uint8_t g2[128], uint8_t out[384]);
+#include "zkc_host_util.h"
 using namespace zkc;
 
 namespace {
-
-const uint32_t G2X0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
-const uint32_t G2X1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
-const uint32_t G2Y0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
-const uint32_t G2Y1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
 
 struct Rng {   // splitmix64
     uint64_t s;
@@ -47,14 +41,6 @@ struct Rng {   // splitmix64
 };
 
 Fr fr_pow(Fr a, uint64_t e) { Fr r = Fr::one(); while (e) { if (e & 1) r = r * a; a = a * a; e >>= 1; } return r; }
-Fr fr_root_of_unity(int logn) {          // 5^((r-1)/2^logn), ffjavascript's Fr.w[logn]
-    uint32_t e[8]; for (int i = 0; i < 8; i++) e[i] = FrParams::p[i]; e[0] -= 1;
-    for (int i = 0; i < 8; i++) e[i] = (e[i] >> 28) | (i < 7 ? e[i + 1] << 4 : 0);
-    Fr g = fp_from_u32<FrParams>(5), w = Fr::one();
-    for (int i = 255; i >= 0; i--) { w = w * w; if ((e[i >> 5] >> (i & 31)) & 1) w = w * g; }
-    for (int i = 28; i > logn; i--) w = w * w;
-    return w;
-}
 void batch_inverse(std::vector<Fr>& v) {  // in place; zeros stay zero
     std::vector<Fr> pre(v.size()); Fr acc = Fr::one();
     for (size_t i = 0; i < v.size(); i++) { pre[i] = acc; if (!v[i].is_zero()) acc = acc * v[i]; }
@@ -67,28 +53,17 @@ struct Cons { std::vector<Term> a, b, c; };
 
 void put32(std::vector<uint8_t>& o, uint32_t v) { uint8_t b[4]; memcpy(b, &v, 4); o.insert(o.end(), b, b + 4); }
 void put_raw(std::vector<uint8_t>& o, const void* p, size_t n) { o.insert(o.end(), (const uint8_t*)p, (const uint8_t*)p + n); }
-void put_fq(std::vector<uint8_t>& o, const Fq& a) { put_raw(o, a.v, 32); }                     // Montgomery, as .zkey stores points
-void put_g1(std::vector<uint8_t>& o, const G1Affine& p) { put_fq(o, p.x); put_fq(o, p.y); }
-void put_g2(std::vector<uint8_t>& o, const G2Affine& p) { put_fq(o, p.x.c0); put_fq(o, p.x.c1); put_fq(o, p.y.c0); put_fq(o, p.y.c1); }
+void put_g1(std::vector<uint8_t>& o, const G1Affine& p) { o.resize(o.size() + 64); wr_g1_mont(o.data() + o.size() - 64, p); }
+void put_g2(std::vector<uint8_t>& o, const G2Affine& p) { o.resize(o.size() + 128); wr_g2_mont(o.data() + o.size() - 128, p); }
 
-std::string dec(const uint32_t s_in[8]) {
-    uint32_t s[8]; memcpy(s, s_in, 32); std::string out;
-    bool nz = true;
-    while (nz) {
-        uint64_t rem = 0; nz = false;
-        for (int i = 7; i >= 0; i--) { uint64_t cur = (rem << 32) | s[i]; s[i] = (uint32_t)(cur / 10); rem = cur % 10; if (s[i]) nz = true; }
-        out.push_back((char)('0' + rem));
-    }
-    return std::string(out.rbegin(), out.rend());
-}
-std::string dec_fq(const Fq& a) { uint32_t s[8]; fp_to_std<FqParams>(s, a); return dec(s); }
+std::string dec_fq(const Fq& a) { uint8_t s[32]; wr_fq_std(s, a); return parse::dec_of(s); }
 std::string json_g1(const G1Affine& p) { return "[\n  \"" + dec_fq(p.x) + "\",\n  \"" + dec_fq(p.y) + "\",\n  \"1\"\n ]"; }
 std::string json_g2(const G2Affine& p) {
     return "[\n  [\n   \"" + dec_fq(p.x.c0) + "\",\n   \"" + dec_fq(p.x.c1) + "\"\n  ],\n  [\n   \"" + dec_fq(p.y.c0) + "\",\n   \"" + dec_fq(p.y.c1) +
            "\"\n  ],\n  [\n   \"1\",\n   \"0\"\n  ]\n ]";
 }
 
-int fail(char* err, size_t errlen, const std::string& m) { if (err && errlen) { snprintf(err, errlen, "%s", m.c_str()); } return ZKC_ERR_FORMAT; }
+int fail(char* err, size_t errlen, const std::string& m) { return err_out(err, errlen, ZKC_ERR_FORMAT, m); }
 
 }  // namespace
 
@@ -110,12 +85,6 @@ struct SetupPoints {
 };
 
 thread_local double g_setup_ms[4] = {0, 0, 0, 0};
-typedef std::chrono::steady_clock::time_point tick;
-tick now() { return std::chrono::steady_clock::now(); }
-double ms_between(tick a, tick b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
-
-G1Affine g1_generator() { return {Fq::one(), fp_from_u32<FqParams>(2)}; }
-G2Affine g2_generator() { return {{fp_from_std<FqParams>(G2X0), fp_from_std<FqParams>(G2X1)}, {fp_from_std<FqParams>(G2Y0), fp_from_std<FqParams>(G2Y1)}}; }
 
 // ---- stage 1: .r1cs -> scalars ----
 int setup_scalars(const char* r1cs_path, uint64_t seed, SetupScalars& S, char* err, size_t errlen) {
@@ -174,9 +143,9 @@ int setup_scalars(const char* r1cs_path, uint64_t seed, SetupScalars& S, char* e
 
 // ---- stage 2 on the host: fixed-base products on host threads ----
 void setup_points_host(const SetupScalars& S, SetupPoints& P) {
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     FixedBase<Fq> fb1(g1_generator()); FixedBase<Fq2> fb2(g2_generator());
-    const tick t1 = now();
+    const clk::time_point t1 = clk::now();
     const uint32_t nWires = S.nWires, n = S.n;
     P.pA.resize(nWires); P.pB1.resize(nWires); P.pC.resize(nWires); P.pH.resize(n); P.pB2.resize(nWires);
     parallel_for(nWires, [&](size_t a, size_t b) {
@@ -185,12 +154,11 @@ void setup_points_host(const SetupScalars& S, SetupPoints& P) {
     parallel_for(n, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) P.pH[i] = fb1.mul(S.h[i]); });
     P.alpha1 = fb1.mul(S.alpha); P.beta1 = fb1.mul(S.beta); P.delta1 = fb1.mul(S.delta);
     P.beta2 = fb2.mul(S.beta); P.gamma2 = fb2.mul(S.gamma); P.delta2 = fb2.mul(S.delta);
-    g_setup_ms[1] = ms_between(t0, t1); g_setup_ms[2] = ms_between(t1, now());
+    g_setup_ms[1] = ms_since(t0, t1); g_setup_ms[2] = ms_since(t1);
 }
 
 // ---- stage 2 on the device: one batch per group.  G1: u | v | kc | h | alpha, beta, delta; G2: v | beta, gamma, delta.  The scalars go up as they are (Montgomery form)
 // and the points come back in Montgomery form, which is what the vectors hold. ----
-struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
 int setup_points_dev(zkc_ctx* ctx, const SetupScalars& S, SetupPoints& P) {
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -198,11 +166,10 @@ int setup_points_dev(zkc_ctx* ctx, const SetupScalars& S, SetupPoints& P) {
     if (N1 > 0xffffffffull) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_setup_from_r1cs_dev: circuit too large");
     P.pA.resize(nWires); P.pB1.resize(nWires); P.pC.resize(nWires); P.pH.resize(n); P.pB2.resize(nWires);
     DevBuf k, out, t1, t2; int rc;
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     if ((rc = fixed_table_g1(ctx, g1_generator(), (G1Affine**)&t1.p, nullptr)) || (rc = fixed_table_g2(ctx, g2_generator(), (uint32_t**)&t2.p, nullptr))) return rc;
-    const tick t1e = now();
-    ZKC_HIP_CHECK(ctx, hipMalloc(&k.p, N1 * sizeof(Fr)));
-    ZKC_HIP_CHECK(ctx, hipMalloc(&out.p, std::max(N1 * sizeof(G1Affine), N2 * sizeof(G2Affine))));
+    const clk::time_point t1e = clk::now();
+    if ((rc = k.alloc(ctx, N1 * sizeof(Fr))) || (rc = out.alloc(ctx, std::max(N1 * sizeof(G1Affine), N2 * sizeof(G2Affine))))) return rc;
     Fr* dk = (Fr*)k.p;
     const Fr tail1[3] = {S.alpha, S.beta, S.delta}, tail2[3] = {S.beta, S.gamma, S.delta};
     ZKC_HIP_CHECK(ctx, hipMemcpy(dk, S.u.data(), nWires * sizeof(Fr), hipMemcpyHostToDevice));
@@ -225,7 +192,7 @@ int setup_points_dev(zkc_ctx* ctx, const SetupScalars& S, SetupPoints& P) {
     ZKC_HIP_CHECK(ctx, hipMemcpy(P.pB2.data(), o2, nWires * sizeof(G2Affine), hipMemcpyDeviceToHost));
     ZKC_HIP_CHECK(ctx, hipMemcpy(got2, o2 + nWires, sizeof(got2), hipMemcpyDeviceToHost));
     P.beta2 = got2[0]; P.gamma2 = got2[1]; P.delta2 = got2[2];
-    g_setup_ms[1] = ms_between(t0, t1e); g_setup_ms[2] = ms_between(t1e, now());
+    g_setup_ms[1] = ms_since(t0, t1e); g_setup_ms[2] = ms_since(t1e);
     return ZKC_OK;
 }
 
@@ -264,10 +231,8 @@ int setup_write(const SetupScalars& S, const SetupPoints& P, const char* zkey_pa
         std::string j = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(nPub) + ",\n";
         j += " \"vk_alpha_1\": " + json_g1(alpha1) + ",\n \"vk_beta_2\": " + json_g2(beta2) + ",\n \"vk_gamma_2\": " + json_g2(gamma2) + ",\n \"vk_delta_2\": " + json_g2(delta2) + ",\n";
         {
-            uint8_t a[64], b[128], e[384]; uint32_t t[8];
-            fp_to_std<FqParams>(t, alpha1.x); memcpy(a, t, 32); fp_to_std<FqParams>(t, alpha1.y); memcpy(a + 32, t, 32);
-            const Fq* bc[4] = {&beta2.x.c0, &beta2.x.c1, &beta2.y.c0, &beta2.y.c1};
-            for (int i = 0; i < 4; i++) { fp_to_std<FqParams>(t, *bc[i]); memcpy(b + 32 * i, t, 32); }
+            uint8_t a[64], b[128], e[384];
+            wr_g1_std(a, alpha1); wr_g2_std(b, beta2);
             if (zkc_pairing_bin(a, b, e) != ZKC_OK) return fail(err, errlen, "pairing e(alpha, beta) failed");
             j += " \"vk_alphabeta_12\": [\n";
             for (int h = 0; h < 2; h++) {
@@ -291,13 +256,13 @@ int setup_write(const SetupScalars& S, const SetupPoints& P, const char* zkey_pa
 extern "C" int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_path, const char* vkey_json_path,
                                    char* err, size_t errlen) {
     SetupScalars S; SetupPoints P;
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     int rc = setup_scalars(r1cs_path, seed, S, err, errlen); if (rc) return rc;
-    const tick t1 = now(); g_setup_ms[0] = ms_between(t0, t1);
+    const clk::time_point t1 = clk::now(); g_setup_ms[0] = ms_since(t0, t1);
     setup_points_host(S, P);
-    const tick t2 = now();
+    const clk::time_point t2 = clk::now();
     rc = setup_write(S, P, zkey_path, vkey_json_path, err, errlen);
-    g_setup_ms[3] = ms_between(t2, now());
+    g_setup_ms[3] = ms_since(t2);
     return rc;
 }
 
@@ -306,13 +271,13 @@ extern "C" int zkc_setup_from_r1cs_dev(zkc_ctx* ctx, const char* r1cs_path, uint
                                        char* err, size_t errlen) {
     if (!ctx) { if (err && errlen) snprintf(err, errlen, "zkc_setup_from_r1cs_dev: no context"); return ZKC_ERR_BAD_ARG; }
     SetupScalars S; SetupPoints P;
-    const tick t0 = now();
+    const clk::time_point t0 = clk::now();
     int rc = setup_scalars(r1cs_path, seed, S, err, errlen); if (rc) return rc;
-    const tick t1 = now(); g_setup_ms[0] = ms_between(t0, t1);
+    const clk::time_point t1 = clk::now(); g_setup_ms[0] = ms_since(t0, t1);
     if ((rc = setup_points_dev(ctx, S, P))) { if (err && errlen) snprintf(err, errlen, "%s", zkc_last_error(ctx)); return rc; }
-    const tick t2 = now();
+    const clk::time_point t2 = clk::now();
     rc = setup_write(S, P, zkey_path, vkey_json_path, err, errlen);
-    g_setup_ms[3] = ms_between(t2, now());
+    g_setup_ms[3] = ms_since(t2);
     return rc;
 }
 

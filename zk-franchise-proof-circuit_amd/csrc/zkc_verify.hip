@@ -30,19 +30,14 @@ static Fq12 pairing_snarkjs(const G1Affine& P, const G2Affine& Q) { return final
 static thread_local std::string g_err;
 
 namespace zkc {
-bool rd_fq_std(Fq& o, const uint8_t* p) { uint32_t s[8]; memcpy(s, p, 32); if (!fp_std_lt_p<FqParams>(s)) return false; o = fp_from_std<FqParams>(s); return true; }
-bool rd_g1_std(G1Affine& o, const uint8_t* p) { return rd_fq_std(o.x, p) && rd_fq_std(o.y, p + 32); }
-bool rd_g2_std(G2Affine& o, const uint8_t* p) { return rd_fq_std(o.x.c0, p) && rd_fq_std(o.x.c1, p + 32) && rd_fq_std(o.y.c0, p + 64) && rd_fq_std(o.y.c1, p + 96); }
 void fq12_to_std(const Fq12& e, uint8_t out[384]) {
     const Fq2* c[6] = {&e.a.a0, &e.a.a1, &e.a.a2, &e.b.a0, &e.b.a1, &e.b.a2};
-    for (int i = 0; i < 6; i++) { uint32_t t[8]; fp_to_std<FqParams>(t, c[i]->c0); memcpy(out + 64 * i, t, 32); fp_to_std<FqParams>(t, c[i]->c1); memcpy(out + 64 * i + 32, t, 32); }
+    for (int i = 0; i < 6; i++) { wr_fq_std(out + 64 * i, c[i]->c0); wr_fq_std(out + 64 * i + 32, c[i]->c1); }
 }
 std::string& verify_error() { return g_err; }
 int vfail(int code, const std::string& m) { g_err = m; return code; }
 }  // namespace zkc
 
-// the text an entry point of rapidsnark's shape hands back beside its code
-static int err_out(char* err, size_t errlen, int code, const std::string& m) { if (err && errlen) snprintf(err, errlen, "%s", m.c_str()); return code; }
 // the header of a key straight from the file image (no GPU, no load, no coefficient scan: that is the loader's)
 static bool zkey_header(const void* zkey, size_t len, parse::ZkeyHeader& zh, std::string& why) {
     parse::BinSections bs;

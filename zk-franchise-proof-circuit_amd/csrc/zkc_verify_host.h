@@ -6,13 +6,11 @@
 #include <vector>
 #include "zkc_prover.h"
 #include "zkc_pairing.h"
+#include "zkc_host_util.h"
 
 #pragma GCC visibility push(hidden)
 namespace zkc {
-// points and field elements in the standard form of the C ABI (32 B little-endian per coordinate); false: a coordinate >= q
-bool rd_fq_std(Fq& o, const uint8_t* p);
-bool rd_g1_std(G1Affine& o, const uint8_t* p);
-bool rd_g2_std(G2Affine& o, const uint8_t* p);
+// points in the standard form of the C ABI: rd_*_std / wr_*_std (zkc_host_util.h)
 // an element of Fq12 as zkc_pairing_bin writes it: 12 x 32 B standard form, c0.a0.(c0, c1) c0.a1 c0.a2 c1.a0 c1.a1 c1.a2
 void fq12_to_std(const pairing::Fq12& e, uint8_t out[384]);
 
