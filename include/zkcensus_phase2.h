@@ -12,7 +12,8 @@
  * not: its G2 challenge is this library's own hash to G2 (SHA-256 try-and-increment), because snarkjs derives it from a ChaCha stream that cannot
  * be restated without its source.  snarkjs' `zkey verify` does not accept the proof of knowledge of a contribution made here, and zkc_zkey_verify_contributions does
  * not accept one made by snarkjs.  Beacon records (type 1) are parsed and carried over byte for byte, never created, and fail verification with a reason that says so.
- * A key from zkc_setup_from_r1cs* stays TEST ONLY after any number of contributions: with tau, alpha, beta known, (1 / delta) G falls out of any C point.
+ * A key from zkc_setup_from_r1cs* stays TEST ONLY after any number of contributions: with tau, alpha, beta known, (1 / delta) G falls out of any C point.  A key from
+ * zkc_setup_from_ptau (zkcensus_ptau.h) over a public powers-of-tau file, with at least one honest contribution on top, is not.
  *
  * The conventions are zkcensus.h's: 0 on success and a ZKC_ERR_* code otherwise, the text in zkc_last_error(ctx) or in err.
  * zkc_g1_scale_dev     : d_out[i] = k * d_points[i] for n points on the device (n x 64 B affine; all zero = infinity and gives infinity) and ONE scalar k (32 B
@@ -33,7 +34,7 @@
  * zkc_zkey_verify_contributions: is `final` an honest chain of contributions on top of `init`?  1 valid, 0 invalid (err names the first failing check), < 0 =
  *                        -ZKC_ERR_*, the convention of zkc_verify_batch.  *n_new (may be NULL) = records of final beyond init's.  seed32: NULL = the weights of check
  *                        (e) come from zkc_random_scalars; given = from the generator the batch verifier seeds the same way (reproducible: for tests).  Checks, in order:
- *                        (a) both images parse; nVars, nPublic, domainSize, alpha1, beta1, beta2, gamma2, csHash equal; sections 3-7 byte-equal
+ *                        (a) both images parse; nVars, nPublic, domainSize, alpha1, beta1, beta2, gamma2 equal; sections 3-7 byte-equal; csHash equal (in this order)
  *                        (b) init's records are a byte-equal prefix of final's
  *                        (c) from delta = init's delta1, for each new record: type 0 (a beacon fails here), points on their curves and g2_spx in G2, the stored
  *                            transcript equals the recomputed one, sameRatio(g1_s, g1_sx; g2_sp, g2_spx), sameRatio(delta, deltaAfter; g2_sp, g2_spx), delta = deltaAfter

@@ -18,7 +18,8 @@
  *                        for the same .r1cs and seed, same return codes and error texts for an unreadable, malformed or truncated .r1cs or an unwritable output
  *                        (ZKC_ERR_FORMAT, text in err); ZKC_ERR_BAD_ARG for ctx = NULL before any file is touched; ZKC_ERR_HIP (text in err and in
  *                        zkc_last_error) when the device fails.  Reading the file and the scalars of the key (linear in the constraint matrix) and writing the
- *                        outputs stay on the host and are shared with zkc_setup_from_r1cs.  TEST ONLY, as that function is: the toxic waste is known.
+ *                        outputs stay on the host and are shared with zkc_setup_from_r1cs.  TEST ONLY, as that function is: the toxic waste is known (a key nobody holds the
+ *                        waste of comes from zkc_setup_from_ptau, zkcensus_ptau.h).
  * zkc_setup_stats      : milliseconds of the calling thread's last zkc_setup_from_r1cs or zkc_setup_from_r1cs_dev: ms[0] read the .r1cs and compute the scalars, ms[1]
  *                        build the two window tables (host; the device path's upload included), ms[2] scalars -> points without the tables (device path: uploads,
  *                        kernels, downloads), ms[3] write the .zkey and the JSON (the pairing e(alpha, beta) included).  A call that failed leaves what it reached. ---- */

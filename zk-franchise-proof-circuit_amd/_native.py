@@ -146,6 +146,10 @@ def load():
     L.zkc_phase2_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
     L.zkc_debug_phase2_challenge_g2.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     L.zkc_debug_phase2_host_scale.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]
+    L.zkc_setup_from_ptau.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz]
+    L.zkc_zkey_verify_circuit.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.c_char_p, u32p, ctypes.c_char_p, sz]
+    L.zkc_setup_ptau_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.zkc_debug_setup_from_waste.argtypes = [ctypes.c_char_p] * 6 + [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz]
     _lib = L
     return L
 

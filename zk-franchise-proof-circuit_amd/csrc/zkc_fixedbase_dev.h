@@ -22,9 +22,10 @@ int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, dou
 int fixed_mul_g1(zkc_ctx* ctx, const G1Affine* d_table, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont);
 int fixed_mul_g2(zkc_ctx* ctx, const uint32_t* d_table29, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont);
 
-// The second half of a batch product on its own, for other kernels that leave XYZZ sums (zkc_phase2.hip): d_in (n points on the device, infinity = ZZ zero) -> d_out
-// (n x 64 B affine, all zero = infinity; d_out may alias whatever d_in was computed from) through the batched inversion of zkc_fixed_affine.  Launches on ctx->stream,
+// The second half of a batch product on its own, for other kernels that leave XYZZ sums (zkc_phase2.hip, zkc_setup_ptau.hip): d_in (n points on the device, infinity = ZZ
+// zero) -> d_out (n x 64 B affine, G2: n x 128 B; all zero = infinity; d_out may alias whatever d_in was computed from) through the batched inversion of zkc_fixed_affine.  Launches on ctx->stream,
 // synchronises and frees its work space before it returns; the context's lock is held by the caller.
 int fixed_affine_g1(zkc_ctx* ctx, const G1XYZZ* d_in, uint32_t n, void* d_out, bool out_mont);
+int fixed_affine_g2(zkc_ctx* ctx, const G2XYZZ* d_in, uint32_t n, void* d_out, bool out_mont);
 
 }  // namespace zkc

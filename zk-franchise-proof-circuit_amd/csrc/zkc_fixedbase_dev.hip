@@ -216,6 +216,15 @@ int fixed_affine_g1(zkc_ctx* ctx, const G1XYZZ* d_in, uint32_t n, void* d_out, b
     return ZKC_OK;
 }
 
+int fixed_affine_g2(zkc_ctx* ctx, const G2XYZZ* d_in, uint32_t n, void* d_out, bool out_mont) {
+    DevBuf pre; int rc;
+    if ((rc = pre.alloc(ctx, (size_t)n * sizeof(Fq2)))) return rc;
+    hipError_t e = launch_affine<Fq2>(ctx, d_in, pre.as<Fq2>(), n, out_mont, d_out);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_affine_g2: ") + hipGetErrorString(e));
+    return ZKC_OK;
+}
+
 int fixed_mul_g1(zkc_ctx* ctx, const G1Affine* d_table, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont) {
     return fixed_mul<Fq>(ctx, "fixed_mul_g1", n, d_out, out_mont, [&](XYZZ<Fq>* d_sum) {
         hipLaunchKernelGGL(zkc_fixed_acc_g1, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d_table, (const uint32_t*)d_scalars, scalars_mont ? 1 : 0, n, d_sum);

@@ -44,6 +44,15 @@ inline void wr_fq_std(uint8_t* p, const Fq& a) { uint32_t s[8]; fp_to_std<FqPara
 inline void wr_g1_std(uint8_t* p, const G1Affine& a) { wr_fq_std(p, a.x); wr_fq_std(p + 32, a.y); }
 inline void wr_g2_std(uint8_t* p, const G2Affine& a) { wr_fq_std(p, a.x.c0); wr_fq_std(p + 32, a.x.c1); wr_fq_std(p + 64, a.y.c0); wr_fq_std(p + 96, a.y.c1); }
 
+// a coordinate as a hash takes it: big-endian standard form
+inline void be_fq(uint8_t* o, const Fq& a) { uint32_t s[8]; fp_to_std<FqParams>(s, a); for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) o[4 * (7 - i) + (3 - b)] = (uint8_t)(s[i] >> (8 * b)); }
+// the "uncompressed" form of a point: x || y, G2 components c1 before c0; infinity = zeros with bit 0x40 of the first byte set
+inline void unc_g1(uint8_t o[64], const G1Affine& a) { if (a.is_inf()) { memset(o, 0, 64); o[0] = 0x40; return; } be_fq(o, a.x); be_fq(o + 32, a.y); }
+inline void unc_g2(uint8_t o[128], const G2Affine& a) {
+    if (a.is_inf()) { memset(o, 0, 128); o[0] = 0x40; return; }
+    be_fq(o, a.x.c1); be_fq(o + 32, a.x.c0); be_fq(o + 64, a.y.c1); be_fq(o + 96, a.y.c0);
+}
+
 // the text of an error into the caller's buffer (either may be absent); returns code
 inline int err_out(char* err, size_t errlen, int code, const std::string& m) { if (err && errlen) snprintf(err, errlen, "%s", m.c_str()); return code; }
 

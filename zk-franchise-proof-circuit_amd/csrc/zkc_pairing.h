@@ -239,4 +239,10 @@ inline Fq12 final_exp(const Fq12& f) {
     const Fq12 y13 = frobenius(y9, 1) * y11, y14 = frobenius(y8, 2) * y13, y15 = frobenius(conj12(r) * y9, 3);
     return y15 * y14;
 }
+// sameRatio(a, b; c, d) of the ceremonies: e(a, d) == e(b, c)
+inline bool same_ratio(const G1Affine& a, const G1Affine& b, const G2Affine& c, const G2Affine& d) {
+    const G2Prepared pd = prepare_g2(d), pc = prepare_g2(c);
+    const Pair pr[2] = {{a, &pd}, {affine_neg(b), &pc}};
+    return is_one12(final_exp(multi_miller(pr, 2)));
+}
 }}  // namespace zkc::pairing

@@ -157,14 +157,7 @@ int scale_dev(zkc_ctx* ctx, const void* d_points, uint32_t n, const uint32_t k[8
 }
 
 // ---- points of a .zkey on the host: rd_*_mont / wr_*_mont (zkc_host_util.h) ----
-// a coordinate as a hash takes it: big-endian standard form
-void be_fq(uint8_t* o, const Fq& a) { uint32_t s[8]; fp_to_std<FqParams>(s, a); for (int i = 0; i < 8; i++) for (int b = 0; b < 4; b++) o[4 * (7 - i) + (3 - b)] = (uint8_t)(s[i] >> (8 * b)); }
-// the "uncompressed" form of a point: x || y, G2 components c1 before c0; infinity = zeros with bit 0x40 of the first byte set
-void unc_g1(uint8_t o[64], const G1Affine& a) { if (a.is_inf()) { memset(o, 0, 64); o[0] = 0x40; return; } be_fq(o, a.x); be_fq(o + 32, a.y); }
-void unc_g2(uint8_t o[128], const G2Affine& a) {
-    if (a.is_inf()) { memset(o, 0, 128); o[0] = 0x40; return; }
-    be_fq(o, a.x.c1); be_fq(o + 32, a.x.c0); be_fq(o + 64, a.y.c1); be_fq(o + 96, a.y.c0);
-}
+// the uncompressed form of a point as a hash takes it: unc_g1 / unc_g2 (zkc_host_util.h)
 template <class F> Affine<F> host_mul(const Affine<F>& p, const uint32_t k[8]) { return xyzz_to_affine(xyzz_mul(XYZZ<F>::from_affine(p), k)); }
 
 // a square root in Fq2 = Fq[u] / (u^2 + 1), q = 3 mod 4, by the complex method (Adj, Rodriguez-Henriquez, "Square root computation over even extension fields", alg. 9):
@@ -215,12 +208,7 @@ G2Affine phase2_challenge_g2(const uint8_t transcript[64]) {
     }
 }
 
-// e(a, d) == e(b, c)
-bool same_ratio(const G1Affine& a, const G1Affine& b, const G2Affine& c, const G2Affine& d) {
-    const pairing::G2Prepared pd = pairing::prepare_g2(d), pc = pairing::prepare_g2(c);
-    const pairing::Pair pr[2] = {{a, &pd}, {affine_neg(b), &pc}};
-    return pairing::is_one12(pairing::final_exp(pairing::multi_miller(pr, 2)));
-}
+using pairing::same_ratio;                                  // e(a, d) == e(b, c): zkc_pairing.h
 
 // pubkey_j of a record: U(deltaAfter) U(g1_s) U(g1_sx) U(g2_spx) transcript, 384 bytes.  false: a coordinate >= q
 bool pubkey_bytes(const parse::P2Record& r, uint8_t out[384]) {
@@ -385,9 +373,9 @@ extern "C" int zkc_zkey_verify_contributions(zkc_ctx* ctx, const void* init, siz
     if (!read_image(final_, final_len, B, why)) return invalid("check (a): the final key does not parse: " + why);
     if (A.zh.nVars != B.zh.nVars || A.zh.nPub != B.zh.nPub || A.zh.n != B.zh.n) return invalid("check (a): nVars, nPublic or domainSize differ");
     if (memcmp(A.bs.sec[2] + OFF_ALPHA1, B.bs.sec[2] + OFF_ALPHA1, OFF_DELTA1 - OFF_ALPHA1)) return invalid("check (a): alpha1, beta1, beta2 or gamma2 differ");
-    if (memcmp(A.p2.csHash, B.p2.csHash, 64)) return invalid("check (a): the circuit hashes differ");
     for (int s = 3; s <= 7; s++)
         if (A.bs.ssz[s] != B.bs.ssz[s] || memcmp(A.bs.sec[s], B.bs.sec[s], (size_t)A.bs.ssz[s])) return invalid("check (a): section " + std::to_string(s) + " differs");
+    if (memcmp(A.p2.csHash, B.p2.csHash, 64)) return invalid("check (a): the circuit hashes differ");      // after the sections: a key of another circuit is told by the section that shows it
     // ---- (b) ----
     if (B.p2.n < A.p2.n || B.p2.records_len < A.p2.records_len) return invalid("check (b): the final key has fewer contributions than the initial key");
     {

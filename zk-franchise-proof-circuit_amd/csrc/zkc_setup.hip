@@ -25,6 +25,8 @@
 #include "zkc_hostparse.h"
 #include "zkc_r1cs_parse.h"
 #include "zkc_host_util.h"
+#include "zkc_setup_write.h"
+#include "../../include/zkcensus_ptau.h"
 using namespace zkc;
 
 namespace {
@@ -48,69 +50,25 @@ void batch_inverse(std::vector<Fr>& v) {  // in place; zeros stay zero
     for (size_t i = v.size(); i-- > 0;) { if (v[i].is_zero()) continue; Fr t = ai * pre[i]; ai = ai * v[i]; v[i] = t; }
 }
 
-struct Term { uint32_t wire; Fr coef; };
-struct Cons { std::vector<Term> a, b, c; };
-
-void put32(std::vector<uint8_t>& o, uint32_t v) { uint8_t b[4]; memcpy(b, &v, 4); o.insert(o.end(), b, b + 4); }
-void put_raw(std::vector<uint8_t>& o, const void* p, size_t n) { o.insert(o.end(), (const uint8_t*)p, (const uint8_t*)p + n); }
-void put_g1(std::vector<uint8_t>& o, const G1Affine& p) { o.resize(o.size() + 64); wr_g1_mont(o.data() + o.size() - 64, p); }
-void put_g2(std::vector<uint8_t>& o, const G2Affine& p) { o.resize(o.size() + 128); wr_g2_mont(o.data() + o.size() - 128, p); }
-
-std::string dec_fq(const Fq& a) { uint8_t s[32]; wr_fq_std(s, a); return parse::dec_of(s); }
-std::string json_g1(const G1Affine& p) { return "[\n  \"" + dec_fq(p.x) + "\",\n  \"" + dec_fq(p.y) + "\",\n  \"1\"\n ]"; }
-std::string json_g2(const G2Affine& p) {
-    return "[\n  [\n   \"" + dec_fq(p.x.c0) + "\",\n   \"" + dec_fq(p.x.c1) + "\"\n  ],\n  [\n   \"" + dec_fq(p.y.c0) + "\",\n   \"" + dec_fq(p.y.c1) +
-           "\"\n  ],\n  [\n   \"1\",\n   \"0\"\n  ]\n ]";
-}
-
-int fail(char* err, size_t errlen, const std::string& m) { return err_out(err, errlen, ZKC_ERR_FORMAT, m); }
-
 }  // namespace
 
 
 namespace {
 
-// what stage 1 leaves: the circuit, and every scalar of the key (Montgomery form)
-struct SetupScalars {
-    uint32_t nWires = 0, nPub = 0, nCons = 0, n = 0;             // n: the domain size
-    std::vector<Cons> cons;
-    std::vector<Fr> u, v, kc;                                    // per wire: A(tau), B(tau), (beta A + alpha B + C)(tau) / gamma (public wires) or / delta
-    std::vector<Fr> h;                                           // per domain point: L'_i(tau) Z(tau) / (-2 delta)
-    Fr alpha, beta, gamma, delta;
-};
-// what stage 2 leaves: the same, times the generators
-struct SetupPoints {
-    std::vector<G1Affine> pA, pB1, pC, pH; std::vector<G2Affine> pB2;
-    G1Affine alpha1, beta1, delta1; G2Affine beta2, gamma2, delta2;
-};
-
 thread_local double g_setup_ms[4] = {0, 0, 0, 0};
 
 // ---- stage 1: .r1cs -> scalars ----
-int setup_scalars(const char* r1cs_path, uint64_t seed, SetupScalars& S, char* err, size_t errlen) {
-    // ---- read .r1cs ----
-    FILE* f = fopen(r1cs_path, "rb"); if (!f) return fail(err, errlen, std::string("cannot open ") + r1cs_path);
-    fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    std::vector<uint8_t> buf((size_t)sz); if (fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) { fclose(f); return fail(err, errlen, "short read"); } fclose(f);
-    // ---- parse it (zkc_r1cs_parse.h: the host-only reader, with every check and its text) ----
-    parse::R1cs cs; std::string perr;
-    if (!parse::r1cs_parse(buf.data(), buf.size(), cs, perr)) return fail(err, errlen, perr);
-    const uint32_t nWires = cs.h.nWires, nPub = cs.h.nPub, nCons = cs.h.nCons;
-    std::vector<Cons>& cons = S.cons; cons.resize(nCons);
-    for (uint32_t k = 0; k < nCons; k++) {
-        std::vector<Term>* v[3] = {&cons[k].a, &cons[k].b, &cons[k].c};
-        for (int m = 0; m < 3; m++) {
-            const uint64_t t0 = cs.ptr[m][k], t1 = cs.ptr[m][k + 1];
-            v[m]->resize((size_t)(t1 - t0));
-            for (uint64_t t = t0; t < t1; t++) { uint32_t s[8]; memcpy(s, cs.terms[m][t].coef, 32); (*v[m])[t - t0] = Term{cs.terms[m][t].wire, fp_from_std<FrParams>(s)}; }
-        }
-    }
-    uint32_t logn = 0; while ((1u << logn) < nCons + nPub + 1) logn++;
-    const uint32_t n = 1u << logn;
-    S.nWires = nWires; S.nPub = nPub; S.nCons = nCons; S.n = n;
+// the five values a seed stands for: tau, alpha, beta, gamma, delta
+void draw_waste(uint64_t seed, Fr w[5]) { Rng rng{seed}; for (int i = 0; i < 5; i++) w[i] = rng.fr(); }
+
+int setup_scalars(const char* r1cs_path, const Fr waste[5], SetupScalars& S, char* err, size_t errlen) {
+    std::vector<uint8_t> buf; int rc;
+    if ((rc = read_file(r1cs_path, buf, err, errlen)) || (rc = setup_circuit(buf, S, err, errlen))) return rc;
+    const uint32_t nWires = S.nWires, nPub = S.nPub, nCons = S.nCons, n = S.n;
+    const std::vector<Cons>& cons = S.cons;
+    uint32_t logn = 0; while ((1u << logn) < n) logn++;
     // ---- toxic waste ----
-    Rng rng{seed};
-    const Fr tau = rng.fr(), alpha = rng.fr(), beta = rng.fr(), gamma = rng.fr(), delta = rng.fr();
+    const Fr tau = waste[0], alpha = waste[1], beta = waste[2], gamma = waste[3], delta = waste[4];
     S.alpha = alpha; S.beta = beta; S.gamma = gamma; S.delta = delta;
     const Fr w = fr_root_of_unity((int)logn), g = fr_root_of_unity((int)logn + 1);
     const Fr ninv = fp_inv<FrParams>(fp_from_u32<FrParams>(n));
@@ -196,60 +154,7 @@ int setup_points_dev(zkc_ctx* ctx, const SetupScalars& S, SetupPoints& P) {
     return ZKC_OK;
 }
 
-// ---- stage 3: points -> .zkey and verification_key.json ----
-int setup_write(const SetupScalars& S, const SetupPoints& P, const char* zkey_path, const char* vkey_json_path, char* err, size_t errlen) {
-    const uint32_t nWires = S.nWires, nPub = S.nPub, nCons = S.nCons, n = S.n;
-    const std::vector<Cons>& cons = S.cons;
-    const std::vector<G1Affine>&pA = P.pA, &pB1 = P.pB1, &pC = P.pC, &pH = P.pH; const std::vector<G2Affine>& pB2 = P.pB2;
-    const G1Affine &alpha1 = P.alpha1, &beta1 = P.beta1, &delta1 = P.delta1; const G2Affine &beta2 = P.beta2, &gamma2 = P.gamma2, &delta2 = P.delta2;
-    // ---- .zkey ----
-    std::vector<std::vector<uint8_t>> sec(11);
-    put32(sec[1], 1);
-    put32(sec[2], 32); put_raw(sec[2], FqParams::p, 32); put32(sec[2], 32); put_raw(sec[2], FrParams::p, 32);
-    put32(sec[2], nWires); put32(sec[2], nPub); put32(sec[2], n);
-    put_g1(sec[2], alpha1); put_g1(sec[2], beta1); put_g2(sec[2], beta2); put_g2(sec[2], gamma2); put_g1(sec[2], delta1); put_g2(sec[2], delta2);
-    for (uint32_t i = 0; i <= nPub; i++) put_g1(sec[3], pC[i]);
-    {
-        uint32_t ncoef = nPub + 1; for (auto& c : cons) ncoef += (uint32_t)(c.a.size() + c.b.size());
-        put32(sec[4], ncoef);
-        Fr r2; for (int i = 0; i < 8; i++) r2.v[i] = FrParams::r2[i];
-        auto put_coef = [&](uint32_t m, uint32_t c, uint32_t s, const Fr& val) { put32(sec[4], m); put32(sec[4], c); put32(sec[4], s); Fr dm = val * r2; put_raw(sec[4], dm.v, 32); };
-        for (uint32_t k = 0; k < nCons; k++) { for (auto& t : cons[k].a) put_coef(0, k, t.wire, t.coef); for (auto& t : cons[k].b) put_coef(1, k, t.wire, t.coef); }
-        for (uint32_t i = 0; i <= nPub; i++) put_coef(0, nCons + i, i, Fr::one());
-    }
-    for (uint32_t i = 0; i < nWires; i++) { put_g1(sec[5], pA[i]); put_g1(sec[6], pB1[i]); put_g2(sec[7], pB2[i]); }
-    for (uint32_t i = nPub + 1; i < nWires; i++) put_g1(sec[8], pC[i]);
-    for (uint32_t i = 0; i < n; i++) put_g1(sec[9], pH[i]);
-    sec[10].assign(64, 0); put32(sec[10], 0);                              // circuit hash (unused here), 0 contributions
-    FILE* o = fopen(zkey_path, "wb"); if (!o) return fail(err, errlen, std::string("cannot write ") + zkey_path);
-    fwrite("zkey", 1, 4, o); uint32_t ver = 1, ns = 10; fwrite(&ver, 4, 1, o); fwrite(&ns, 4, 1, o);
-    for (uint32_t id = 1; id <= 10; id++) { uint64_t len = sec[id].size(); fwrite(&id, 4, 1, o); fwrite(&len, 8, 1, o); fwrite(sec[id].data(), 1, len, o); }
-    fclose(o);
-    // ---- verification_key.json (members and order of artifacts/zkCensus/dev/160/verification_key.json, vk_alphabeta_12 = e(alpha1, beta2)
-    //      as snarkjs' `zkey export verificationkey` prints it, circuit/circuit-compiler.sh:133-134) ----
-    if (vkey_json_path) {
-        std::string j = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(nPub) + ",\n";
-        j += " \"vk_alpha_1\": " + json_g1(alpha1) + ",\n \"vk_beta_2\": " + json_g2(beta2) + ",\n \"vk_gamma_2\": " + json_g2(gamma2) + ",\n \"vk_delta_2\": " + json_g2(delta2) + ",\n";
-        {
-            uint8_t a[64], b[128], e[384];
-            wr_g1_std(a, alpha1); wr_g2_std(b, beta2);
-            if (zkc_pairing_bin(a, b, e) != ZKC_OK) return fail(err, errlen, "pairing e(alpha, beta) failed");
-            j += " \"vk_alphabeta_12\": [\n";
-            for (int h = 0; h < 2; h++) {
-                j += "  [\n";
-                for (int k = 0; k < 3; k++) j += "   [\"" + zkc::parse::dec_of(e + 64 * (3 * h + k)) + "\", \"" + zkc::parse::dec_of(e + 64 * (3 * h + k) + 32) + "\"]" + (k < 2 ? ",\n" : "\n");
-                j += h == 0 ? "  ],\n" : "  ]\n";
-            }
-            j += " ],\n";
-        }
-        j += " \"IC\": [\n";
-        for (uint32_t i = 0; i <= nPub; i++) j += "  " + json_g1(pC[i]) + (i < nPub ? ",\n" : "\n");
-        j += " ]\n}\n";
-        FILE* v = fopen(vkey_json_path, "wb"); if (!v) return fail(err, errlen, std::string("cannot write ") + vkey_json_path);
-        fwrite(j.data(), 1, j.size(), v); fclose(v);
-    }
-    return ZKC_OK;
-}
+// ---- stage 3: points -> .zkey and verification_key.json: setup_write (zkc_setup_write.h), shared with zkc_setup_ptau.hip ----
 
 }  // namespace
 
@@ -257,7 +162,8 @@ extern "C" int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const c
                                    char* err, size_t errlen) {
     SetupScalars S; SetupPoints P;
     const clk::time_point t0 = clk::now();
-    int rc = setup_scalars(r1cs_path, seed, S, err, errlen); if (rc) return rc;
+    Fr waste[5]; draw_waste(seed, waste);
+    int rc = setup_scalars(r1cs_path, waste, S, err, errlen); if (rc) return rc;
     const clk::time_point t1 = clk::now(); g_setup_ms[0] = ms_since(t0, t1);
     setup_points_host(S, P);
     const clk::time_point t2 = clk::now();
@@ -272,7 +178,8 @@ extern "C" int zkc_setup_from_r1cs_dev(zkc_ctx* ctx, const char* r1cs_path, uint
     if (!ctx) { if (err && errlen) snprintf(err, errlen, "zkc_setup_from_r1cs_dev: no context"); return ZKC_ERR_BAD_ARG; }
     SetupScalars S; SetupPoints P;
     const clk::time_point t0 = clk::now();
-    int rc = setup_scalars(r1cs_path, seed, S, err, errlen); if (rc) return rc;
+    Fr waste[5]; draw_waste(seed, waste);
+    int rc = setup_scalars(r1cs_path, waste, S, err, errlen); if (rc) return rc;
     const clk::time_point t1 = clk::now(); g_setup_ms[0] = ms_since(t0, t1);
     if ((rc = setup_points_dev(ctx, S, P))) { if (err && errlen) snprintf(err, errlen, "%s", zkc_last_error(ctx)); return rc; }
     const clk::time_point t2 = clk::now();
@@ -285,4 +192,21 @@ extern "C" int zkc_setup_stats(double ms[4]) {
     if (!ms) return ZKC_ERR_BAD_ARG;
     for (int i = 0; i < 4; i++) ms[i] = g_setup_ms[i];
     return ZKC_OK;
+}
+
+// Test hook (zkcensus_ptau.h): the host generator with the waste given instead of drawn.  What a key from a powers-of-tau file of that (tau, alpha, beta) must equal at
+// gamma = delta = 1 (tests/test_ptau_setup_cpu.py).  Every value is 32 bytes, little endian, standard form, in [1, r).
+extern "C" int zkc_debug_setup_from_waste(const char* r1cs_path, const uint8_t tau[32], const uint8_t alpha[32], const uint8_t beta[32], const uint8_t gamma[32],
+                                          const uint8_t delta[32], const char* zkey_path, const char* vkey_json_path, char* err, size_t errlen) {
+    if (!r1cs_path || !tau || !alpha || !beta || !gamma || !delta || !zkey_path) return err_out(err, errlen, ZKC_ERR_BAD_ARG, "zkc_debug_setup_from_waste: bad argument");
+    const uint8_t* in[5] = {tau, alpha, beta, gamma, delta}; Fr waste[5];
+    for (int i = 0; i < 5; i++) {
+        uint32_t s[8]; memcpy(s, in[i], 32);
+        if (!fp_std_lt_p<FrParams>(s) || !(s[0] | s[1] | s[2] | s[3] | s[4] | s[5] | s[6] | s[7])) return err_out(err, errlen, ZKC_ERR_BAD_ARG, "zkc_debug_setup_from_waste: a value outside [1, r)");
+        waste[i] = fp_from_std<FrParams>(s);
+    }
+    SetupScalars S; SetupPoints P;
+    int rc = setup_scalars(r1cs_path, waste, S, err, errlen); if (rc) return rc;
+    setup_points_host(S, P);
+    return setup_write(S, P, zkey_path, vkey_json_path, err, errlen);
 }

@@ -3,7 +3,8 @@
 
 The key material a contribution writes and the record layout of section 10 are snarkjs'; the proof of knowledge is not (its G2 challenge is this library's own hash to
 G2), so snarkjs' `zkey verify` does not accept a contribution made here and verify() does not accept one made by snarkjs.  A key from setup.ensure_test_artifacts stays
-TEST ONLY after any number of contributions: its toxic waste is known."""
+TEST ONLY after any number of contributions: its toxic waste is known.  A key from setup.from_ptau over a public powers-of-tau file, with at least one honest
+contribution on top, is not: verify_circuit() is `snarkjs zkey verify circuit.r1cs pot.ptau key.zkey` for it."""
 import ctypes
 from . import _native
 
@@ -61,6 +62,17 @@ def verify(ctx, init, final, seed=None):
     the weights of the batch check reproducible (tests); None draws them from the OS generator."""
     n, err = ctypes.c_uint32(0), ctypes.create_string_buffer(512)
     rc = ctx._lib.zkc_zkey_verify_contributions(ctx._h, init, len(init), final, len(final), None if seed is None else bytes(seed), ctypes.byref(n), err, 512)
+    if rc < 0:
+        raise _native.ZkcError(-rc, err.value.decode())
+    return rc == 1, n.value, err.value.decode()
+
+
+def verify_circuit(ctx, r1cs_path, ptau_path, final, seed=None):
+    """`snarkjs zkey verify` in full: is `final` an honest chain of contributions on top of THE initial key of this circuit and this powers-of-tau file?  The initial key
+    is derived on ctx's GPU (setup.from_ptau, into memory) and checked as verify() checks.  -> (ok, n_new, reason)."""
+    import os
+    n, err = ctypes.c_uint32(0), ctypes.create_string_buffer(512)
+    rc = ctx._lib.zkc_zkey_verify_circuit(ctx._h, os.fsencode(r1cs_path), os.fsencode(ptau_path), final, len(final), None if seed is None else bytes(seed), ctypes.byref(n), err, 512)
     if rc < 0:
         raise _native.ZkcError(-rc, err.value.decode())
     return rc == 1, n.value, err.value.decode()

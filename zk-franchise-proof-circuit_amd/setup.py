@@ -1,5 +1,6 @@
-"""Test-only key generation: r1cs.build() -> .r1cs -> zkc_setup_from_r1cs[_dev] -> .zkey + verification_key.json.
-Stand-in for `make compile` (circuit/circuit-compiler.sh:80-136) whose outputs are missing blobs."""
+"""Key generation.  Test-only keys: r1cs.build() -> .r1cs -> zkc_setup_from_r1cs[_dev] -> .zkey + verification_key.json, the stand-in for `make compile`
+(circuit/circuit-compiler.sh:80-136) whose outputs are missing blobs; their toxic waste comes from a seed.  Keys nobody holds the waste of: from_ptau(), `snarkjs
+groth16 setup` from a public prepared powers-of-tau file (include/zkcensus_ptau.h), to be followed by phase2.contribute."""
 import ctypes
 import hashlib
 import os
@@ -19,7 +20,7 @@ def artifact_paths(nLevels=160, seed=DEFAULT_SEED, directory=None):
 def _generator_stamp():
     """sha256 over the sources that decide the artifacts' bytes: a key written by an older generator is regenerated, never reused."""
     h = hashlib.sha256()
-    for f in (os.path.join(_HERE, 'r1cs.py'), os.path.join(_HERE, 'csrc', 'zkc_setup.hip'), os.path.join(_HERE, 'csrc', 'zkc_fixedbase.h'),
+    for f in (os.path.join(_HERE, 'r1cs.py'), os.path.join(_HERE, 'csrc', 'zkc_setup.hip'), os.path.join(_HERE, 'csrc', 'zkc_setup_write.h'), os.path.join(_HERE, 'csrc', 'zkc_fixedbase.h'),
               os.path.join(_HERE, 'csrc', 'zkc_fixedbase_dev.hip')):
         with open(f, 'rb') as fh:
             h.update(fh.read())
@@ -52,3 +53,23 @@ def ensure_test_artifacts(nLevels=160, seed=DEFAULT_SEED, directory=None, force=
         fh.write(stamp)
     os.replace(stamp_path + '.tmp%d' % os.getpid(), stamp_path)
     return r, z, v
+
+
+def from_ptau(r1cs_path, ptau_path, zkey_path, vkey=None, ctx=None):
+    """`snarkjs groth16 setup r1cs ptau zkey`: the initial key (gamma = delta = 1, no contributions) of the circuit from a PREPARED powers-of-tau file, and unless `vkey`
+    is None its verification_key.json.  With a Context the sums over the file's points run on its GPU, without one on host threads; the bytes are the same.  Raises
+    ZkcError with the refusal's text for a file that does not parse, does not fit the circuit, holds a point off its curve or fails a sanity check; nothing is written then."""
+    err = ctypes.create_string_buffer(512)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_setup_from_ptau(None if ctx is None else ctx._h, os.fsencode(r1cs_path), os.fsencode(ptau_path), os.fsencode(zkey_path),
+                                 None if vkey is None else os.fsencode(vkey), err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    return zkey_path, vkey
+
+
+def ptau_stats():
+    """Milliseconds of the calling thread's last from_ptau (or phase2.verify_circuit), by stage."""
+    ms = (ctypes.c_double * 6)()
+    _native.load().zkc_setup_ptau_stats(ms)
+    return dict(zip(['read_parse', 'transpose', 'upload', 'scale', 'accumulate_reduce', 'checks_write'], list(ms)))
