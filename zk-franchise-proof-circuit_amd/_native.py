@@ -150,6 +150,11 @@ def load():
     L.zkc_zkey_verify_circuit.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.c_char_p, u32p, ctypes.c_char_p, sz]
     L.zkc_setup_ptau_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
     L.zkc_debug_setup_from_waste.argtypes = [ctypes.c_char_p] * 6 + [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz]
+    L.zkc_g1_lagrange_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int, vp]
+    L.zkc_g2_lagrange_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int, vp]
+    L.zkc_ptau_prepare.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz]
+    L.zkc_ptau_check_prepared.argtypes = [vp, ctypes.c_char_p, u32p, u64p, ctypes.c_char_p, sz]
+    L.zkc_ptau_prepare_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _lib = L
     return L
 

@@ -1,0 +1,28 @@
+// zkc_ecntt.h -- host-side interface of the transform over points (zkc_ecntt.hip), for the file that builds on it (zkc_ptau_prepare.hip).  The kernels themselves are
+// launched only from their own file, so zkc_kernels.h does not list them.
+#pragma once
+#include "zkc_internal.h"
+#include "zkc_curve.h"
+
+namespace zkc {
+
+constexpr uint32_t ECNTT_MAX_LOGN = 28;            // the two-adicity of r - 1: Fr has no root of unity of a higher order (fr_root_of_unity)
+
+// The inverse twiddles w^-j, j < 2^(logn - 1), of the size-2^logn domain as Montgomery-form Fr on the device: the `inv` table of the loaders' twiddle set
+// (ntt_twiddle_tables without its limb forms; the forward table is freed again).  A table of a larger domain serves every smaller one by stride.  1 <= logn <=
+// ECNTT_MAX_LOGN, anything else is ZKC_ERR_BAD_ARG.  Free with hipFree.
+int ecntt_twiddles(zkc_ctx* ctx, uint32_t logn, Fr** d_tw);
+
+// d_out[c] = 1/n sum_i w^(-c i) d_pts[i] for the n = 2^logn affine points at d_pts (Montgomery words, all zero = infinity, ALREADY CHECKED: zkc_ptau_check_*), natural
+// order on both sides, affine again (out_mont: Montgomery words).  d_tw: ecntt_twiddles of tw_logn >= logn (may be NULL when logn < 2).  d_out may be d_pts.  Launches on
+// ctx->stream, has synchronised and freed its work space on return; the context's lock is held by the caller.  ms (may be NULL): += [0] the transform, [1] to affine.
+int ecntt_g1(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms);
+int ecntt_g2(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms);
+// the device bytes one call needs beside d_pts and d_out
+inline size_t ecntt_work_bytes(uint32_t logn, bool g2) { return ((size_t)1 << logn) * (g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ)) * 2; }
+
+// *bad = the smallest index of a point of d_pts (n points, Montgomery words) with a coordinate >= q or off its curve, 0xffffffff when there is none
+int ecntt_check_g1(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad);
+int ecntt_check_g2(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad);
+
+}  // namespace zkc

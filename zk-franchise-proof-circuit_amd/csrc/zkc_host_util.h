@@ -1,10 +1,15 @@
 // zkc_host_util.h -- host-side helpers with no other home, once each: the roots of unity of Fr, the generators, points as files and the C ABI carry them, an error text
-// into a caller's buffer, a millisecond timer.  Host only (nothing here is ZKC_HD), internal to the library.
+// into a caller's buffer, a millisecond timer, a loop over host threads.  Host only (nothing here is ZKC_HD), internal to the library.
 #pragma once
 #include <chrono>
 #include <cstdio>
+#include <algorithm>
+#include <atomic>
 #include <cstring>
+#include <functional>
 #include <string>
+#include <thread>
+#include <vector>
 #include "zkc_curve.h"
 
 #pragma GCC visibility push(hidden)
@@ -59,6 +64,19 @@ inline int err_out(char* err, size_t errlen, int code, const std::string& m) { i
 // milliseconds from t0 to t1 (now, when not given)
 using clk = std::chrono::steady_clock;
 inline double ms_since(clk::time_point t0, clk::time_point t1 = clk::now()) { return std::chrono::duration<double, std::milli>(t1 - t0).count(); }
+
+constexpr unsigned HOST_THREADS = 16;            // of the ctx = NULL paths (zkc_setup_ptau.hip, zkc_ptau_prepare.hip)
+// f over [0, n) in chunks of `grain`, handed out to at most HOST_THREADS threads as they come free (equal shares need not be equal work)
+inline void par_chunks(size_t n, size_t grain, const std::function<void(size_t, size_t)>& f) {
+    unsigned nt = std::thread::hardware_concurrency(); if (nt == 0) nt = 4; if (nt > HOST_THREADS) nt = HOST_THREADS;
+    if (n <= grain || nt == 1) { if (n) f(0, n); return; }
+    std::atomic<size_t> next{0};
+    auto work = [&] { for (;;) { const size_t a = next.fetch_add(grain); if (a >= n) return; f(a, std::min(n, a + grain)); } };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+}
 
 }  // namespace zkc
 #pragma GCC visibility pop

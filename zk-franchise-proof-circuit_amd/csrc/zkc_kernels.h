@@ -3,9 +3,10 @@
 // The kernels have C linkage, so the parameter list is not part of the symbol: a launch through a declaration that disagrees with the definition in another .hip file links
 // and then packs the wrong bytes into the kernel arguments.  Hence the launching files AND the defining file include this header: C++ allows one function of a given name with
 // C linkage, so a definition that disagrees with it fails to compile ("conflicting types").  No .hip file declares a kernel by hand (tests/test_kernel_decls_cpu.py); a kernel
-// used only inside its own file is not listed.  Needs only zkc_device.h and zkc_field.h: no host-side header reaches the kernel files through it.
+// used only inside its own file is not listed.  Needs only zkc_device.h, zkc_field.h and zkc_curve.h: no host-side header reaches the kernel files through it.
 #pragma once
 #include "zkc_field.h"
+#include "zkc_curve.h"
 #include "zkc_device.h"
 #include "zkc_jds.h"
 
@@ -64,5 +65,9 @@ extern "C" __global__ void zkc_smt_check_absent_wave(PoseidonTable tab, const ui
 extern "C" __global__ void zkc_r1cs_range(const Fr* wtns_std, size_t wtns_stride, uint32_t nWires, uint32_t* flag);
 extern "C" __global__ void zkc_r1cs_check_rows(const uint4* rows, const uint32_t* jdptr, const uint32_t* col, const Fr* val, const Fr* wtns_std, size_t wtns_stride,
                                                const Fr* wm_all, size_t wm_stride, uint32_t nCons, uint32_t nlong, uint32_t* first, uint32_t* count, const uint32_t* flag);
+
+// ---- zkc_setup_ptau.hip: the points of a file checked (launched from zkc_ecntt.hip too).  Montgomery words; *bad starts as 0xffffffff and ends as the smallest bad index ----
+extern "C" __global__ void zkc_ptau_check_g1(const uint32_t* pts, uint32_t n, uint32_t* bad);
+extern "C" __global__ void zkc_ptau_check_g2(const uint32_t* pts, uint32_t n, Fq2 twist_b, uint32_t* bad);
 
 }  // namespace zkc

@@ -434,7 +434,7 @@ int ntt_make_tw29(zkc_ctx* ctx, const Fr* d_tw, uint32_t count, uint32_t** out) 
 
 // The twiddles of a 2^logn transform: w^j and w^-j for j < n / 2, uploaded in Fr form and turned into the limb form.  Every table is built into a local owner and handed
 // over only when all of them exist: a failure leaves *out as it was and nothing allocated.
-int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out) {
+int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out, bool with_29) {
     const uint32_t half = 1u << (logn - 1);
     const Fr w = fr_root_of_unity(logn), wi = fp_inv<FrParams>(w);
     std::vector<Fr> f(half), b(half);
@@ -443,7 +443,7 @@ int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out)
     if ((rc = d_f.alloc(ctx, half * sizeof(Fr))) || (rc = d_b.alloc(ctx, half * sizeof(Fr)))) return rc;
     ZKC_HIP_CHECK(ctx, hipMemcpy(d_f.p, f.data(), half * sizeof(Fr), hipMemcpyHostToDevice));
     ZKC_HIP_CHECK(ctx, hipMemcpy(d_b.p, b.data(), half * sizeof(Fr), hipMemcpyHostToDevice));
-    if ((rc = ntt_make_tw29(ctx, d_f.as<Fr>(), half, (uint32_t**)&d_f29.p)) || (rc = ntt_make_tw29(ctx, d_b.as<Fr>(), half, (uint32_t**)&d_b29.p))) return rc;
+    if (with_29 && ((rc = ntt_make_tw29(ctx, d_f.as<Fr>(), half, (uint32_t**)&d_f29.p)) || (rc = ntt_make_tw29(ctx, d_b.as<Fr>(), half, (uint32_t**)&d_b29.p)))) return rc;
     out->fwd29 = (uint32_t*)d_f29.release(); out->inv29 = (uint32_t*)d_b29.release();
     out->fwd = keep_fr ? (Fr*)d_f.release() : nullptr; out->inv = keep_fr ? (Fr*)d_b.release() : nullptr;
     return ZKC_OK;

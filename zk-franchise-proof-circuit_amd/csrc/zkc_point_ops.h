@@ -1,0 +1,93 @@
+// zkc_point_ops.h -- G1 and G2 behind one interface for the kernels that work on the points of a file (zkc_setup_ptau.hip: a sparse matrix times a vector of points;
+// zkc_ecntt.hip: a transform over points): an accumulator in radix 2^29, set from / added to by an affine point in Montgomery words, and the complete additions of two
+// such accumulators.  Device only; product code.
+//
+// The additions.  Unlike a prover's bases these points are an adversary's, or merely unlucky, and all three exceptional cases of an addition occur in files the tests make:
+// equal points, opposite points, and infinity (with tau a root of unity all but one Lagrange point are infinity, and the monomial points repeat).  So: an all-zero point is
+// skipped, an accumulator at infinity is set rather than added to, and f29_madd's `false` return is taken at every mixed addition -- equal: double the accumulator (it holds
+// that very point), opposite: back to infinity -- in both groups (add_point).  G::add is the complete f29_pt_add / f29g2_pt_add.
+#pragma once
+#include "zkc_f29.h"
+#include "zkc_f29_g1.h"
+#include "zkc_f29_g2.h"
+
+namespace zkc {
+
+template <int W> __device__ __forceinline__ void load_words(uint32_t* w, const uint32_t* __restrict__ p) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+    for (int k = 0; k < W / 4; k++) { const uint4 v = q[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+}
+template <int W> __device__ __forceinline__ bool all_zero(const uint32_t* w) { uint32_t o = 0;
+#pragma unroll
+    for (int k = 0; k < W; k++) o |= w[k]; return o == 0; }
+__device__ __forceinline__ Fq fq_of(const uint32_t* w) { Fq a;
+#pragma unroll
+    for (int k = 0; k < 8; k++) a.v[k] = w[k]; return a; }
+// the leading bit of the 256-bit k leaves as the return value; k moves up by one
+__device__ __forceinline__ uint32_t shl1_out(uint32_t k[8]) {
+    const uint32_t top = k[7] >> 31;
+#pragma unroll
+    for (int i = 7; i > 0; i--) k[i] = (k[i] << 1) | (k[i - 1] >> 31);
+    k[0] <<= 1;
+    return top;
+}
+
+struct G1Ops {
+    static constexpr int W = 16;                                 // words of an affine point
+    typedef Fq F; typedef Acc29 Acc;
+    struct Pt { uint32_t x[9], y[9]; };
+    __device__ static __forceinline__ Pt enter(const uint32_t* w, bool neg) {
+        Pt p; Fq Y = fq_of(w + 8); if (neg) Y = fp_neg(Y);
+        f29_enter_fq(p.x, w); f29_enter_fq(p.y, Y.v);            // below 1.2 p each: well inside what f29_madd takes
+        return p;
+    }
+    __device__ static __forceinline__ void set(Acc& a, const Pt& p) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) { a.X[k] = p.x[k]; a.Y[k] = p.y[k]; a.ZZ[k] = a.ZZZ[k] = F29K<FqParams>::one.l[k]; }
+    }
+    __device__ static __forceinline__ bool madd(Acc& a, const Pt& p, bool& same_y) { return f29_madd(a, p.x, p.y, same_y); }
+    __device__ static __forceinline__ void dbl(Acc& a) { f29_acc_dbl(a); }
+    __device__ static __forceinline__ XYZZ<Fq> leave(const Acc& a) { return f29_pt_to_xyzz(a); }
+    // the complete operations' own form (loose, zkc_f29_g1.h)
+    __device__ static __forceinline__ Acc from_xyzz(const XYZZ<Fq>& p) { return f29_pt_from_xyzz(p); }
+    __device__ static __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29_pt_add(r, a, b); }
+    __device__ static __forceinline__ void pt_dbl(Acc& r, const Acc& a) { f29_pt_dbl(r, a); }
+    __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29_pt_is_inf(a); }
+};
+struct G2Ops {
+    static constexpr int W = 32;
+    typedef Fq2 F; typedef Acc29G2 Acc;
+    struct Pt { F2x29 x, y; };
+    __device__ static __forceinline__ Pt enter(const uint32_t* w, bool neg) {
+        Pt p; Fq2 X{fq_of(w), fq_of(w + 8)}, Y{fq_of(w + 16), fq_of(w + 24)}; if (neg) Y = fp_neg(Y);
+        f29g2_enter(p.x, X); f29g2_enter(p.y, Y);               // carried, below 3 p per component
+        return p;
+    }
+    __device__ static __forceinline__ void set(Acc& a, const Pt& p) {
+        a.X = p.x; a.Y = p.y;
+#pragma unroll
+        for (int k = 0; k < 9; k++) { a.ZZ.c0[k] = a.ZZZ.c0[k] = F29K<FqParams>::one.l[k]; a.ZZ.c1[k] = a.ZZZ.c1[k] = 0; }
+    }
+    __device__ static __forceinline__ bool madd(Acc& a, const Pt& p, bool& same_y) { return f29g2_madd_lean(a, p.x, p.y, same_y); }
+    // f29g2_pt_dbl returns X, Y below 3 p and ZZ, ZZZ below 2.6 p, carried: inside what f29g2_madd takes (its D24 dominates carried values below 5.29 p), and
+    // f29g2_madd's results are tame, which is what f29g2_pt_dbl takes
+    __device__ static __forceinline__ void dbl(Acc& a) { Acc r; f29g2_pt_dbl(r, a); a = r; }
+    __device__ static __forceinline__ XYZZ<Fq2> leave(const Acc& a) { return f29g2_pt_to_xyzz(a); }
+    __device__ static __forceinline__ Acc from_xyzz(const XYZZ<Fq2>& p) { return f29g2_pt_from_xyzz(p); }
+    __device__ static __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29g2_pt_add(r, a, b); }
+    __device__ static __forceinline__ void pt_dbl(Acc& r, const Acc& a) { f29g2_pt_dbl(r, a); }
+    __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29g2_pt_is_inf(a); }
+};
+
+// acc (inf: at infinity) += p, every case handled: see the head of the file
+template <class G> __device__ __forceinline__ void add_point(typename G::Acc& acc, bool& inf, const typename G::Pt& p) {
+    if (inf) { G::set(acc, p); inf = false; return; }
+    bool same_y = false;
+    if (!G::madd(acc, p, same_y)) {
+        if (same_y) G::dbl(acc);                 // acc holds p itself
+        else inf = true;                         // acc holds -p
+    }
+}
+
+}  // namespace zkc

@@ -252,7 +252,8 @@ int ntt_run(zkc_ctx* ctx, hipStream_t st, const Fr* src, Fr* dst, const uint32_t
 int ntt_make_tw29(zkc_ctx* ctx, const Fr* d_tw, uint32_t count, uint32_t** out);
 // w^j, w^-j (j < 2^(logn - 1)) on the device, in Fr form (keep_fr; else nullptr) and in radix 2^29.  All four or, on failure, none: *out is written on success only
 struct TwiddleTables { Fr *fwd = nullptr, *inv = nullptr; uint32_t *fwd29 = nullptr, *inv29 = nullptr; };
-int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out);
+// with_29 = false (and keep_fr): the Fr tables alone, fwd29 / inv29 stay nullptr and no conversion kernel runs (zkc_ecntt.hip reads scalars, not limbs)
+int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out, bool with_29 = true);
 // the window-c table of `count` G2 bases (device, window 0 = the bases as a .zkey stores them) in the accumulation's row form, 60 words per point: a copy of the bases is
 // shifted to msm_nw(c) windows, converted and dropped.  *out is written on success only; ends with ctx->stream synchronised
 int msm_g2_window_table29(zkc_ctx* ctx, const G2Affine* d_bases, uint32_t count, int c, const char* what, uint32_t** out);

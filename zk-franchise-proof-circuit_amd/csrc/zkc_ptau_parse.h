@@ -1,8 +1,8 @@
-// zkc_ptau_parse.h -- the host-only reader of a prepared powers-of-tau file, `.ptau` (product code): what `snarkjs powersoftau prepare phase2` leaves and
-// `snarkjs groth16 setup` reads (circuit/circuit-compiler.sh:99-108).
+// zkc_ptau_parse.h -- the host-only reader of a powers-of-tau file, `.ptau` (product code): what `snarkjs powersoftau prepare phase2` reads (circuit/circuit-compiler.sh:71;
+// ptau_open with need_prepared = false) and what it leaves and `snarkjs groth16 setup` reads (circuit/circuit-compiler.sh:99-108).
 //
 // Plain C++17 and POSIX pread, no HIP, in the manner of zkc_phase2_parse.h: compiled into libzkcensus.so by hipcc (zkc_setup_ptau.hip) and, with
-// -fsanitize=address,undefined, into tests/host/ptau_parse_asan.cc.  A public file is hundreds of GB (power 28), so nothing here reads a section: ptau_open walks the
+// -fsanitize=address,undefined, into tests/host/ptau_parse_asan.cc and tests/host/ptau_prepare_asan.cc.  A public file is hundreds of GB (power 28), so nothing here reads a section: ptau_open walks the
 // section table, 12 bytes per section at 64-bit offsets, and reads section 1; ptau_read fetches a range of points of one section into the caller's buffer.  Every
 // offset is checked against the file's size before it is used, in arithmetic that cannot wrap (power <= 28 bounds every product below 2^37), every failure has its
 // own text, and nothing is allocated in proportion to a number the file merely claims.
@@ -30,10 +30,14 @@
 namespace zkc { namespace parse {
 
 constexpr uint32_t PTAU_MAX_POWER = 28;
+// Fr has no root of unity of order above 2^28, and preparing a file of power p transforms at size 2^(p+1) (section 12's last block): `prepare phase2` and the check of a
+// prepared file stop one power below what the reader takes
+constexpr uint32_t PTAU_MAX_PREPARE_POWER = 27;
 struct Ptau {
     int fd = -1; uint64_t size = 0;
     uint32_t power = 0, ceremonyPower = 0;
     uint64_t off[16] = {0}, len[16] = {0}; bool have[16] = {false};
+    uint32_t nsections = 0; uint64_t end = 12;      // the table's count, and where its last section ends: [12, end) is every section as it lies in the file
     Ptau() = default; Ptau(const Ptau&) = delete; Ptau& operator=(const Ptau&) = delete;
     ~Ptau() { if (fd >= 0) close(fd); }
 };
@@ -54,7 +58,9 @@ inline uint64_t ptau_section_points(int section, uint32_t power) {
     }
 }
 
-inline bool ptau_open(const char* path, Ptau& p, std::string& err) {
+// need_prepared = false: sections 12 .. 15 are not asked for (the input of `prepare phase2`, zkc_ptau_prepare.hip); which of them the file has is in p.have.
+// max_power < PTAU_MAX_POWER: a file of a power above it is refused with a text of its own, before its section lengths are looked at (zkc_ptau_prepare.hip: 27)
+inline bool ptau_open(const char* path, Ptau& p, std::string& err, bool need_prepared = true, uint32_t max_power = PTAU_MAX_POWER) {
     if (!path) { err = "ptau: no path"; return false; }
     p.fd = open(path, O_RDONLY | O_CLOEXEC);
     if (p.fd < 0) { err = std::string("ptau: cannot open ") + path; return false; }
@@ -75,6 +81,7 @@ inline bool ptau_open(const char* path, Ptau& p, std::string& err) {
         if (id < 16 && !p.have[id]) { p.have[id] = true; p.off[id] = at; p.len[id] = n; }
         at += n;
     }
+    p.nsections = nsec; p.end = at;
     if (!p.have[1]) { err = "ptau: no section 1 (header)"; return false; }
     if (p.len[1] != 44) { err = "ptau: section 1 is not 44 bytes"; return false; }
     uint8_t s1[44];
@@ -83,10 +90,16 @@ inline bool ptau_open(const char* path, Ptau& p, std::string& err) {
     if (memcmp(s1 + 4, kFqP, 32) != 0) { err = "ptau: q is not BN254's"; return false; }
     p.power = rd32(s1 + 36); p.ceremonyPower = rd32(s1 + 40);
     if (p.power == 0 || p.power > PTAU_MAX_POWER) { err = "ptau: power " + std::to_string(p.power) + " outside [1, 28]"; return false; }
+    if (p.power > max_power) {
+        err = "ptau: power " + std::to_string(p.power) + " cannot be prepared or checked here: section 12's last block is a transform of size 2^" + std::to_string(p.power + 1) +
+              ", and Fr has no root of unity of order above 2^28 (the largest power is " + std::to_string(max_power) + ")";
+        return false;
+    }
     for (int id : {2, 3, 4, 5, 6}) {
         if (!p.have[id]) { err = "ptau: no section " + std::to_string(id); return false; }
         if (p.len[id] != ptau_section_points(id, p.power) * ptau_point_bytes(id)) { err = "ptau: the length of section " + std::to_string(id) + " does not match power " + std::to_string(p.power); return false; }
     }
+    if (!need_prepared) return true;
     if (!p.have[12]) { err = "ptau: no section 12: run `powersoftau prepare phase2`"; return false; }
     for (int id : {12, 13, 14, 15}) {
         if (!p.have[id]) { err = "ptau: no section " + std::to_string(id) + ": the file is only partly prepared"; return false; }

@@ -37,8 +37,11 @@
 #include "zkc_f29.h"
 #include "zkc_f29_g1.h"
 #include "zkc_f29_g2.h"
+#include "zkc_point_ops.h"
 #include "zkc_pairing.h"
+#include "zkc_file_points.h"
 #include "zkc_jds.h"
+#include "zkc_kernels.h"
 #include "zkc_phase2_parse.h"
 #include "zkc_ptau_parse.h"
 #include "zkc_setup_write.h"
@@ -47,37 +50,11 @@
 
 using namespace zkc;
 
-namespace {
-
-constexpr uint32_t SEG = 32;                     // terms per lane of the accumulation
-constexpr uint32_t RED = 32;                     // partial sums per lane of a reduction step
-constexpr uint32_t T_NEG = 0x80000000u, T_IDX = 0x7fffffffu;
-constexpr unsigned HOST_THREADS = 16;            // of the ctx = NULL path
-
-// ================================================================ device ================================================================
-
-template <int W> __device__ __forceinline__ void load_words(uint32_t* w, const uint32_t* __restrict__ p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int k = 0; k < W / 4; k++) { const uint4 v = q[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
-}
-template <int W> __device__ __forceinline__ bool all_zero(const uint32_t* w) { uint32_t o = 0;
-#pragma unroll
-    for (int k = 0; k < W; k++) o |= w[k]; return o == 0; }
-__device__ __forceinline__ Fq fq_of(const uint32_t* w) { Fq a;
-#pragma unroll
-    for (int k = 0; k < 8; k++) a.v[k] = w[k]; return a; }
-// the leading bit of the 256-bit k leaves as the return value; k moves up by one
-__device__ __forceinline__ uint32_t shl1_out(uint32_t k[8]) {
-    const uint32_t top = k[7] >> 31;
-#pragma unroll
-    for (int i = 7; i > 0; i--) k[i] = (k[i] << 1) | (k[i - 1] >> 31);
-    k[0] <<= 1;
-    return top;
-}
+namespace zkc {
 
 // ---- check: *bad (initialised to 0xffffffff) = the smallest index of a point with a coordinate >= q or off its curve; all zero is infinity and passes ----
-__global__ void __launch_bounds__(256)
+// (declared in zkc_kernels.h: zkc_ecntt.hip launches them too; Montgomery words)
+extern "C" __global__ void __launch_bounds__(256)
 zkc_ptau_check_g1(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -87,7 +64,7 @@ zkc_ptau_check_g1(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __rest
     const Fq X = fq_of(w), Y = fq_of(w + 8);
     if (!(fp_sqr(Y) == fp_sqr(X) * X + fp_from_u32<FqParams>(3))) atomicMin(bad, i);
 }
-__global__ void __launch_bounds__(256)
+extern "C" __global__ void __launch_bounds__(256)
 zkc_ptau_check_g2(const uint32_t* __restrict__ pts, uint32_t n, Fq2 twist_b, uint32_t* __restrict__ bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -98,61 +75,17 @@ zkc_ptau_check_g2(const uint32_t* __restrict__ pts, uint32_t n, Fq2 twist_b, uin
     if (!(fp_sqr(Y) == fp_sqr(X) * X + twist_b)) atomicMin(bad, i);
 }
 
-// ---- the two groups behind one interface: an accumulator in radix 2^29, set from / added to by an affine point in Montgomery words ----
-struct G1Ops {
-    static constexpr int W = 16;                                 // words of an affine point
-    typedef Fq F; typedef Acc29 Acc;
-    struct Pt { uint32_t x[9], y[9]; };
-    __device__ static __forceinline__ Pt enter(const uint32_t* w, bool neg) {
-        Pt p; Fq Y = fq_of(w + 8); if (neg) Y = fp_neg(Y);
-        f29_enter_fq(p.x, w); f29_enter_fq(p.y, Y.v);            // below 1.2 p each: well inside what f29_madd takes
-        return p;
-    }
-    __device__ static __forceinline__ void set(Acc& a, const Pt& p) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) { a.X[k] = p.x[k]; a.Y[k] = p.y[k]; a.ZZ[k] = a.ZZZ[k] = F29K<FqParams>::one.l[k]; }
-    }
-    __device__ static __forceinline__ bool madd(Acc& a, const Pt& p, bool& same_y) { return f29_madd(a, p.x, p.y, same_y); }
-    __device__ static __forceinline__ void dbl(Acc& a) { f29_acc_dbl(a); }
-    __device__ static __forceinline__ XYZZ<Fq> leave(const Acc& a) { return f29_pt_to_xyzz(a); }
-    // the reduction's own form (loose, zkc_f29_g1.h)
-    __device__ static __forceinline__ Acc from_xyzz(const XYZZ<Fq>& p) { return f29_pt_from_xyzz(p); }
-    __device__ static __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29_pt_add(r, a, b); }
-    __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29_pt_is_inf(a); }
-};
-struct G2Ops {
-    static constexpr int W = 32;
-    typedef Fq2 F; typedef Acc29G2 Acc;
-    struct Pt { F2x29 x, y; };
-    __device__ static __forceinline__ Pt enter(const uint32_t* w, bool neg) {
-        Pt p; Fq2 X{fq_of(w), fq_of(w + 8)}, Y{fq_of(w + 16), fq_of(w + 24)}; if (neg) Y = fp_neg(Y);
-        f29g2_enter(p.x, X); f29g2_enter(p.y, Y);               // carried, below 3 p per component
-        return p;
-    }
-    __device__ static __forceinline__ void set(Acc& a, const Pt& p) {
-        a.X = p.x; a.Y = p.y;
-#pragma unroll
-        for (int k = 0; k < 9; k++) { a.ZZ.c0[k] = a.ZZZ.c0[k] = F29K<FqParams>::one.l[k]; a.ZZ.c1[k] = a.ZZZ.c1[k] = 0; }
-    }
-    __device__ static __forceinline__ bool madd(Acc& a, const Pt& p, bool& same_y) { return f29g2_madd_lean(a, p.x, p.y, same_y); }
-    // f29g2_pt_dbl returns X, Y below 3 p and ZZ, ZZZ below 2.6 p, carried: inside what f29g2_madd takes (its D24 dominates carried values below 5.29 p), and
-    // f29g2_madd's results are tame, which is what f29g2_pt_dbl takes
-    __device__ static __forceinline__ void dbl(Acc& a) { Acc r; f29g2_pt_dbl(r, a); a = r; }
-    __device__ static __forceinline__ XYZZ<Fq2> leave(const Acc& a) { return f29g2_pt_to_xyzz(a); }
-    __device__ static __forceinline__ Acc from_xyzz(const XYZZ<Fq2>& p) { return f29g2_pt_from_xyzz(p); }
-    __device__ static __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29g2_pt_add(r, a, b); }
-    __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29g2_pt_is_inf(a); }
-};
+}  // namespace zkc
 
-// acc (inf: at infinity) += p, every case handled: see the head of the file
-template <class G> __device__ __forceinline__ void add_point(typename G::Acc& acc, bool& inf, const typename G::Pt& p) {
-    if (inf) { G::set(acc, p); inf = false; return; }
-    bool same_y = false;
-    if (!G::madd(acc, p, same_y)) {
-        if (same_y) G::dbl(acc);                 // acc holds p itself
-        else inf = true;                         // acc holds -p
-    }
-}
+namespace {
+
+constexpr uint32_t SEG = 32;                     // terms per lane of the accumulation
+constexpr uint32_t RED = 32;                     // partial sums per lane of a reduction step
+constexpr uint32_t T_NEG = 0x80000000u, T_IDX = 0x7fffffffu;
+
+// ================================================================ device ================================================================
+
+// load_words, all_zero, fq_of, shl1_out, the two groups behind one interface (G1Ops, G2Ops) and add_point: zkc_point_ops.h
 
 // ---- scale: out[j] = k_j * pts[src_j] as canonical XYZZ (infinity: all zero).  k_j: 8 words, standard form, 1 < k_j <= (r - 1) / 2 ----
 template <class G> __device__ __forceinline__ void scale_body(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ ks, const uint32_t* __restrict__ src,
@@ -238,17 +171,7 @@ zkc_ptau_red_g2(const XYZZ<Fq2>* __restrict__ in, const uint32_t* __restrict__ j
 
 thread_local double g_ptau_ms[6] = {0, 0, 0, 0, 0, 0};
 
-// f over [0, n) in chunks of `grain`, handed out to at most HOST_THREADS threads as they come free (the rows are sorted by length: equal shares would not be equal work)
-void par_chunks(size_t n, size_t grain, const std::function<void(size_t, size_t)>& f) {
-    unsigned nt = std::thread::hardware_concurrency(); if (nt == 0) nt = 4; if (nt > HOST_THREADS) nt = HOST_THREADS;
-    if (n <= grain || nt == 1) { if (n) f(0, n); return; }
-    std::atomic<size_t> next{0};
-    auto work = [&] { for (;;) { const size_t a = next.fetch_add(grain); if (a >= n) return; f(a, std::min(n, a + grain)); } };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-}
+// par_chunks (at most HOST_THREADS threads): zkc_host_util.h
 
 // ---- stage 2: the rows of one group ----
 struct GenTerm { uint32_t row, word; uint32_t k[8]; };          // word: the SOURCE point (and the sign) until the jobs are numbered
@@ -325,11 +248,7 @@ std::vector<std::vector<uint32_t>> reduction_steps(const Plan& P) {
 }
 
 // ---- stage 3 on host threads (zkc_curve.h), over the same plan ----
-template <class F> bool host_point_ok(const Affine<F>& a);
-template <> bool host_point_ok<Fq>(const G1Affine& a) { return fp_std_lt_p<FqParams>(a.x.v) && fp_std_lt_p<FqParams>(a.y.v) && pairing::g1_on_curve(a); }
-template <> bool host_point_ok<Fq2>(const G2Affine& a) {
-    return fp_std_lt_p<FqParams>(a.x.c0.v) && fp_std_lt_p<FqParams>(a.x.c1.v) && fp_std_lt_p<FqParams>(a.y.c0.v) && fp_std_lt_p<FqParams>(a.y.c1.v) && pairing::g2_on_curve(a);
-}
+// host_point_ok: zkc_file_points.h
 template <class F>
 void run_host(const Plan& P, std::vector<Affine<F>>& pts, std::vector<Affine<F>>& rows, uint32_t& bad, double ms[3]) {
     std::atomic<uint32_t> first_bad{0xffffffffu};

@@ -2,7 +2,8 @@
 `G1.multiExpAffine`; ts_inputs/src/example.ts:358) over device buffers.  Thin ctypes wrappers of include/zkcensus.h
 zkc_ntt_dev / zkc_g1_mul_batch_dev / zkc_msm_g1_*; used by SURVEY.md 8(d) config 5 (ii) (tools/stress.py) and its parity tests.
 g1_fixed_mul / g2_fixed_mul (include/zkcensus_setup.h) are the windowed fixed-base batch products the device key generator is built from; g1_scale
-(include/zkcensus_phase2.h) is the opposite shape, many points times one scalar, which a phase-2 contribution is made of."""
+(include/zkcensus_phase2.h) is the opposite shape, many points times one scalar, which a phase-2 contribution is made of; g1_lagrange / g2_lagrange
+(include/zkcensus_ptau_prepare.h) are the inverse transform over points that prepares a powers-of-tau file."""
 import ctypes
 
 R_MONT = 1 << 256
@@ -43,6 +44,18 @@ def g1_scale(ctx, d_points_ptr, n, k, d_out_ptr, mont=False):
     the text)."""
     kb = k.to_bytes(32, 'little') if isinstance(k, int) else bytes(k)
     ctx._check(ctx._lib.zkc_g1_scale_dev(ctx._h, d_points_ptr, n, kb, 1 if mont else 0, d_out_ptr))
+
+
+def g1_lagrange(ctx, d_points_ptr, logn, d_out_ptr, mont=False):
+    """d_out[c] = 1/n sum_i w^(-c i) d_points[i] for n = 2^logn affine G1 points (64 B, all zero = infinity), natural order on both sides: monomial powers-of-tau points
+    to the Lagrange basis of the size-n domain (include/zkcensus_ptau_prepare.h).  mont: Montgomery coordinates on both sides, as a .ptau stores them.  d_out may equal
+    d_points.  A point off the curve raises (ZKC_ERR_FORMAT, the smallest index in the text) and nothing is written."""
+    ctx._check(ctx._lib.zkc_g1_lagrange_dev(ctx._h, d_points_ptr, logn, 1 if mont else 0, d_out_ptr))
+
+
+def g2_lagrange(ctx, d_points_ptr, logn, d_out_ptr, mont=False):
+    """The same in G2: points 128 B (x.c0 | x.c1 | y.c0 | y.c1)."""
+    ctx._check(ctx._lib.zkc_g2_lagrange_dev(ctx._h, d_points_ptr, logn, 1 if mont else 0, d_out_ptr))
 
 
 def fixed_mul_window():

@@ -1,6 +1,7 @@
 """Key generation.  Test-only keys: r1cs.build() -> .r1cs -> zkc_setup_from_r1cs[_dev] -> .zkey + verification_key.json, the stand-in for `make compile`
 (circuit/circuit-compiler.sh:80-136) whose outputs are missing blobs; their toxic waste comes from a seed.  Keys nobody holds the waste of: from_ptau(), `snarkjs
-groth16 setup` from a public prepared powers-of-tau file (include/zkcensus_ptau.h), to be followed by phase2.contribute."""
+groth16 setup` from a public prepared powers-of-tau file (include/zkcensus_ptau.h), to be followed by phase2.contribute; prepare_ptau() and check_prepared() are
+`snarkjs powersoftau prepare phase2` and the check of a prepared file against its own monomial sections (include/zkcensus_ptau_prepare.h)."""
 import ctypes
 import hashlib
 import os
@@ -73,3 +74,34 @@ def ptau_stats():
     ms = (ctypes.c_double * 6)()
     _native.load().zkc_setup_ptau_stats(ms)
     return dict(zip(['read_parse', 'transpose', 'upload', 'scale', 'accumulate_reduce', 'checks_write'], list(ms)))
+
+
+def prepare_ptau(src, dst, ctx=None):
+    """`snarkjs powersoftau prepare phase2 src dst`: dst = src's sections as they are, then the Lagrange sections 12 .. 15 (include/zkcensus_ptau_prepare.h, which also says
+    what the top block of section 12 holds).  With a Context the transforms over the file's points run on its GPU, without one on host threads; the bytes are the same.
+    Raises ZkcError with the refusal's text for a file that does not parse, is already prepared, holds a bad point or does not fit the device; nothing is left at dst then."""
+    err = ctypes.create_string_buffer(512)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_ptau_prepare(None if ctx is None else ctx._h, os.fsencode(src), os.fsencode(dst), err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    return dst
+
+
+def check_prepared(ptau, ctx=None):
+    """Are sections 12 .. 15 of a prepared file the transforms of its sections 2 .. 5?  -> (ok, section, index, reason): the first point that differs, in the order 12, 13,
+    14, 15 and then by index in the section (0, 0, '' when ok).  Raises ZkcError for a file that does not parse, is not prepared or holds a bad monomial point."""
+    err = ctypes.create_string_buffer(512)
+    sec, idx = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_ptau_check_prepared(None if ctx is None else ctx._h, os.fsencode(ptau), ctypes.byref(sec), ctypes.byref(idx), err, 512)
+    if rc < 0:
+        raise _native.ZkcError(-rc, err.value.decode())
+    return rc == 1, sec.value, idx.value, err.value.decode()
+
+
+def ptau_prepare_stats():
+    """Milliseconds of the calling thread's last prepare_ptau or check_prepared, by stage."""
+    ms = (ctypes.c_double * 6)()
+    _native.load().zkc_ptau_prepare_stats(ms)
+    return dict(zip(['read', 'upload_check', 'transforms_g1', 'transforms_g2', 'affine_download', 'write_or_compare'], list(ms)))
