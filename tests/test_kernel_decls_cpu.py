@@ -45,6 +45,9 @@ def test_host_helpers_are_defined_once_and_declared_in_headers():
     assert [f for f, _ in definitions(r'\bdouble\s+ms_\w+' + body)] == ['zkc_host_util.h']
     assert [f for f, _ in definitions(r'duration\s*<\s*double\s*,\s*std::milli\s*>')] == ['zkc_host_util.h']
     assert [f for f, _ in definitions(r'0xd992f6edu')] == ['zkc_host_util.h']       # first word of the G2 generator
+    # the check of the points of a file: one device entry and one host-thread loop, whichever file of kernels asks
+    assert [f for f, _ in definitions(r'\bpoints_check_dev' + body)] == ['zkc_fixedbase_dev.hip']
+    assert [f for f, _ in definitions(r'\bhost_first_bad' + body)] == ['zkc_file_points.h']
     # body-less declarations of cross-file functions: in headers only
     # a type, then the name, a parameter list and a semicolon (a call has no type in front of it)
     for name in ('zkc_lane_streams', 'zkc_get_template', 'zkc_witness_chunk_async', 'zkc_ctx_lanes_destroy', 'zkc_pairing_bin'):

@@ -25,7 +25,7 @@ DBL_PRODUCTS, MADD_PRODUCTS = 9, 10          # f29_acc_dbl and f29_madd (csrc/zk
 
 
 def naf_chain(k):
-    """the addition chain zkc_p2_scale_g1 walks for the scalar k: doublings (the index of the leading digit) and mixed additions (non-zero digits below it)"""
+    """the addition chain zkc_p2_scale_g1 walks for the scalar k (G1Ops::dbl and add_point, csrc/zkc_point_ops.h): doublings (the index of the leading digit) and mixed additions (non-zero digits below it)"""
     top, nz, j = -1, 0, 0
     while k:
         if k & 1:

@@ -1,4 +1,4 @@
-// host check of the addition chain of zkc_p2_scale_g1 (csrc/zkc_phase2.hip): f29_acc_dbl and f29_madd alternating on one accumulator along the non-adjacent form of a
+// host check of the addition chain of zkc_p2_scale_g1 (csrc/zkc_phase2.hip, through G1Ops::dbl and add_point of zkc_point_ops.h): f29_acc_dbl and f29_madd alternating on one accumulator along the non-adjacent form of a
 // scalar, against xyzz_mul of zkc_curve.h on points of the curve.  Also records the largest top limb each accumulator coordinate reaches, against the invariant the two
 // formulas state (X, Y < 10.5 p; ZZ, ZZZ < 4 p).  The recoding below restates the library's (digit = 2 - (k mod 4) for odd k).
 #include <array>

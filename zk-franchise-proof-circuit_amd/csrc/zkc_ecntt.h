@@ -13,16 +13,12 @@ constexpr uint32_t ECNTT_MAX_LOGN = 28;            // the two-adicity of r - 1: 
 // ECNTT_MAX_LOGN, anything else is ZKC_ERR_BAD_ARG.  Free with hipFree.
 int ecntt_twiddles(zkc_ctx* ctx, uint32_t logn, Fr** d_tw);
 
-// d_out[c] = 1/n sum_i w^(-c i) d_pts[i] for the n = 2^logn affine points at d_pts (Montgomery words, all zero = infinity, ALREADY CHECKED: zkc_ptau_check_*), natural
-// order on both sides, affine again (out_mont: Montgomery words).  d_tw: ecntt_twiddles of tw_logn >= logn (may be NULL when logn < 2).  d_out may be d_pts.  Launches on
-// ctx->stream, has synchronised and freed its work space on return; the context's lock is held by the caller.  ms (may be NULL): += [0] the transform, [1] to affine.
-int ecntt_g1(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms);
-int ecntt_g2(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms);
+// d_out[c] = 1/n sum_i w^(-c i) d_pts[i] for the n = 2^logn affine points at d_pts (F = Fq: G1, Fq2: G2; Montgomery words, all zero = infinity, ALREADY CHECKED:
+// points_check_dev, zkc_fixedbase_dev.h), natural order on both sides, affine again (out_mont: Montgomery words).  d_tw: ecntt_twiddles of tw_logn >= logn (may be NULL when
+// logn < 2).  d_out may be d_pts.  Launches on ctx->stream, has synchronised and freed its work space on return; the context's lock is held by the caller.  ms (may be NULL):
+// += [0] the transform, [1] to affine.
+template <class F> int ecntt(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms);
 // the device bytes one call needs beside d_pts and d_out
 inline size_t ecntt_work_bytes(uint32_t logn, bool g2) { return ((size_t)1 << logn) * (g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ)) * 2; }
-
-// *bad = the smallest index of a point of d_pts (n points, Montgomery words) with a coordinate >= q or off its curve, 0xffffffff when there is none
-int ecntt_check_g1(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad);
-int ecntt_check_g2(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad);
 
 }  // namespace zkc

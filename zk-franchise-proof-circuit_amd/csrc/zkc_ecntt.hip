@@ -12,7 +12,7 @@
 //           appears: k < half.)  Otherwise t Q is double-and-add from the scalar's leading bit with the COMPLETE doubling and addition (G::pt_dbl, G::add): after the
 //           load no operand is affine.  The two additions of the butterfly are complete as well: with tau on a domain the monomial points repeat, and P + t Q meets equal
 //           points, opposite points and infinity (zkc_point_ops.h).
-//   affine  the batched inversion of the fixed-base engine (fixed_affine_g1 / _g2): the bytes are canonical, so host and device compare byte for byte.
+//   affine  the batched inversion of the fixed-base engine (fixed_affine<F>): the bytes are canonical, so host and device compare byte for byte.
 // There is no workgroup-resident group of stages and no tile: no constant here sets how many stages or points a workgroup handles (the tests' T), every launch is
 // (n / 2 + 63) / 64 workgroups of one wave.  A product is ~254 doublings and ~127 additions of ~9 and ~14 field products on ONE lane, so a stage moves 256 (G2: 512) bytes
 // per butterfly against some 4 000 (G2: 12 000) field products: the kernel is bound by the vector units, not by the trips through global memory that separate launches
@@ -23,7 +23,6 @@
 #include "zkc_fixedbase_dev.h"
 #include "zkc_host_util.h"
 #include "zkc_point_ops.h"
-#include "zkc_pairing.h"
 #include "zkc_kernels.h"
 #include "zkc_ecntt.h"
 #include "../../include/zkcensus_ptau_prepare.h"
@@ -50,7 +49,8 @@ zkc_ecntt_to_mont(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, s
 }
 
 // ---- load: work[bitrev(i)] = s * pts[i] as canonical XYZZ (infinity: all zero); s != 0 ----
-template <class G> __device__ __forceinline__ void load_body(const uint32_t* __restrict__ pts, uint32_t logn, const EcScalar& s, XYZZ<typename G::F>* __restrict__ work) {
+template <class G> __global__ void __launch_bounds__(64)
+zkc_ecntt_load(const uint32_t* __restrict__ pts, uint32_t logn, EcScalar s, XYZZ<typename G::F>* __restrict__ work) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (1u << logn)) return;
     uint32_t w[G::W]; load_words<G::W>(w, pts + (size_t)G::W * i);
@@ -67,12 +67,9 @@ template <class G> __device__ __forceinline__ void load_body(const uint32_t* __r
     }
     work[at] = o;
 }
-__global__ void __launch_bounds__(64)
-zkc_ecntt_load_g1(const uint32_t* __restrict__ pts, uint32_t logn, EcScalar s, XYZZ<Fq>* __restrict__ work) { load_body<G1Ops>(pts, logn, s, work); }
-__global__ void __launch_bounds__(64)
-zkc_ecntt_load_g2(const uint32_t* __restrict__ pts, uint32_t logn, EcScalar s, XYZZ<Fq2>* __restrict__ work) { load_body<G2Ops>(pts, logn, s, work); }
 
 // ---- one stage: see the head of the file.  tw_shift = tw_logn - 1 - s: the stride of this stage's twiddles in the table ----
+// The kernel below only hands its arguments to this body: written in the kernel itself the G2 stage was measured at 1232 bytes of scratch per lane, in this form at 1200.
 template <class G> __device__ __forceinline__ void stage_body(XYZZ<typename G::F>* __restrict__ work, uint32_t logn, uint32_t s, const Fr* __restrict__ tw, uint32_t tw_shift) {
     typedef XYZZ<typename G::F> X;
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,75 +98,17 @@ template <class G> __device__ __forceinline__ void stage_body(XYZZ<typename G::F
     G::add(r, p, q);
     work[b] = G::is_inf(r) ? X::inf() : G::leave(r);
 }
-__global__ void __launch_bounds__(64)
-zkc_ecntt_stage_g1(XYZZ<Fq>* __restrict__ work, uint32_t logn, uint32_t s, const Fr* __restrict__ tw, uint32_t tw_shift) { stage_body<G1Ops>(work, logn, s, tw, tw_shift); }
-__global__ void __launch_bounds__(64)
-zkc_ecntt_stage_g2(XYZZ<Fq2>* __restrict__ work, uint32_t logn, uint32_t s, const Fr* __restrict__ tw, uint32_t tw_shift) { stage_body<G2Ops>(work, logn, s, tw, tw_shift); }
+
+template <class G> __global__ void __launch_bounds__(64)
+zkc_ecntt_stage(XYZZ<typename G::F>* __restrict__ work, uint32_t logn, uint32_t s, const Fr* __restrict__ tw, uint32_t tw_shift) { stage_body<G>(work, logn, s, tw, tw_shift); }
 
 // ================================================================ host ================================================================
-
-template <class F> struct DevE;
-template <> struct DevE<Fq> {
-    static constexpr const char* name = "zkc_g1_lagrange_dev";
-    static void check(zkc_ctx* ctx, const uint32_t* pts, uint32_t n, uint32_t* bad) { hipLaunchKernelGGL(zkc_ptau_check_g1, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pts, n, bad); }
-    static void load(zkc_ctx* ctx, const uint32_t* pts, uint32_t logn, const EcScalar& s, XYZZ<Fq>* work) {
-        hipLaunchKernelGGL(zkc_ecntt_load_g1, dim3(((1u << logn) + 63) / 64), dim3(64), 0, ctx->stream, pts, logn, s, work); }
-    static void stage(zkc_ctx* ctx, XYZZ<Fq>* work, uint32_t logn, uint32_t s, const Fr* tw, uint32_t sh) {
-        hipLaunchKernelGGL(zkc_ecntt_stage_g1, dim3(((1u << (logn - 1)) + 63) / 64), dim3(64), 0, ctx->stream, work, logn, s, tw, sh); }
-    static int affine(zkc_ctx* ctx, const XYZZ<Fq>* in, uint32_t n, void* out, bool mont) { return fixed_affine_g1(ctx, in, n, out, mont); }
-};
-template <> struct DevE<Fq2> {
-    static constexpr const char* name = "zkc_g2_lagrange_dev";
-    static void check(zkc_ctx* ctx, const uint32_t* pts, uint32_t n, uint32_t* bad) {
-        hipLaunchKernelGGL(zkc_ptau_check_g2, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pts, n, pairing::consts().twist_b, bad); }
-    static void load(zkc_ctx* ctx, const uint32_t* pts, uint32_t logn, const EcScalar& s, XYZZ<Fq2>* work) {
-        hipLaunchKernelGGL(zkc_ecntt_load_g2, dim3(((1u << logn) + 63) / 64), dim3(64), 0, ctx->stream, pts, logn, s, work); }
-    static void stage(zkc_ctx* ctx, XYZZ<Fq2>* work, uint32_t logn, uint32_t s, const Fr* tw, uint32_t sh) {
-        hipLaunchKernelGGL(zkc_ecntt_stage_g2, dim3(((1u << (logn - 1)) + 63) / 64), dim3(64), 0, ctx->stream, work, logn, s, tw, sh); }
-    static int affine(zkc_ctx* ctx, const XYZZ<Fq2>* in, uint32_t n, void* out, bool mont) { return fixed_affine_g2(ctx, in, n, out, mont); }
-};
-
-template <class F>
-int check_dev(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad) {
-    DevBuf flag; int rc;
-    if ((rc = flag.alloc(ctx, 4))) return rc;
-    ZKC_HIP_CHECK(ctx, hipMemsetAsync(flag.p, 0xff, 4, ctx->stream));
-    DevE<F>::check(ctx, (const uint32_t*)d_pts, n, flag.as<uint32_t>());
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(bad, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return ZKC_OK;
-}
-
-template <class F>
-int run_dev(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms) {
-    typedef DevE<F> K;
-    if (logn > ECNTT_MAX_LOGN || (logn >= 2 && (!d_tw || tw_logn < logn))) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "ecntt: bad size or twiddle table");
-    const uint32_t n = 1u << logn;
-    EcScalar s{}; s.top = 0;
-    fp_to_std<FrParams>(s.k, fp_inv<FrParams>(fp_from_u32<FrParams>(n)));
-    for (int i = 255; i >= 0; i--) if ((s.k[i >> 5] >> (i & 31)) & 1u) { s.top = i; break; }
-    DevBuf work; int rc;
-    if ((rc = work.alloc(ctx, (size_t)n * sizeof(XYZZ<F>)))) return rc;
-    const clk::time_point t0 = clk::now();
-    K::load(ctx, (const uint32_t*)d_pts, logn, s, work.as<XYZZ<F>>());
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    for (uint32_t st = 0; st < logn; st++) {
-        K::stage(ctx, work.as<XYZZ<F>>(), logn, st, d_tw, st ? tw_logn - 1 - st : 0);      // stage 0 reads no twiddle
-        ZKC_HIP_CHECK(ctx, hipGetLastError());
-    }
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const clk::time_point t1 = clk::now();
-    rc = K::affine(ctx, work.as<XYZZ<F>>(), n, d_out, out_mont);      // synchronises
-    if (ms) { ms[0] += ms_since(t0, t1); ms[1] += ms_since(t1); }
-    return rc;
-}
 
 // the body of the two public calls
 template <class F>
 int lagrange_entry(zkc_ctx* ctx, const void* d_points, uint32_t logn, int mont, void* d_out) {
-    typedef DevE<F> K;
-    if (!ctx || !d_points || !d_out || logn > ECNTT_MAX_LOGN) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, std::string(K::name) + ": bad argument");
+    const std::string name = GroupOf<F>::lagrange_dev;
+    if (!ctx || !d_points || !d_out || logn > ECNTT_MAX_LOGN) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, name + ": bad argument");
     ZKC_LOCK(ctx);
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t n = 1u << logn; constexpr size_t PT = sizeof(Affine<F>);
@@ -183,10 +122,10 @@ int lagrange_entry(zkc_ctx* ctx, const void* d_points, uint32_t logn, int mont, 
         src = conv.p;
     }
     uint32_t bad = 0;
-    if ((rc = check_dev<F>(ctx, src, n, &bad))) return rc;
-    if (bad != 0xffffffffu) return zkc_fail(ctx, ZKC_ERR_FORMAT, std::string(K::name) + ": point " + std::to_string(bad) + " has a coordinate >= q or is not on the curve");
+    if ((rc = points_check_dev<F>(ctx, src, n, &bad))) return rc;
+    if (bad != 0xffffffffu) return zkc_fail(ctx, ZKC_ERR_FORMAT, name + ": point " + std::to_string(bad) + " has a coordinate >= q or is not on the curve");
     if (logn >= 2 && (rc = ecntt_twiddles(ctx, logn, (Fr**)&tw.p))) return rc;
-    return run_dev<F>(ctx, src, logn, tw.as<Fr>(), logn, d_out, mont != 0, nullptr);
+    return ecntt<F>(ctx, src, logn, tw.as<Fr>(), logn, d_out, mont != 0, nullptr);
 }
 
 }  // namespace
@@ -201,12 +140,32 @@ int ecntt_twiddles(zkc_ctx* ctx, uint32_t logn, Fr** d_tw) {
     *d_tw = t.inv;
     return ZKC_OK;
 }
-int ecntt_g1(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms) {
-    return run_dev<Fq>(ctx, d_pts, logn, d_tw, tw_logn, d_out, out_mont, ms); }
-int ecntt_g2(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms) {
-    return run_dev<Fq2>(ctx, d_pts, logn, d_tw, tw_logn, d_out, out_mont, ms); }
-int ecntt_check_g1(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad) { return check_dev<Fq>(ctx, d_pts, n, bad); }
-int ecntt_check_g2(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad) { return check_dev<Fq2>(ctx, d_pts, n, bad); }
+
+template <class F>
+int ecntt(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms) {
+    typedef typename GroupOf<F>::Ops G;
+    if (logn > ECNTT_MAX_LOGN || (logn >= 2 && (!d_tw || tw_logn < logn))) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "ecntt: bad size or twiddle table");
+    const uint32_t n = 1u << logn;
+    EcScalar s{}; s.top = 0;
+    fp_to_std<FrParams>(s.k, fp_inv<FrParams>(fp_from_u32<FrParams>(n)));
+    for (int i = 255; i >= 0; i--) if ((s.k[i >> 5] >> (i & 31)) & 1u) { s.top = i; break; }
+    DevBuf work; int rc;
+    if ((rc = work.alloc(ctx, (size_t)n * sizeof(XYZZ<F>)))) return rc;
+    const clk::time_point t0 = clk::now();
+    hipLaunchKernelGGL(zkc_ecntt_load<G>, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, (const uint32_t*)d_pts, logn, s, work.as<XYZZ<F>>());
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    for (uint32_t st = 0; st < logn; st++) {
+        hipLaunchKernelGGL(zkc_ecntt_stage<G>, dim3((n / 2 + 63) / 64), dim3(64), 0, ctx->stream, work.as<XYZZ<F>>(), logn, st, d_tw, st ? tw_logn - 1 - st : 0);      // stage 0 reads no twiddle
+        ZKC_HIP_CHECK(ctx, hipGetLastError());
+    }
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    const clk::time_point t1 = clk::now();
+    rc = fixed_affine<F>(ctx, work.as<XYZZ<F>>(), n, d_out, out_mont);      // synchronises
+    if (ms) { ms[0] += ms_since(t0, t1); ms[1] += ms_since(t1); }
+    return rc;
+}
+template int ecntt<Fq>(zkc_ctx*, const void*, uint32_t, const Fr*, uint32_t, void*, bool, double*);
+template int ecntt<Fq2>(zkc_ctx*, const void*, uint32_t, const Fr*, uint32_t, void*, bool, double*);
 
 }  // namespace zkc
 

@@ -1,5 +1,7 @@
-// zkc_fixedbase_dev.h -- host-side interface of the device fixed-base batch products (zkc_fixedbase_dev.hip), for the files that build on them (zkc_setup.hip).
-// The kernels themselves are launched only from their own file, so zkc_kernels.h does not list them.
+// zkc_fixedbase_dev.h -- host-side interface of the device fixed-base batch products (zkc_fixedbase_dev.hip), for the files that build on them (zkc_setup.hip), and of
+// the two steps that every file of kernels over the points of a file shares (zkc_phase2.hip, zkc_setup_ptau.hip, zkc_ecntt.hip, zkc_ptau_prepare.hip): the check of the
+// points read (points_check_dev) and the way back from XYZZ sums to affine points (fixed_affine).  The kernels themselves are launched only from their own file, so
+// zkc_kernels.h does not list them.
 #pragma once
 #include "zkc_internal.h"
 #include "zkc_curve.h"
@@ -22,10 +24,14 @@ int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, dou
 int fixed_mul_g1(zkc_ctx* ctx, const G1Affine* d_table, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont);
 int fixed_mul_g2(zkc_ctx* ctx, const uint32_t* d_table29, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont);
 
-// The second half of a batch product on its own, for other kernels that leave XYZZ sums (zkc_phase2.hip, zkc_setup_ptau.hip): d_in (n points on the device, infinity = ZZ
-// zero) -> d_out (n x 64 B affine, G2: n x 128 B; all zero = infinity; d_out may alias whatever d_in was computed from) through the batched inversion of zkc_fixed_affine.  Launches on ctx->stream,
-// synchronises and frees its work space before it returns; the context's lock is held by the caller.
-int fixed_affine_g1(zkc_ctx* ctx, const G1XYZZ* d_in, uint32_t n, void* d_out, bool out_mont);
-int fixed_affine_g2(zkc_ctx* ctx, const G2XYZZ* d_in, uint32_t n, void* d_out, bool out_mont);
+// The second half of a batch product on its own, for other kernels that leave XYZZ sums (zkc_phase2.hip, zkc_setup_ptau.hip, zkc_ecntt.hip): d_in (n points on the device,
+// infinity = ZZ zero) -> d_out (n x 64 B affine, G2: n x 128 B; all zero = infinity; d_out may alias whatever d_in was computed from) through the batched inversion of
+// zkc_fixed_affine<F>.  F = Fq or Fq2.  Launches on ctx->stream, synchronises and frees its work space before it returns; the context's lock is held by the caller.
+template <class F> int fixed_affine(zkc_ctx* ctx, const XYZZ<F>* d_in, uint32_t n, void* d_out, bool out_mont);
+
+// *bad = the smallest index of a point of d_pts (n affine points on the device, Montgomery words, F = Fq: G1, Fq2: G2) with a coordinate >= q or off its curve, 0xffffffff
+// when there is none; all zero is infinity and passes (the device side of host_point_ok, zkc_file_points.h).  Launches on ctx->stream and has synchronised on return; the
+// context's lock is held by the caller.
+template <class F> int points_check_dev(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad);
 
 }  // namespace zkc

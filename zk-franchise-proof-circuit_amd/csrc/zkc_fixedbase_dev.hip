@@ -7,6 +7,8 @@
 //   zkc_fixed_acc_g1 / _g2   one lane per scalar: walk the digits from the lowest window up, gather T[j][d - 1], add; the sum leaves as a canonical XYZZ point
 //   zkc_fixed_affine<F>      XYZZ -> affine without an inversion per point: a lane takes FIXED_INV_CHUNK points (strided, so that the lanes of a wave read neighbours),
 //                            multiplies their ZZZ up (Montgomery's trick), inverts the product once and walks back: 3 products per point plus 1 / 8 of an inversion
+//   zkc_points_check<G>      not part of a product: one lane per affine point of a file, coordinates < q and on the curve (zkc_point_ops.h).  It is here because this
+//                            file is what every user of it already builds on, for zkc_fixed_affine
 // The tables live in global memory (G1: 8160 x 64 B = 510 KB; G2: 8160 x 240 B = 1.9 MB in the row format of zkc_g2_table29) and are built on the host.
 #include <cstring>
 #include <string>
@@ -18,6 +20,7 @@
 #include "zkc_f29_g1.h"
 #include "zkc_f29_g2.h"
 #include "zkc_host_util.h"
+#include "zkc_point_ops.h"
 #include "zkc_pairing.h"
 #include "../../include/zkcensus_setup.h"
 
@@ -159,6 +162,17 @@ zkc_fixed_affine(const XYZZ<F>* __restrict__ in, F* __restrict__ pre, uint32_t n
     }
 }
 
+// *bad (initialised to 0xffffffff) = the smallest index of a point with a coordinate >= q or off its curve y^2 = x^3 + b; all zero is infinity and passes.  Montgomery words
+template <class G>
+__global__ void __launch_bounds__(256)
+zkc_points_check(const uint32_t* __restrict__ pts, uint32_t n, typename G::F b, uint32_t* __restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[G::W]; load_words<G::W>(w, pts + (size_t)G::W * i);
+    if (all_zero<G::W>(w)) return;
+    if (!coords_below_q<G>(w) || !on_curve<G>(w, b)) atomicMin(bad, i);
+}
+
 // the second launch of a batch: d_sum (n XYZZ points) -> d_out (n affine points), d_pre = n x F of work space; enqueued on ctx->stream, not waited for
 template <class F>
 hipError_t launch_affine(zkc_ctx* ctx, const XYZZ<F>* d_sum, F* d_pre, uint32_t n, bool out_mont, void* d_out) {
@@ -207,23 +221,33 @@ int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, dou
     return msm_g2_rows29(ctx, tmp.as<G2Affine>(), fb.tab.size(), "fixed_table_g2", d_table29);      // the row format of the G2 MSM, made by its kernel
 }
 
-int fixed_affine_g1(zkc_ctx* ctx, const G1XYZZ* d_in, uint32_t n, void* d_out, bool out_mont) {
+template <class F>
+int fixed_affine(zkc_ctx* ctx, const XYZZ<F>* d_in, uint32_t n, void* d_out, bool out_mont) {
     DevBuf pre; int rc;
-    if ((rc = pre.alloc(ctx, (size_t)n * sizeof(Fq)))) return rc;
-    hipError_t e = launch_affine<Fq>(ctx, d_in, pre.as<Fq>(), n, out_mont, d_out);
+    if ((rc = pre.alloc(ctx, (size_t)n * sizeof(F)))) return rc;
+    hipError_t e = launch_affine<F>(ctx, d_in, pre.as<F>(), n, out_mont, d_out);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_affine_g1: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string(GroupOf<F>::g2 ? "fixed_affine<Fq2>: " : "fixed_affine<Fq>: ") + hipGetErrorString(e));
     return ZKC_OK;
 }
+template int fixed_affine<Fq>(zkc_ctx*, const XYZZ<Fq>*, uint32_t, void*, bool);
+template int fixed_affine<Fq2>(zkc_ctx*, const XYZZ<Fq2>*, uint32_t, void*, bool);
 
-int fixed_affine_g2(zkc_ctx* ctx, const G2XYZZ* d_in, uint32_t n, void* d_out, bool out_mont) {
-    DevBuf pre; int rc;
-    if ((rc = pre.alloc(ctx, (size_t)n * sizeof(Fq2)))) return rc;
-    hipError_t e = launch_affine<Fq2>(ctx, d_in, pre.as<Fq2>(), n, out_mont, d_out);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("fixed_affine_g2: ") + hipGetErrorString(e));
+template <class F>
+int points_check_dev(zkc_ctx* ctx, const void* d_pts, uint32_t n, uint32_t* bad) {
+    F b;
+    if constexpr (GroupOf<F>::g2) b = pairing::consts().twist_b; else b = fp_from_u32<FqParams>(3);
+    DevBuf flag; int rc;
+    if ((rc = flag.alloc(ctx, 4))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(flag.p, 0xff, 4, ctx->stream));
+    hipLaunchKernelGGL(zkc_points_check<typename GroupOf<F>::Ops>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)d_pts, n, b, flag.as<uint32_t>());
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(bad, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKC_OK;
 }
+template int points_check_dev<Fq>(zkc_ctx*, const void*, uint32_t, uint32_t*);
+template int points_check_dev<Fq2>(zkc_ctx*, const void*, uint32_t, uint32_t*);
 
 int fixed_mul_g1(zkc_ctx* ctx, const G1Affine* d_table, const void* d_scalars, bool scalars_mont, uint32_t n, void* d_out, bool out_mont) {
     return fixed_mul<Fq>(ctx, "fixed_mul_g1", n, d_out, out_mont, [&](XYZZ<Fq>* d_sum) {

@@ -1,4 +1,4 @@
-// zkc_host_util.h -- host-side helpers with no other home, once each: the roots of unity of Fr, the generators, points as files and the C ABI carry them, an error text
+// zkc_host_util.h -- host-side helpers with no other home, once each: the roots of unity of Fr, the generators, points as files and the C ABI carry them, the order of 256-bit integers, an error text
 // into a caller's buffer, a millisecond timer, a loop over host threads.  Host only (nothing here is ZKC_HD), internal to the library.
 #pragma once
 #include <chrono>
@@ -57,6 +57,9 @@ inline void unc_g2(uint8_t o[128], const G2Affine& a) {
     if (a.is_inf()) { memset(o, 0, 128); o[0] = 0x40; return; }
     be_fq(o, a.x.c1); be_fq(o + 32, a.x.c0); be_fq(o + 64, a.y.c1); be_fq(o + 96, a.y.c0);
 }
+
+// a < b for two 256-bit integers of eight words, lowest first (standard form)
+inline bool std_less(const uint32_t a[8], const uint32_t b[8]) { for (int i = 7; i >= 0; i--) if (a[i] != b[i]) return a[i] < b[i]; return false; }
 
 // the text of an error into the caller's buffer (either may be absent); returns code
 inline int err_out(char* err, size_t errlen, int code, const std::string& m) { if (err && errlen) snprintf(err, errlen, "%s", m.c_str()); return code; }

@@ -66,8 +66,4 @@ extern "C" __global__ void zkc_r1cs_range(const Fr* wtns_std, size_t wtns_stride
 extern "C" __global__ void zkc_r1cs_check_rows(const uint4* rows, const uint32_t* jdptr, const uint32_t* col, const Fr* val, const Fr* wtns_std, size_t wtns_stride,
                                                const Fr* wm_all, size_t wm_stride, uint32_t nCons, uint32_t nlong, uint32_t* first, uint32_t* count, const uint32_t* flag);
 
-// ---- zkc_setup_ptau.hip: the points of a file checked (launched from zkc_ecntt.hip too).  Montgomery words; *bad starts as 0xffffffff and ends as the smallest bad index ----
-extern "C" __global__ void zkc_ptau_check_g1(const uint32_t* pts, uint32_t n, uint32_t* bad);
-extern "C" __global__ void zkc_ptau_check_g2(const uint32_t* pts, uint32_t n, Fq2 twist_b, uint32_t* bad);
-
 }  // namespace zkc

@@ -6,7 +6,8 @@
 // form (digits -1, 0, +1, no two neighbours non-zero, one in three non-zero on average) and reaches the kernel as two 256-bit masks in the launch arguments: the digits
 // are wave-uniform, so is every branch on them, and no lane extracts a digit.  From the leading digit down: f29_acc_dbl on the accumulator, and on a non-zero digit the
 // mixed addition f29_madd of +P_i or -P_i (negating an affine point is free: -y is computed once per lane).  No per-lane table: accumulator 36 registers, the point 27
-// (x, y, -y).  Results leave as canonical XYZZ and become affine through the batched inversion of the fixed-base products (fixed_affine_g1).
+// (x, y, -y).  Results leave as canonical XYZZ and become affine through the batched inversion of the fixed-base products (fixed_affine<Fq>).  The point check, the
+// accumulator and the handling of the addition's exceptional cases are those of every kernel over the points of a file: zkc_point_ops.h.
 //
 // Why the incomplete addition is enough, and where it is not.  Write the recoding of k (0 < k < r) as digits d_t .. d_0 with d_t = +1, and m_j = sum_{i >= j} d_i 2^(i - j)
 // for its prefixes: m_t = 1, m_0 = k, and |k - m_j 2^j| < 2^(j + 1) / 3 (a tail of a non-adjacent form is below two thirds of its leading power), so 0 < m_j < k / 2^j + 1.
@@ -25,6 +26,7 @@
 #include "zkc_fixedbase_dev.h"
 #include "zkc_f29.h"
 #include "zkc_f29_g1.h"
+#include "zkc_point_ops.h"
 #include "zkc_verify_host.h"
 #include "zkc_phase2_parse.h"
 #include "../../include/zkcensus_phase2.h"
@@ -36,54 +38,44 @@ namespace {
 // the non-adjacent form of the scalar: bit j of pos / neg = digit j is +1 / -1; top = the index of the leading digit (+1 for a positive scalar)
 struct ScaleDigits { uint32_t pos[8], neg[8]; int top; };
 
-__device__ __forceinline__ void load_point(uint32_t x[8], uint32_t y[8], const uint32_t* __restrict__ pts, uint32_t i) {
-    const uint4* q = reinterpret_cast<const uint4*>(pts + 16 * (size_t)i);
-    const uint4 a = q[0], b = q[1], c = q[2], e = q[3];
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-    y[0] = c.x; y[1] = c.y; y[2] = c.z; y[3] = c.w; y[4] = e.x; y[5] = e.y; y[6] = e.z; y[7] = e.w;
-}
-
-// out[i] = k * pts[i] as canonical XYZZ (infinity: all zero).  *bad (initialised to 0xffffffff) = the smallest index of a point with a coordinate >= q or off the curve.
+// out[i] = k * pts[i] as canonical XYZZ (infinity: all zero).  *bad (initialised to 0xffffffff) = the smallest index of a point with a coordinate >= q or off the curve: the
+// check of zkc_point_ops.h, fused here so that a contribution makes one pass over its points.
 __global__ void __launch_bounds__(64)
 zkc_p2_scale_g1(const uint32_t* __restrict__ pts, uint32_t n, ScaleDigits d, int mont, XYZZ<Fq>* __restrict__ out, uint32_t* __restrict__ bad) {
+    typedef G1Ops G;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint32_t xs[8], ys[8]; load_point(xs, ys, pts, i);
-    uint32_t any = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) any |= xs[k] | ys[k];
+    uint32_t w[16]; load_words<16>(w, pts + 16 * (size_t)i);
     XYZZ<Fq> o = XYZZ<Fq>::inf();
-    if (!any) { out[i] = o; return; }
-    if (!fp_std_lt_p<FqParams>(xs) || !fp_std_lt_p<FqParams>(ys)) { atomicMin(bad, i); out[i] = o; return; }
-    Fq X, Y;
-    if (mont) {
+    if (all_zero<16>(w)) { out[i] = o; return; }
+    if (!coords_below_q<G>(w)) { atomicMin(bad, i); out[i] = o; return; }
+    if (!mont) {
+        const Fq X = fp_from_std<FqParams>(w), Y = fp_from_std<FqParams>(w + 8);
 #pragma unroll
-        for (int k = 0; k < 8; k++) { X.v[k] = xs[k]; Y.v[k] = ys[k]; }
-    } else { X = fp_from_std<FqParams>(xs); Y = fp_from_std<FqParams>(ys); }
-    if (!(fp_sqr(Y) == fp_sqr(X) * X + fp_from_u32<FqParams>(3))) { atomicMin(bad, i); out[i] = o; return; }
-    const Fq nY = fp_neg(Y);
-    uint32_t px[9], py[9], pny[9];
-    f29_enter_fq(px, X.v); f29_enter_fq(py, Y.v); f29_enter_fq(pny, nY.v);          // below 1.2 p each: well inside what f29_madd takes (below 32 p)
-    Acc29 acc;
+        for (int k = 0; k < 8; k++) { w[k] = X.v[k]; w[8 + k] = Y.v[k]; }
+    }
+    if (!on_curve<G>(w, fp_from_u32<FqParams>(3))) { atomicMin(bad, i); out[i] = o; return; }
+    // x is entered once and y twice, as y and -y (below 1.2 p each: well inside what f29_madd takes, below 32 p), and the digit picks between the two.  Not G::enter for
+    // P and again for -P: that form takes 245 registers and leaves two waves per SIMD where this one leaves three
+    const Fq nY = fp_neg(fq_of(w + 8));
+    G::Pt p; uint32_t py[9], pny[9];
+    f29_enter_fq(p.x, w); f29_enter_fq(py, w + 8); f29_enter_fq(pny, nY.v);
 #pragma unroll
-    for (int k = 0; k < 9; k++) { acc.X[k] = px[k]; acc.Y[k] = py[k]; acc.ZZ[k] = acc.ZZZ[k] = F29K<FqParams>::one.l[k]; }
+    for (int k = 0; k < 9; k++) p.y[k] = py[k];
+    G::Acc acc; G::set(acc, p);
     bool inf = false;
     for (int j = d.top - 1; j >= 0; j--) {
-        f29_acc_dbl(acc);
+        G::dbl(acc);
         const uint32_t sh = (uint32_t)j & 31u;
         const bool plus = (d.pos[j >> 5] >> sh) & 1u, minus = (d.neg[j >> 5] >> sh) & 1u;      // wave-uniform
         if (plus | minus) {
-            uint32_t ya[9];
 #pragma unroll
-            for (int k = 0; k < 9; k++) ya[k] = minus ? pny[k] : py[k];
-            bool same_y = false;
-            if (!f29_madd(acc, px, ya, same_y)) {           // k = r - 2 at its last digit (see above); for any other scalar below r this is not reached
-                if (same_y) f29_acc_dbl(acc);
-                else { inf = true; break; }
-            }
+            for (int k = 0; k < 9; k++) p.y[k] = minus ? pny[k] : py[k];
+            add_point<G>(acc, inf, p);                      // exceptional for k = r - 2 at its last digit (see above) and for no other scalar below r
+            if (inf) break;                                 // ... where the product is infinity
         }
     }
-    if (!inf) { o.X = f29_to_fp<FqParams>(acc.X); o.Y = f29_to_fp<FqParams>(acc.Y); o.ZZ = f29_to_fp<FqParams>(acc.ZZ); o.ZZZ = f29_to_fp<FqParams>(acc.ZZZ); }
+    if (!inf) o = G::leave(acc);
     out[i] = o;
 }
 
@@ -92,12 +84,10 @@ __global__ void __launch_bounds__(256)
 zkc_p2_mont_to_std(uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint32_t xs[8], ys[8]; load_point(xs, ys, pts, i);
-    if (!fp_std_lt_p<FqParams>(xs) || !fp_std_lt_p<FqParams>(ys)) { atomicOr(bad, 1u); return; }
-    Fq X, Y;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { X.v[k] = xs[k]; Y.v[k] = ys[k]; }
-    fp_to_std<FqParams>(xs, X); fp_to_std<FqParams>(ys, Y);
+    uint32_t w[16]; load_words<16>(w, pts + 16 * (size_t)i);
+    if (!coords_below_q<G1Ops>(w)) { atomicOr(bad, 1u); return; }
+    uint32_t xs[8], ys[8];
+    fp_to_std<FqParams>(xs, fq_of(w)); fp_to_std<FqParams>(ys, fq_of(w + 8));
     uint4* q = reinterpret_cast<uint4*>(pts + 16 * (size_t)i);
     q[0] = make_uint4(xs[0], xs[1], xs[2], xs[3]); q[1] = make_uint4(xs[4], xs[5], xs[6], xs[7]);
     q[2] = make_uint4(ys[0], ys[1], ys[2], ys[3]); q[3] = make_uint4(ys[4], ys[5], ys[6], ys[7]);
@@ -151,7 +141,7 @@ int scale_dev(zkc_ctx* ctx, const void* d_points, uint32_t n, const uint32_t k[8
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const clk::time_point t1 = clk::now();
     if (bad != 0xffffffffu) return zkc_fail(ctx, ZKC_ERR_FORMAT, "zkc_g1_scale_dev: point " + std::to_string(bad) + " has a coordinate >= q or is not on the curve");
-    const int rc = fixed_affine_g1(ctx, (const G1XYZZ*)sum.p, n, d_out, mont);
+    const int rc = fixed_affine<Fq>(ctx, (const G1XYZZ*)sum.p, n, d_out, mont);
     if (ms) { ms[0] = ms_since(t0, t1); ms[1] = ms_since(t1); }
     return rc;
 }
@@ -172,7 +162,6 @@ Fq2 fq2_sqrt_candidate(const Fq2& a) {
     if (alpha == minus1) return Fq2{fp_neg(x0.c1), x0.c0};     // u x0
     return pairing::fq2_pow(Fq2::one() + alpha, e12, 256) * x0;
 }
-bool std_less(const uint32_t a[8], const uint32_t b[8]) { for (int i = 7; i >= 0; i--) if (a[i] != b[i]) return a[i] < b[i]; return false; }
 
 // THE ONE PLACE that says how the G2 challenge of a contribution is derived from its transcript.  It must be a hash to G2 with UNKNOWN discrete logarithm: a multiple
 // of the generator by a hashed scalar would let anyone compute g2_spx = x g2_sp from g1_sx without knowing x, and the proof of knowledge would prove nothing.

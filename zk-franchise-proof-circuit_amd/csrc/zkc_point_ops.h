@@ -1,6 +1,7 @@
-// zkc_point_ops.h -- G1 and G2 behind one interface for the kernels that work on the points of a file (zkc_setup_ptau.hip: a sparse matrix times a vector of points;
-// zkc_ecntt.hip: a transform over points): an accumulator in radix 2^29, set from / added to by an affine point in Montgomery words, and the complete additions of two
-// such accumulators.  Device only; product code.
+// zkc_point_ops.h -- G1 and G2 behind one interface for the kernels that work on the points of a file (zkc_phase2.hip: one scalar times many points; zkc_setup_ptau.hip:
+// a sparse matrix times a vector of points; zkc_ecntt.hip: a transform over points): the check of such a point, an accumulator in radix 2^29, set from / added to by an
+// affine point in Montgomery words, the complete additions of two such accumulators, and the trait by which host code that is generic in the field picks the group
+// (GroupOf).  The operations are device only and the header needs hipcc: a plain C++ host program (tests/host/*.cc) cannot include it.  Product code.
 //
 // The additions.  Unlike a prover's bases these points are an adversary's, or merely unlucky, and all three exceptional cases of an addition occur in files the tests make:
 // equal points, opposite points, and infinity (with tau a root of unity all but one Lagrange point are infinity, and the monomial points repeat).  So: an all-zero point is
@@ -37,6 +38,7 @@ struct G1Ops {
     static constexpr int W = 16;                                 // words of an affine point
     typedef Fq F; typedef Acc29 Acc;
     struct Pt { uint32_t x[9], y[9]; };
+    __device__ static __forceinline__ Fq coord(const uint32_t* w) { return fq_of(w); }
     __device__ static __forceinline__ Pt enter(const uint32_t* w, bool neg) {
         Pt p; Fq Y = fq_of(w + 8); if (neg) Y = fp_neg(Y);
         f29_enter_fq(p.x, w); f29_enter_fq(p.y, Y.v);            // below 1.2 p each: well inside what f29_madd takes
@@ -59,8 +61,9 @@ struct G2Ops {
     static constexpr int W = 32;
     typedef Fq2 F; typedef Acc29G2 Acc;
     struct Pt { F2x29 x, y; };
+    __device__ static __forceinline__ Fq2 coord(const uint32_t* w) { return Fq2{fq_of(w), fq_of(w + 8)}; }
     __device__ static __forceinline__ Pt enter(const uint32_t* w, bool neg) {
-        Pt p; Fq2 X{fq_of(w), fq_of(w + 8)}, Y{fq_of(w + 16), fq_of(w + 24)}; if (neg) Y = fp_neg(Y);
+        Pt p; Fq2 X = coord(w), Y = coord(w + 16); if (neg) Y = fp_neg(Y);
         f29g2_enter(p.x, X); f29g2_enter(p.y, Y);               // carried, below 3 p per component
         return p;
     }
@@ -79,6 +82,24 @@ struct G2Ops {
     __device__ static __forceinline__ void pt_dbl(Acc& r, const Acc& a) { f29g2_pt_dbl(r, a); }
     __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29g2_pt_is_inf(a); }
 };
+
+// field -> group, for host code that is generic in F: the operations its kernels are instantiated with, and the words its messages need
+template <class F> struct GroupOf;
+template <> struct GroupOf<Fq> { typedef G1Ops Ops; static constexpr bool g2 = false; static constexpr const char *curve = "curve", *lagrange_dev = "zkc_g1_lagrange_dev"; };
+template <> struct GroupOf<Fq2> { typedef G2Ops Ops; static constexpr bool g2 = true; static constexpr const char *curve = "twist", *lagrange_dev = "zkc_g2_lagrange_dev"; };
+
+// ---- the check of a point read from a file, w = its G::W Montgomery words (all zero is infinity and is not brought here): every coordinate < q, which is a test of the
+// raw words, and y^2 = x^3 + b (G1: 3; G2: the twist's 3 / (9 + u), computed on the host) ----
+template <class G> __device__ __forceinline__ bool coords_below_q(const uint32_t* w) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < G::W; c += 8) ok = ok && fp_std_lt_p<FqParams>(w + c);
+    return ok;
+}
+template <class G> __device__ __forceinline__ bool on_curve(const uint32_t* w, const typename G::F& b) {
+    const typename G::F X = G::coord(w), Y = G::coord(w + G::W / 2);
+    return fp_sqr(Y) == fp_sqr(X) * X + b;
+}
 
 // acc (inf: at infinity) += p, every case handled: see the head of the file
 template <class G> __device__ __forceinline__ void add_point(typename G::Acc& acc, bool& inf, const typename G::Pt& p) {

@@ -5,8 +5,8 @@
 // Both entry points are one walk over the four families (12 from 2, 13 from 3, 14 from 4, 15 from 5).  Per family:
 //   1 (host)  read the monomial section whole (zkc_ptau_parse.h).  Section 2 is one point short of its largest block, 2^(power+1): the missing point is left all zero,
 //             infinity -- the padded top block of zkcensus_ptau_prepare.h
-//   2         check every point read: coordinates < q, on its curve (GPU: upload, zkc_ptau_check_*; ctx = NULL: host threads); the smallest bad index is named
-//   3         for p = 0 .. power (section 12: power + 1) the transform of the first 2^p points: on the GPU ecntt_g1 / ecntt_g2 over the section resident on the device,
+//   2         check every point read: coordinates < q, on its curve (GPU: upload, points_check_dev; ctx = NULL: host_first_bad on host threads); the smallest bad index is named
+//   3         for p = 0 .. power (section 12: power + 1) the transform of the first 2^p points: on the GPU ecntt<F> over the section resident on the device,
 //             one block at a time and each downloaded as it is done; with ctx = NULL the same butterflies with zkc_curve.h on at most HOST_THREADS threads
 //   4 (host)  prepare: the block goes into the section's image, which is written when the family is done (zkc_ptau_write.h); check_prepared: the block is compared with
 //             the stored one and the walk ends at the first point that differs.
@@ -17,6 +17,8 @@
 #include <vector>
 #include "zkc_prover.h"
 #include "zkc_ecntt.h"
+#include "zkc_fixedbase_dev.h"
+#include "zkc_point_ops.h"
 #include "zkc_host_util.h"
 #include "zkc_pairing.h"
 #include "zkc_file_points.h"
@@ -59,25 +61,13 @@ void host_lagrange(const Affine<F>* in, uint32_t logn, Affine<F>* out) {
     par_chunks(n, 64, [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) out[i] = xyzz_to_affine_gcd(v[i]); });
 }
 
-template <class F> struct Grp;
-template <> struct Grp<Fq> {
-    static int check(zkc_ctx* ctx, const void* d, uint32_t n, uint32_t* bad) { return ecntt_check_g1(ctx, d, n, bad); }
-    static int run(zkc_ctx* ctx, const void* d, uint32_t logn, const Fr* tw, uint32_t twl, void* o, double* ms) { return ecntt_g1(ctx, d, logn, tw, twl, o, true, ms); }
-    static constexpr bool g2 = false; static constexpr const char* curve = "curve";
-};
-template <> struct Grp<Fq2> {
-    static int check(zkc_ctx* ctx, const void* d, uint32_t n, uint32_t* bad) { return ecntt_check_g2(ctx, d, n, bad); }
-    static int run(zkc_ctx* ctx, const void* d, uint32_t logn, const Fr* tw, uint32_t twl, void* o, double* ms) { return ecntt_g2(ctx, d, logn, tw, twl, o, true, ms); }
-    static constexpr bool g2 = true; static constexpr const char* curve = "twist";
-};
-
 // what the walk hands over: block p of section `sec`, 2^p points of PT bytes.  false ends the walk (the walk then returns ZKC_OK: the callback has kept its verdict)
 typedef std::function<bool(int sec, uint32_t p, const uint8_t* bytes, size_t nbytes)> BlockFn;
 
 // one family.  The context's lock is held and the device is set when ctx != NULL.  d_tw: ecntt_twiddles of tw_logn = power + 1.  *go = false: the callback ended the walk
 template <class F>
 int family(zkc_ctx* ctx, const parse::Ptau& pt, int sec, const Fr* d_tw, uint32_t tw_logn, const BlockFn& fn, bool* go, char* err, size_t errlen) {
-    typedef Grp<F> G;
+    typedef GroupOf<F> G;
     constexpr size_t PT = sizeof(Affine<F>);
     const int mono = parse::ptau_monomial_of(sec);
     const uint32_t last = parse::ptau_last_block(sec, pt.power);
@@ -101,14 +91,8 @@ int family(zkc_ctx* ctx, const parse::Ptau& pt, int sec, const Fr* d_tw, uint32_
                                              std::to_string(need >> 20) + " MB needed, " + std::to_string(free_b >> 20) + " MB free)");
         if ((rc = d_in.alloc(ctx, nmax * PT)) || (rc = d_out.alloc(ctx, nmax * PT))) return err_out(err, errlen, rc, zkc_last_error(ctx));
         if (hipMemcpy(d_in.p, in.data(), nmax * PT, hipMemcpyHostToDevice) != hipSuccess) return err_out(err, errlen, zkc_fail(ctx, ZKC_ERR_HIP, "zkc_ptau_prepare: upload"), zkc_last_error(ctx));
-        if ((rc = G::check(ctx, d_in.p, (uint32_t)nmax, &bad))) return err_out(err, errlen, rc, zkc_last_error(ctx));
-    } else {
-        std::atomic<uint32_t> first_bad{0xffffffffu};
-        par_chunks(npts, 4096, [&](size_t a, size_t b) {
-            for (size_t i = a; i < b; i++) if (!host_point_ok<F>(in[i])) { uint32_t cur = first_bad.load(); while ((uint32_t)i < cur && !first_bad.compare_exchange_weak(cur, (uint32_t)i)) {} break; }
-        });
-        bad = first_bad.load();
-    }
+        if ((rc = points_check_dev<F>(ctx, d_in.p, (uint32_t)nmax, &bad))) return err_out(err, errlen, rc, zkc_last_error(ctx));
+    } else bad = host_first_bad<F>(in.data(), npts);
     g_prep_ms[1] += ms_since(t0);
     if (bad != 0xffffffffu) return setup_fail(err, errlen, "ptau: section " + std::to_string(mono) + " point " + std::to_string(bad) + " has a coordinate >= q or is not on the " + G::curve);
     // ---- 3, 4 ----
@@ -118,7 +102,7 @@ int family(zkc_ctx* ctx, const parse::Ptau& pt, int sec, const Fr* d_tw, uint32_
         const size_t n = (size_t)1 << p;
         if (ctx) {
             double ms[2] = {0, 0};
-            if ((rc = G::run(ctx, d_in.p, p, d_tw, tw_logn, d_out.p, ms))) return err_out(err, errlen, rc, zkc_last_error(ctx));
+            if ((rc = ecntt<F>(ctx, d_in.p, p, d_tw, tw_logn, d_out.p, true, ms))) return err_out(err, errlen, rc, zkc_last_error(ctx));
             t0 = clk::now();
             if (hipMemcpy((void*)blk.data(), d_out.p, n * PT, hipMemcpyDeviceToHost) != hipSuccess) return err_out(err, errlen, zkc_fail(ctx, ZKC_ERR_HIP, "zkc_ptau_prepare: download"), zkc_last_error(ctx));
             *tms += ms[0]; g_prep_ms[4] += ms[1] + ms_since(t0);

@@ -11,7 +11,7 @@
 //             the jobs are sorted by scalar, so the lanes of a wave walk bit strings of the same length and largely the same bits.  Rows are ordered by decreasing
 //             length (jds_layout, zkc_jds.h: neighbouring lanes get equal work) and cut into SEGMENTS of at most SEG terms.
 //   3 (GPU, or host threads with ctx = NULL)
-//             check      one lane per point read: coordinates < q, on the curve; the smallest bad index comes back (the file is not trusted)
+//             check      one lane per point read: coordinates < q, on the curve; the smallest bad index comes back (the file is not trusted; points_check_dev)
 //             scale      one lane per job: double-and-add from the scalar's leading bit, f29_acc_dbl / f29_madd (G2: f29g2_pt_dbl / f29g2_madd_lean) as zkc_p2_scale_g1;
 //                        the products become affine through the batched inversion of the fixed-base engine and land behind the points read
 //             accumulate one lane per segment: mixed additions of +-P into an XYZZ partial sum
@@ -21,12 +21,9 @@
 //   4 (host)  the sanity checks, csHash, and the shared writer (zkc_setup_write.h).
 // Every loop of every kernel is bounded by a count the host computed; nothing waits on a flag.  SEG, RED are the only tunables.
 //
-// The additions.  Unlike a prover's bases these points are an adversary's, or merely unlucky, and all three exceptional cases of the mixed addition occur in files the
-// tests make: K_s adds alpha L_c and beta L_c, which are EQUAL when alpha = beta and OPPOSITE when alpha = -beta, and with tau a root of unity all but one Lagrange point are
-// infinity.  So: an all-zero point is skipped, an accumulator at infinity is set rather than added to, and f29_madd's `false` return is taken at every addition -- equal:
-// double the accumulator (it holds that very point), opposite: back to infinity -- in both kernels and both groups.  The reduction uses the complete f29_pt_add.
+// The additions: every exceptional case is live and handled, see the head of zkc_point_ops.h.  Here K_s adds alpha L_c and beta L_c, which are EQUAL when alpha = beta and
+// OPPOSITE when alpha = -beta.
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <functional>
 #include <string>
@@ -41,7 +38,6 @@
 #include "zkc_pairing.h"
 #include "zkc_file_points.h"
 #include "zkc_jds.h"
-#include "zkc_kernels.h"
 #include "zkc_phase2_parse.h"
 #include "zkc_ptau_parse.h"
 #include "zkc_setup_write.h"
@@ -49,33 +45,6 @@
 #include "../../include/zkcensus_ptau.h"
 
 using namespace zkc;
-
-namespace zkc {
-
-// ---- check: *bad (initialised to 0xffffffff) = the smallest index of a point with a coordinate >= q or off its curve; all zero is infinity and passes ----
-// (declared in zkc_kernels.h: zkc_ecntt.hip launches them too; Montgomery words)
-extern "C" __global__ void __launch_bounds__(256)
-zkc_ptau_check_g1(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ bad) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t w[16]; load_words<16>(w, pts + 16 * (size_t)i);
-    if (all_zero<16>(w)) return;
-    if (!fp_std_lt_p<FqParams>(w) || !fp_std_lt_p<FqParams>(w + 8)) { atomicMin(bad, i); return; }
-    const Fq X = fq_of(w), Y = fq_of(w + 8);
-    if (!(fp_sqr(Y) == fp_sqr(X) * X + fp_from_u32<FqParams>(3))) atomicMin(bad, i);
-}
-extern "C" __global__ void __launch_bounds__(256)
-zkc_ptau_check_g2(const uint32_t* __restrict__ pts, uint32_t n, Fq2 twist_b, uint32_t* __restrict__ bad) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t w[32]; load_words<32>(w, pts + 32 * (size_t)i);
-    if (all_zero<32>(w)) return;
-    if (!fp_std_lt_p<FqParams>(w) || !fp_std_lt_p<FqParams>(w + 8) || !fp_std_lt_p<FqParams>(w + 16) || !fp_std_lt_p<FqParams>(w + 24)) { atomicMin(bad, i); return; }
-    const Fq2 X{fq_of(w), fq_of(w + 8)}, Y{fq_of(w + 16), fq_of(w + 24)};
-    if (!(fp_sqr(Y) == fp_sqr(X) * X + twist_b)) atomicMin(bad, i);
-}
-
-}  // namespace zkc
 
 namespace {
 
@@ -85,11 +54,11 @@ constexpr uint32_t T_NEG = 0x80000000u, T_IDX = 0x7fffffffu;
 
 // ================================================================ device ================================================================
 
-// load_words, all_zero, fq_of, shl1_out, the two groups behind one interface (G1Ops, G2Ops) and add_point: zkc_point_ops.h
+// load_words, all_zero, shl1_out, the two groups behind one interface (G1Ops, G2Ops) and add_point: zkc_point_ops.h
 
 // ---- scale: out[j] = k_j * pts[src_j] as canonical XYZZ (infinity: all zero).  k_j: 8 words, standard form, 1 < k_j <= (r - 1) / 2 ----
-template <class G> __device__ __forceinline__ void scale_body(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ ks, const uint32_t* __restrict__ src,
-                                                              uint32_t njobs, XYZZ<typename G::F>* __restrict__ out) {
+template <class G> __global__ void __launch_bounds__(64)
+zkc_ptau_scale(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ ks, const uint32_t* __restrict__ src, uint32_t njobs, XYZZ<typename G::F>* __restrict__ out) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= njobs) return;
     XYZZ<typename G::F> o = XYZZ<typename G::F>::inf();
@@ -111,18 +80,10 @@ template <class G> __device__ __forceinline__ void scale_body(const uint32_t* __
     if (!inf) o = G::leave(acc);
     out[j] = o;
 }
-__global__ void __launch_bounds__(64)
-zkc_ptau_scale_g1(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ ks, const uint32_t* __restrict__ src, uint32_t njobs, XYZZ<Fq>* __restrict__ out) {
-    scale_body<G1Ops>(pts, npts, ks, src, njobs, out);
-}
-__global__ void __launch_bounds__(64)
-zkc_ptau_scale_g2(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ ks, const uint32_t* __restrict__ src, uint32_t njobs, XYZZ<Fq2>* __restrict__ out) {
-    scale_body<G2Ops>(pts, npts, ks, src, njobs, out);
-}
 
 // ---- accumulate: part[s] = sum of the terms [seg_start[s], seg_start[s + 1]) (at most SEG of them), each +-pts[index] ----
-template <class G> __device__ __forceinline__ void acc_body(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ terms, const uint32_t* __restrict__ seg_start,
-                                                            uint32_t nseg, XYZZ<typename G::F>* __restrict__ part) {
+template <class G> __global__ void __launch_bounds__(64)
+zkc_ptau_acc(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ terms, const uint32_t* __restrict__ seg_start, uint32_t nseg, XYZZ<typename G::F>* __restrict__ part) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
     const uint32_t t0 = seg_start[s]; uint32_t t1 = seg_start[s + 1];
@@ -140,18 +101,10 @@ template <class G> __device__ __forceinline__ void acc_body(const uint32_t* __re
     if (!inf) o = G::leave(acc);
     part[s] = o;
 }
-__global__ void __launch_bounds__(64)
-zkc_ptau_acc_g1(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ terms, const uint32_t* __restrict__ seg_start, uint32_t nseg, XYZZ<Fq>* __restrict__ part) {
-    acc_body<G1Ops>(pts, npts, terms, seg_start, nseg, part);
-}
-__global__ void __launch_bounds__(64)
-zkc_ptau_acc_g2(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __restrict__ terms, const uint32_t* __restrict__ seg_start, uint32_t nseg, XYZZ<Fq2>* __restrict__ part) {
-    acc_body<G2Ops>(pts, npts, terms, seg_start, nseg, part);
-}
 
 // ---- reduce: out[j] = sum of in[job_start[j] .. job_start[j + 1]) (at most RED of them; none: infinity), complete additions ----
-template <class G> __device__ __forceinline__ void red_body(const XYZZ<typename G::F>* __restrict__ in, const uint32_t* __restrict__ job_start, uint32_t njobs,
-                                                            XYZZ<typename G::F>* __restrict__ out) {
+template <class G> __global__ void __launch_bounds__(64)
+zkc_ptau_red(const XYZZ<typename G::F>* __restrict__ in, const uint32_t* __restrict__ job_start, uint32_t njobs, XYZZ<typename G::F>* __restrict__ out) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= njobs) return;
     const uint32_t a = job_start[j]; uint32_t b = job_start[j + 1];
@@ -162,10 +115,6 @@ template <class G> __device__ __forceinline__ void red_body(const XYZZ<typename 
     for (uint32_t i = a + 1; i < b; i++) { const typename G::Acc o = G::from_xyzz(in[i]); typename G::Acc r; G::add(r, acc, o); acc = r; }
     out[j] = G::is_inf(acc) ? XYZZ<typename G::F>::inf() : G::leave(acc);
 }
-__global__ void __launch_bounds__(64)
-zkc_ptau_red_g1(const XYZZ<Fq>* __restrict__ in, const uint32_t* __restrict__ job_start, uint32_t njobs, XYZZ<Fq>* __restrict__ out) { red_body<G1Ops>(in, job_start, njobs, out); }
-__global__ void __launch_bounds__(64)
-zkc_ptau_red_g2(const XYZZ<Fq2>* __restrict__ in, const uint32_t* __restrict__ job_start, uint32_t njobs, XYZZ<Fq2>* __restrict__ out) { red_body<G2Ops>(in, job_start, njobs, out); }
 
 // ================================================================ host ================================================================
 
@@ -182,7 +131,6 @@ struct Builder {
     Fr one = Fr::one(), minus_one = fp_neg(Fr::one());
     uint32_t half[8];                                           // (r - 1) / 2
     Builder() { for (int i = 0; i < 8; i++) half[i] = (FrParams::p[i] >> 1) | (i < 7 ? FrParams::p[i + 1] << 31 : 0); }
-    static bool std_less(const uint32_t a[8], const uint32_t b[8]) { for (int i = 7; i >= 0; i--) if (a[i] != b[i]) return a[i] < b[i]; return false; }
     void add(uint32_t row, const Fr& coef, uint32_t src) {
         if (coef.is_zero()) return;
         if (coef == one) { unit.emplace_back(row, src); return; }
@@ -204,7 +152,7 @@ struct Plan {
 bool make_plan(Builder& B, Plan& P, std::string& why) {
     P.nbase = B.nbase; P.nrows = B.nrows; P.nunit = B.unit.size(); P.ngen = B.gen.size();
     if ((uint64_t)B.nbase + B.gen.size() > T_IDX || (uint64_t)B.unit.size() + B.gen.size() > 0xfffffff0ull) { why = "circuit too large for 32-bit term words"; return false; }
-    std::stable_sort(B.gen.begin(), B.gen.end(), [](const GenTerm& a, const GenTerm& b) { return Builder::std_less(a.k, b.k); });
+    std::stable_sort(B.gen.begin(), B.gen.end(), [](const GenTerm& a, const GenTerm& b) { return std_less(a.k, b.k); });
     const size_t nj = B.gen.size();
     P.jobk.resize(8 * nj); P.jobsrc.resize(nj);
     std::vector<uint32_t> len(B.nrows, 0);
@@ -248,14 +196,10 @@ std::vector<std::vector<uint32_t>> reduction_steps(const Plan& P) {
 }
 
 // ---- stage 3 on host threads (zkc_curve.h), over the same plan ----
-// host_point_ok: zkc_file_points.h
+// host_first_bad: zkc_file_points.h
 template <class F>
 void run_host(const Plan& P, std::vector<Affine<F>>& pts, std::vector<Affine<F>>& rows, uint32_t& bad, double ms[3]) {
-    std::atomic<uint32_t> first_bad{0xffffffffu};
-    par_chunks(P.nbase, 4096, [&](size_t a, size_t b) {
-        for (size_t i = a; i < b; i++) if (!host_point_ok<F>(pts[i])) { uint32_t cur = first_bad.load(); while ((uint32_t)i < cur && !first_bad.compare_exchange_weak(cur, (uint32_t)i)) {} break; }
-    });
-    bad = first_bad.load();
+    bad = host_first_bad<F>(pts.data(), P.nbase);
     if (bad != 0xffffffffu) return;
     const clk::time_point t0 = clk::now();
     pts.resize((size_t)P.nbase + P.njobs());
@@ -288,46 +232,19 @@ void run_host(const Plan& P, std::vector<Affine<F>>& pts, std::vector<Affine<F>>
 }
 
 // ---- stage 3 on the device.  The context's lock is held and the device is set.  ms: upload, scale, accumulate and reduce ----
-template <class F> struct DevK;
-template <> struct DevK<Fq> {
-    static void check(zkc_ctx* ctx, const uint32_t* pts, uint32_t n, uint32_t* bad) { hipLaunchKernelGGL(zkc_ptau_check_g1, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pts, n, bad); }
-    static void scale(zkc_ctx* ctx, const uint32_t* pts, uint32_t npts, const uint32_t* ks, const uint32_t* src, uint32_t nj, XYZZ<Fq>* out) {
-        hipLaunchKernelGGL(zkc_ptau_scale_g1, dim3((nj + 63) / 64), dim3(64), 0, ctx->stream, pts, npts, ks, src, nj, out); }
-    static void acc(zkc_ctx* ctx, const uint32_t* pts, uint32_t npts, const uint32_t* terms, const uint32_t* seg, uint32_t nseg, XYZZ<Fq>* part) {
-        hipLaunchKernelGGL(zkc_ptau_acc_g1, dim3((nseg + 63) / 64), dim3(64), 0, ctx->stream, pts, npts, terms, seg, nseg, part); }
-    static void red(zkc_ctx* ctx, const XYZZ<Fq>* in, const uint32_t* start, uint32_t nj, XYZZ<Fq>* out) {
-        hipLaunchKernelGGL(zkc_ptau_red_g1, dim3((nj + 63) / 64), dim3(64), 0, ctx->stream, in, start, nj, out); }
-    static int affine(zkc_ctx* ctx, const XYZZ<Fq>* in, uint32_t n, void* out) { return fixed_affine_g1(ctx, in, n, out, true); }
-};
-template <> struct DevK<Fq2> {
-    static void check(zkc_ctx* ctx, const uint32_t* pts, uint32_t n, uint32_t* bad) {
-        hipLaunchKernelGGL(zkc_ptau_check_g2, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, pts, n, pairing::consts().twist_b, bad); }
-    static void scale(zkc_ctx* ctx, const uint32_t* pts, uint32_t npts, const uint32_t* ks, const uint32_t* src, uint32_t nj, XYZZ<Fq2>* out) {
-        hipLaunchKernelGGL(zkc_ptau_scale_g2, dim3((nj + 63) / 64), dim3(64), 0, ctx->stream, pts, npts, ks, src, nj, out); }
-    static void acc(zkc_ctx* ctx, const uint32_t* pts, uint32_t npts, const uint32_t* terms, const uint32_t* seg, uint32_t nseg, XYZZ<Fq2>* part) {
-        hipLaunchKernelGGL(zkc_ptau_acc_g2, dim3((nseg + 63) / 64), dim3(64), 0, ctx->stream, pts, npts, terms, seg, nseg, part); }
-    static void red(zkc_ctx* ctx, const XYZZ<Fq2>* in, const uint32_t* start, uint32_t nj, XYZZ<Fq2>* out) {
-        hipLaunchKernelGGL(zkc_ptau_red_g2, dim3((nj + 63) / 64), dim3(64), 0, ctx->stream, in, start, nj, out); }
-    static int affine(zkc_ctx* ctx, const XYZZ<Fq2>* in, uint32_t n, void* out) { return fixed_affine_g2(ctx, in, n, out, true); }
-};
-
 template <class F>
 int run_dev(zkc_ctx* ctx, const Plan& P, const std::vector<Affine<F>>& base, std::vector<Affine<F>>& rows, uint32_t& bad, double ms[3]) {
-    typedef DevK<F> K;
+    typedef typename GroupOf<F>::Ops G;
     constexpr size_t PT = sizeof(Affine<F>);
     const uint32_t nj = P.njobs(), npts = P.nbase + nj;
     int rc;
     const clk::time_point t0 = clk::now();
-    DevBuf pts, flag, terms, seg;
-    if ((rc = pts.alloc(ctx, (size_t)npts * PT)) || (rc = flag.alloc(ctx, 4)) || (rc = terms.alloc(ctx, P.terms.size() * 4)) || (rc = seg.alloc(ctx, P.seg_start.size() * 4))) return rc;
+    DevBuf pts, terms, seg;
+    if ((rc = pts.alloc(ctx, (size_t)npts * PT)) || (rc = terms.alloc(ctx, P.terms.size() * 4)) || (rc = seg.alloc(ctx, P.seg_start.size() * 4))) return rc;
     ZKC_HIP_CHECK(ctx, hipMemcpy(pts.p, base.data(), (size_t)P.nbase * PT, hipMemcpyHostToDevice));
     if (!P.terms.empty()) ZKC_HIP_CHECK(ctx, hipMemcpy(terms.p, P.terms.data(), P.terms.size() * 4, hipMemcpyHostToDevice));
     ZKC_HIP_CHECK(ctx, hipMemcpy(seg.p, P.seg_start.data(), P.seg_start.size() * 4, hipMemcpyHostToDevice));
-    ZKC_HIP_CHECK(ctx, hipMemsetAsync(flag.p, 0xff, 4, ctx->stream));
-    K::check(ctx, pts.as<uint32_t>(), P.nbase, flag.as<uint32_t>());
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = points_check_dev<F>(ctx, pts.p, P.nbase, &bad))) return rc;
     if (bad != 0xffffffffu) return ZKC_OK;                     // the caller names the point
     const clk::time_point t1 = clk::now();
     if (nj) {
@@ -335,26 +252,32 @@ int run_dev(zkc_ctx* ctx, const Plan& P, const std::vector<Affine<F>>& base, std
         if ((rc = ks.alloc(ctx, (size_t)nj * 32)) || (rc = src.alloc(ctx, (size_t)nj * 4)) || (rc = prod.alloc(ctx, (size_t)nj * sizeof(XYZZ<F>)))) return rc;
         ZKC_HIP_CHECK(ctx, hipMemcpy(ks.p, P.jobk.data(), (size_t)nj * 32, hipMemcpyHostToDevice));
         ZKC_HIP_CHECK(ctx, hipMemcpy(src.p, P.jobsrc.data(), (size_t)nj * 4, hipMemcpyHostToDevice));
-        K::scale(ctx, pts.as<uint32_t>(), P.nbase, ks.as<uint32_t>(), src.as<uint32_t>(), nj, prod.as<XYZZ<F>>());
+        hipLaunchKernelGGL(zkc_ptau_scale<G>, dim3((nj + 63) / 64), dim3(64), 0, ctx->stream, pts.as<uint32_t>(), P.nbase, ks.as<uint32_t>(), src.as<uint32_t>(), nj, prod.as<XYZZ<F>>());
         ZKC_HIP_CHECK(ctx, hipGetLastError());
-        if ((rc = K::affine(ctx, prod.as<XYZZ<F>>(), nj, (uint8_t*)pts.p + (size_t)P.nbase * PT))) return rc;      // synchronises
+        if ((rc = fixed_affine<F>(ctx, prod.as<XYZZ<F>>(), nj, (uint8_t*)pts.p + (size_t)P.nbase * PT, true))) return rc;      // synchronises
     }
     const clk::time_point t2 = clk::now();
     DevBuf cur, nxt;
     if ((rc = cur.alloc(ctx, (size_t)P.nseg * sizeof(XYZZ<F>)))) return rc;
-    if (P.nseg) { K::acc(ctx, pts.as<uint32_t>(), npts, terms.as<uint32_t>(), seg.as<uint32_t>(), P.nseg, cur.as<XYZZ<F>>()); ZKC_HIP_CHECK(ctx, hipGetLastError()); }
+    if (P.nseg) {
+        hipLaunchKernelGGL(zkc_ptau_acc<G>, dim3((P.nseg + 63) / 64), dim3(64), 0, ctx->stream, pts.as<uint32_t>(), npts, terms.as<uint32_t>(), seg.as<uint32_t>(), P.nseg, cur.as<XYZZ<F>>());
+        ZKC_HIP_CHECK(ctx, hipGetLastError());
+    }
     for (const std::vector<uint32_t>& start : reduction_steps(P)) {
         const uint32_t njobs = (uint32_t)start.size() - 1;
         DevBuf st;
         if ((rc = st.alloc(ctx, start.size() * 4)) || (rc = nxt.alloc(ctx, (size_t)njobs * sizeof(XYZZ<F>)))) return rc;
         ZKC_HIP_CHECK(ctx, hipMemcpyAsync(st.p, start.data(), start.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (njobs) { K::red(ctx, cur.as<XYZZ<F>>(), st.as<uint32_t>(), njobs, nxt.as<XYZZ<F>>()); ZKC_HIP_CHECK(ctx, hipGetLastError()); }
+        if (njobs) {
+            hipLaunchKernelGGL(zkc_ptau_red<G>, dim3((njobs + 63) / 64), dim3(64), 0, ctx->stream, cur.as<XYZZ<F>>(), st.as<uint32_t>(), njobs, nxt.as<XYZZ<F>>());
+            ZKC_HIP_CHECK(ctx, hipGetLastError());
+        }
         ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));                                                  // `start` and `st` end with this turn of the loop
         (void)hipFree(cur.p); cur.p = nxt.release();
     }
     // cur: one sum per sorted row
     DevBuf aff;
-    if ((rc = aff.alloc(ctx, (size_t)P.nrows * PT)) || (rc = K::affine(ctx, cur.as<XYZZ<F>>(), P.nrows, aff.p))) return rc;
+    if ((rc = aff.alloc(ctx, (size_t)P.nrows * PT)) || (rc = fixed_affine<F>(ctx, cur.as<XYZZ<F>>(), P.nrows, aff.p, true))) return rc;
     std::vector<Affine<F>> sorted(P.nrows);
     ZKC_HIP_CHECK(ctx, hipMemcpy(sorted.data(), aff.p, (size_t)P.nrows * PT, hipMemcpyDeviceToHost));
     rows.resize(P.nrows);
@@ -363,8 +286,7 @@ int run_dev(zkc_ctx* ctx, const Plan& P, const std::vector<Affine<F>>& base, std
     return ZKC_OK;
 }
 
-bool same_point(const G1Affine& a, const G1Affine& b) { return a.x == b.x && a.y == b.y; }
-bool same_point(const G2Affine& a, const G2Affine& b) { return a.x == b.x && a.y == b.y; }
+template <class F> bool same_point(const Affine<F>& a, const Affine<F>& b) { return a.x == b.x && a.y == b.y; }
 
 // csHash of the initial key: the serialisation of zkcensus_ptau.h
 void circuit_hash(const SetupScalars& S, const SetupPoints& P, uint8_t out[64]) {
