@@ -136,7 +136,7 @@ FULL = 0x2a9e3c1f7b5d08e64c3a1f9d7e5b2c0a8f6e4d2b1a0918273645546372819aaf % R
 
 def crafted():
     rng = random.Random(11)
-    kinds = [1, R - 1, 2, R - 2, 1 << 253, FULL, None]
+    kinds = [1, R - 1, 2, R - 2, 1 << 253, FULL, None, (R - 1) // 2, (R + 1) // 2]
     n_cons = max(LENS)
     cons = []
     for c in range(n_cons):

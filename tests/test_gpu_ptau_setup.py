@@ -65,7 +65,7 @@ def crafted():
     infinity) and its K row the sum; coefficients cycle through 1, r - 1, 2, r - 2, 2^253, a full-width value that repeats within the row, and random full-width ones.
     Wire 9 is squared with coefficient 1, and with FULL, in constraints of its own (alpha = +-beta: P + P and P - P in K), C empty there."""
     rng = random.Random(11)
-    kinds = [1, R - 1, 2, R - 2, 1 << 253, FULL, None]
+    kinds = [1, R - 1, 2, R - 2, 1 << 253, FULL, None, (R - 1) // 2, (R + 1) // 2]
     n_cons = max(LENS)
     cons = []
     for c in range(n_cons):

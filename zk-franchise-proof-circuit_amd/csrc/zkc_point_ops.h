@@ -3,10 +3,20 @@
 // affine point in Montgomery words, the complete additions of two such accumulators, and the trait by which host code that is generic in the field picks the group
 // (GroupOf).  The operations are device only and the header needs hipcc: a plain C++ host program (tests/host/*.cc) cannot include it.  Product code.
 //
-// The additions.  Unlike a prover's bases these points are an adversary's, or merely unlucky, and all three exceptional cases of an addition occur in files the tests make:
-// equal points, opposite points, and infinity (with tau a root of unity all but one Lagrange point are infinity, and the monomial points repeat).  So: an all-zero point is
-// skipped, an accumulator at infinity is set rather than added to, and f29_madd's `false` return is taken at every mixed addition -- equal: double the accumulator (it holds
-// that very point), opposite: back to infinity -- in both groups (add_point).  G::add is the complete f29_pt_add / f29g2_pt_add.
+// The additions.  Unlike a prover's bases these points are an adversary's, or merely unlucky, and an addition can meet equal points, opposite points and infinity.  So:
+// an all-zero point is skipped, an accumulator at infinity is set rather than added to, and f29_madd's `false` return is taken at every mixed addition -- equal: double
+// the accumulator (it holds that very point), opposite: back to infinity -- in both groups (add_point).  G::add is the complete f29_pt_add / f29g2_pt_add.
+// Where the GPU tests reach each case ("setup": tests/test_gpu_ptau_setup.py; "repeats": tests/test_gpu_ptau_setup_repeats.py, named by the rows of
+// tests/repeat_circuits.py, whose A and B1 rows are G1 and whose B2 row of the same shape is G2):
+//   infinity              G1, G2: setup and tests/test_gpu_ptau_prepare.py with tau a root of unity (all but one Lagrange point are infinity, and the monomial points
+//                         repeat); repeats `pmp` (set again after P - P), `empty`, and every row but the long ones with tau a root of unity
+//   add_point, equal      G1: setup, the K rows with alpha = beta.  G1, G2: repeats `pp`, `p5` (then lean additions onto what G::dbl left), `kk` (two scaled terms), and
+//                         the first two terms of every segment of the long rows (zkc_ptau_acc)
+//   add_point, opposite   G1: setup, the K rows with alpha = -beta.  G1, G2: repeats `pm`, `pmp`, `k-k`, `half` (zkc_ptau_acc)
+//   G::add, equal         G1, G2: repeats `red_eq` at the first reduction step, `red_eq2` at the second, `red3_eq` at the third (zkc_ptau_red)
+//   G::add, opposite      G1, G2: repeats `red_op` (zkc_ptau_red)
+// The double-and-add users of add_point (zkc_ptau_scale, the load kernel of zkc_ecntt.hip) meet no equal or opposite operand for a scalar below r, so no test takes the
+// `false` return there; zkc_p2_scale_g1 walks signed digits and meets it for the scalar r - 2 alone (zkc_phase2.hip).
 #pragma once
 #include "zkc_f29.h"
 #include "zkc_f29_g1.h"

@@ -16,13 +16,15 @@
 //                        the products become affine through the batched inversion of the fixed-base engine and land behind the points read
 //             accumulate one lane per segment: mixed additions of +-P into an XYZZ partial sum
 //             reduce     one lane per up to RED partial sums of one row (full additions), repeated until every row has one: rows of more than SEG x RED terms -- the
-//                        partition-of-unity sums from domain 2^11 on, wire 0 of a large circuit -- take a second step
+//                        partition-of-unity sums from domain 2^11 on, wire 0 of a large circuit -- take a second, and from 32 769 terms a third
 //             then affine again, and home in row order.
 //   4 (host)  the sanity checks, csHash, and the shared writer (zkc_setup_write.h).
 // Every loop of every kernel is bounded by a count the host computed; nothing waits on a flag.  SEG, RED are the only tunables.
 //
-// The additions: every exceptional case is live and handled, see the head of zkc_point_ops.h.  Here K_s adds alpha L_c and beta L_c, which are EQUAL when alpha = beta and
-// OPPOSITE when alpha = -beta.
+// The additions: every exceptional case is handled, and the head of zkc_point_ops.h names the test that reaches each, per group.  Here K_s adds alpha L_c and beta L_c,
+// which are EQUAL when alpha = beta and OPPOSITE when alpha = -beta (G1 only: tests/test_gpu_ptau_setup.py).  A wire named twice in one linear combination stays two terms
+// (zkc_r1cs_parse.h), so a row can hold one point many times: tests/test_gpu_ptau_setup_repeats.py makes such rows and through them reaches, in G1 and in G2, equal and
+// opposite points in the accumulation, equal and opposite partial sums at the first, second and third reduction step, and rows at each side of the third step.
 #include <algorithm>
 #include <cstring>
 #include <functional>
