@@ -304,7 +304,8 @@ int zkc_debug_pairing_dev(zkc_ctx* ctx, const uint8_t* g1, const uint8_t* g2, co
  * MockInputs; ts_inputs/src/inputs.ts:38-88).  arbo tree semantics: leaf = H(key, value, 1), node = H(left, right), path bit i = bit i (LSB first) of the key, an empty
  * subtree is 0, a subtree holding one leaf is that leaf's hash.  The trie is split on the host, every hash runs on the GPU (leaves in one launch, inner nodes one launch per
  * depth), sibling lists are written on the device: 8 192 voters in tens of milliseconds.  All values 32-byte little-endian, standard form, below r; host buffers.
- * zkc_poseidon_batch   : n_inputs in {2, 3, 4}; inputs B x n_inputs x 32 B, out B x 32 B.
+ * zkc_poseidon_batch   : n_inputs in {2, 3, 4}; inputs B x n_inputs x 32 B, out B x 32 B.  The one entry point of this block that does not refuse a word at or above r:
+ *                        it takes any 256-bit word and hashes its residue mod r, H(r, 1) = H(0, 1) (tests/test_gpu_census_values.py).
  * zkc_smt_build        : one tree over n (key, value) pairs with distinct keys -> root (32 B), siblings (n x (nLevels + 1) x 32 B, zero-padded, may be NULL: leaf i's sibling
  *                        at level l in slot i (nLevels + 1) + l) and depths (levels above leaf i; may be NULL).  ZKC_ERR_BAD_ARG: duplicate keys, or two keys that share
  *                        their first nLevels path bits.

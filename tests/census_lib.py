@@ -1,5 +1,6 @@
-"""What the census GPU tests share (test_gpu_smt_check, test_gpu_census_tree, _delete, _snapshot): byte helpers, the ZKC_SMT_* verdicts, key sets, the comparison of
-a resident tree with zkc_smt_build over the same set, and a pure-Python proof climber over the oracle's Poseidon.  A plain module beside oracle_lib.py: no fixtures."""
+"""What the census GPU tests share (test_gpu_smt_check, test_gpu_census_tree, _delete, _snapshot, _values): byte helpers, the ZKC_SMT_* verdicts, key sets, the comparison of
+a resident tree with zkc_smt_build over the same set, a pure-Python proof climber over the oracle's Poseidon, and voters' circuit inputs from arbo_model trees.  A plain
+module beside oracle_lib.py: no fixtures."""
 import oracle_lib as ol
 
 W = ol.le32
@@ -32,6 +33,22 @@ def oracle_verdict(key, value, sibs, root, nl, old_key=None, is_old0=False):
     for l in range(d - 1, -1, -1):
         cur = ol.poseidon([sibs[l], cur]) if (key >> l) & 1 else ol.poseidon([cur, sibs[l]])
     return VALID if cur == root else ROOT_MISMATCH
+
+
+def model_voters(election_id, address, password, signature, avail, vote, vote_hash, nl):
+    """The 12-key circuit inputs (oracle_lib.INPUT_KEYS, decimal strings) of voters whose census tree (address -> available weight) and SIK tree (address ->
+    H(address, password, signature)) are arbo_model trees: no GPU code on this side.  Lists of ints; vote_hash: pairs; election_id: a pair."""
+    import arbo_model as am
+    sik = [ol.poseidon([a, p, s]) for a, p, s in zip(address, password, signature)]
+    ckv, skv = dict(zip(address, avail)), dict(zip(address, sik))
+    out = []
+    for i, a in enumerate(address):
+        v = {'electionId': list(election_id), 'nullifier': ol.poseidon([signature[i], password[i], election_id[0], election_id[1]]), 'availableWeight': avail[i],
+             'voteHash': list(vote_hash[i]), 'sikRoot': am.root(skv, nl), 'censusRoot': am.root(ckv, nl), 'address': a, 'password': password[i],
+             'signature': signature[i], 'voteWeight': vote[i], 'censusSiblings': am.proof(ckv, nl, a)[0], 'sikSiblings': am.proof(skv, nl, a)[0]}
+        assert list(v) == ol.INPUT_KEYS
+        out.append({k: [str(y) for y in x] if isinstance(x, list) else str(x) for k, x in v.items()})
+    return out
 
 
 def tree_keys(rng, nl, n, avoid=()):
