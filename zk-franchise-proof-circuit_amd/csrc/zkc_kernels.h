@@ -29,9 +29,11 @@ __device__ __forceinline__ Fr mv_term(const Fr* __restrict__ val, const Fr* __re
 
 // ---- zkc_ntt.hip (launched from zkc_prove.hip) ----
 extern "C" __global__ void zkc_wtns_mont(const Fr* wtns_std, size_t wtns_stride, Fr* wm, size_t wm_stride, uint32_t nv);
+extern "C" __global__ void zkc_wtns_mont_list(const Fr* wtns_std, size_t wtns_stride, Fr* wm, size_t wm_stride, const uint32_t* list, uint32_t nlist);
+extern "C" __global__ void zkc_abc_fill(const uint4* tmpl, uint4* abc, uint32_t per);
 extern "C" __global__ void zkc_matvec_jds(const uint32_t* perm, const uint32_t* rowlen, const uint32_t* jdptr, const uint32_t* col, const Fr* val, const Fr* wtns_std,
-                                          size_t wtns_stride, Fr* abc, int n, uint32_t nlong, const Fr* wm_all, size_t wm_stride);
-extern "C" __global__ void zkc_pointwise_mul(Fr* abc, int n);
+                                          size_t wtns_stride, Fr* abc, int n, uint32_t nlong, const Fr* wm_all, size_t wm_stride, const uint32_t* list, uint32_t nrows);
+extern "C" __global__ void zkc_pointwise_mul(Fr* abc, int n, const uint32_t* list, uint32_t count);
 extern "C" __global__ void zkc_join_abc(const Fr* abc, uint32_t* p_std, int n);
 
 // ---- zkc_witness.hip: witness generation and batched Poseidon (launched from zkc_api.hip) ----

@@ -40,16 +40,35 @@ zkc_wtns_mont(const Fr* __restrict__ wtns_std, size_t wtns_stride, Fr* __restric
     for (int k = 0; k < 8; k++) r2.v[k] = FrParams::r2[k];
     st_fr(wm + (size_t)blockIdx.y * wm_stride + i, ld_fr(wtns_std + (size_t)blockIdx.y * wtns_stride + i) * r2);
 }
+// [abc fold] the same for the `nlist` wires of `list` only (the wires that the voter rows of a folded pass read, zkc_abc_rows.h): wm keeps its indexing by wire
+extern "C" __global__ void __launch_bounds__(256)
+zkc_wtns_mont_list(const Fr* __restrict__ wtns_std, size_t wtns_stride, Fr* __restrict__ wm, size_t wm_stride, const uint32_t* __restrict__ list, uint32_t nlist) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nlist) return;
+    const uint32_t i = list[e];
+    Fr r2;
+#pragma unroll
+    for (int k = 0; k < 8; k++) r2.v[k] = FrParams::r2[k];
+    st_fr(wm + (size_t)blockIdx.y * wm_stride + i, ld_fr(wtns_std + (size_t)blockIdx.y * wtns_stride + i) * r2);
+}
+// [abc fold] every proof's [3][n] block := the key's template abc (per = uint4 per block); the listed rows are then computed over it
+extern "C" __global__ void __launch_bounds__(256)
+zkc_abc_fill(const uint4* __restrict__ tmpl, uint4* __restrict__ abc, uint32_t per) {
+    uint4* __restrict__ dst = abc + (size_t)blockIdx.y * per;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < per; i += gridDim.x * blockDim.x) dst[i] = tmpl[i];
+}
+// [abc fold] list != nullptr: the kernel walks the `nrows` sorted positions list[0 .. nrows) instead of all 2 n (ascending, so the first `nlong` of them are long rows and
+// neighbouring lanes still hold neighbouring positions of equal or nearly equal length); every other row of abc is left as it is (the template's, zkc_abc_fill)
 extern "C" __global__ void __launch_bounds__(256)
 zkc_matvec_jds(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ rowlen, const uint32_t* __restrict__ jdptr,
                const uint32_t* __restrict__ col, const Fr* __restrict__ val, const Fr* __restrict__ wtns_std, size_t wtns_stride,
-               Fr* __restrict__ abc, int n, uint32_t nlong, const Fr* __restrict__ wm_all, size_t wm_stride) {
+               Fr* __restrict__ abc, int n, uint32_t nlong, const Fr* __restrict__ wm_all, size_t wm_stride, const uint32_t* __restrict__ list, uint32_t nrows) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;      // rows [0,n) = A, [n,2n) = B ; abc layout [proof][3][n]
     const Fr* __restrict__ w = wtns_std + (size_t)blockIdx.y * wtns_stride;
     const Fr* __restrict__ wm = wm_all ? wm_all + (size_t)blockIdx.y * wm_stride : nullptr;
     Fr acc = Fr::zero();
     if ((t >> 6) < nlong) {                         // wave-uniform
-        const uint32_t r = t >> 6, len = rowlen[r];
+        const uint32_t r = list ? list[t >> 6] : t >> 6, len = rowlen[r];
         for (uint32_t k = lane; k < len; k += 64) { const uint32_t idx = jdptr[k] + r; acc = acc + mv_term(val, w, wm, idx, col[idx]); }
         for (int d = 32; d > 0; d >>= 1) {
             Fr o;
@@ -60,18 +79,21 @@ zkc_matvec_jds(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ r
         if (lane == 0) st_fr(abc + (size_t)blockIdx.y * 3 * n + perm[r], acc);
         return;
     }
-    const uint32_t r = t - nlong * 63u;             // = nlong + (t - 64 nlong)
-    if (r >= 2u * (uint32_t)n) return;
+    const uint32_t e = t - nlong * 63u;             // = nlong + (t - 64 nlong)
+    if (e >= nrows) return;
+    const uint32_t r = list ? list[e] : e;
     const uint32_t len = rowlen[r];
     for (uint32_t k = 0; k < len; k++) { const uint32_t idx = jdptr[k] + r; acc = acc + mv_term(val, w, wm, idx, col[idx]); }
     st_fr(abc + (size_t)blockIdx.y * 3 * n + perm[r], acc);
 }
-// c = a * b
+// c = a * b ; list != nullptr: for the `count` constraints of `list` only
 extern "C" __global__ void __launch_bounds__(256)
-zkc_pointwise_mul(Fr* __restrict__ abc, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+zkc_pointwise_mul(Fr* __restrict__ abc, int n, const uint32_t* __restrict__ list, uint32_t count) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     Fr* a = abc + (size_t)blockIdx.y * 3 * n;
-    if (i < n) st_fr(a + 2 * (size_t)n + i, ld_fr(a + i) * ld_fr(a + n + i));
+    if (e >= count) return;
+    const uint32_t i = list ? list[e] : e;
+    st_fr(a + 2 * (size_t)n + i, ld_fr(a + i) * ld_fr(a + n + i));
 }
 // joinABC: p = a*b - c, written in STANDARD form (the H-MSM reads scalar digits from it).  In radix 2^29: the three operands enter as
 // 32 x value (their R' form), (a b + (D - c) 2^261) / 2^261 is one fused product (zkc_f29.h), and a second reduction of the nine limbs alone

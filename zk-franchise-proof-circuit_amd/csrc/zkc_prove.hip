@@ -21,13 +21,25 @@ using namespace zkc;
 
 // buildABC for `nb` proofs on stream `mv` (zkc_ntt.hip): unit coefficients add the wire's Montgomery form, made once per wire in the lane's transform scratch (d_t is idle here:
 // the pair runs in place, the two-transform form writes it afterwards) when it is large enough for nVars elements per proof
-static void matvec_launch(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv) {
+// [abc fold] d_abc / d_wm: where the products and the wires' Montgomery forms go (a lane's d_abc and d_t; the key's template buffers once, abc_template).  al != nullptr (a folded
+// pass, abc_rows below): every proof's block is first the key's template abc, then the SAME three kernels run over the voter rows of the pass' depths and the wires those read
+static void matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr) {
     const uint32_t n = zk->n, nv = zk->nVars;
     const bool units = zk->n_unit_coeffs > 0 && nv <= 3 * (size_t)n && sw::on<sw::ZKC_MATVEC_UNITS>();
-    if (units) hipLaunchKernelGGL(zkc_wtns_mont, dim3((nv + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)d_wtns0, (size_t)nv, L.d_t, 3 * (size_t)n, nv);
+    const Fr* wm = units ? (const Fr*)d_wm : (const Fr*)nullptr;
+    if (al) {
+        const uint32_t per = 6 * n;                                                  // uint4 per [3][n] block
+        hipLaunchKernelGGL(zkc_abc_fill, dim3((per + 1023) / 1024, nb), dim3(256), 0, mv, (const uint4*)zk->fold.d_abc_tmpl, (uint4*)d_abc, per);
+        if (units && al->nW) hipLaunchKernelGGL(zkc_wtns_mont_list, dim3((al->nW + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)d_wtns0, (size_t)nv, d_wm, 3 * (size_t)n, al->d + al->offW, al->nW);
+        if (al->nrows) hipLaunchKernelGGL(zkc_matvec_jds, dim3((al->nrows + 63 * al->nlong + 255) / 256, nb), dim3(256), 0, mv, zk->d_perm, zk->d_rowlen, zk->d_jdptr, zk->d_col, zk->d_val,
+                                          (const Fr*)d_wtns0, (size_t)nv, d_abc, (int)n, al->nlong, wm, 3 * (size_t)n, (const uint32_t*)al->d, al->nrows);
+        if (al->nC) hipLaunchKernelGGL(zkc_pointwise_mul, dim3((al->nC + 255) / 256, nb), dim3(256), 0, mv, d_abc, (int)n, (const uint32_t*)(al->d + al->offC), al->nC);
+        return;
+    }
+    if (units) hipLaunchKernelGGL(zkc_wtns_mont, dim3((nv + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)d_wtns0, (size_t)nv, d_wm, 3 * (size_t)n, nv);
     hipLaunchKernelGGL(zkc_matvec_jds, dim3((2 * n + 63 * zk->nlong + 255) / 256, nb), dim3(256), 0, mv, zk->d_perm, zk->d_rowlen, zk->d_jdptr, zk->d_col, zk->d_val,
-                       (const Fr*)d_wtns0, (size_t)nv, L.d_abc, (int)n, zk->nlong, units ? (const Fr*)L.d_t : (const Fr*)nullptr, 3 * (size_t)n);
-    hipLaunchKernelGGL(zkc_pointwise_mul, dim3((n + 255) / 256, nb), dim3(256), 0, mv, L.d_abc, (int)n);
+                       (const Fr*)d_wtns0, (size_t)nv, d_abc, (int)n, zk->nlong, wm, 3 * (size_t)n, (const uint32_t*)nullptr, 2 * n);
+    hipLaunchKernelGGL(zkc_pointwise_mul, dim3((n + 255) / 256, nb), dim3(256), 0, mv, d_abc, (int)n, (const uint32_t*)nullptr, n);
 }
 static constexpr uint32_t MATVEC_LONG = 16;      // rows with more coefficients are summed by a whole wave
 
@@ -56,6 +68,12 @@ zkc_fold_check(WitnessLayout L, const uint32_t* __restrict__ wtns, const uint32_
     const uint4* t = reinterpret_cast<const uint4*>(tmpl) + 2 * (size_t)start;
     uint32_t diff = 0;
     for (int i = threadIdx.x; i < 2 * (end - start); i += 64) { uint4 x = w[i], y = t[i]; diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w); }
+    // [abc fold] wire 0 (the constant 1) counts with the census tree's old-key block: a witness that carries anything else there is a foreign one and unfolds its pass, so a
+    // row over wire 0 and folded levels alone is the template's row (zkc_abc_rows.h)
+    if (g == n - 1 && tree == 0 && threadIdx.x < 2) {
+        const uint4 x = reinterpret_cast<const uint4*>(wtns + (size_t)b * L.nWires * 8)[threadIdx.x], y = reinterpret_cast<const uint4*>(tmpl)[threadIdx.x];
+        diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+    }
     const unsigned long long any = __ballot(diff != 0);
     if (threadIdx.x == 0) flags[((size_t)b * 2 + tree) * n + g] = any ? 1u : 0u;
 }
@@ -85,6 +103,8 @@ extern "C" void zkc_zkey_free(zkc_zkey* zk) {
                     zk->d_tblDelta1, zk->d_tblAlpha1, zk->d_tblBeta1, zk->d_tblDelta2, zk->d_fb4, zk->d_fb4g2, zk->d_depths};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& kv : zk->fold.vmaps) if (kv.second.d) (void)hipFree(kv.second.d);
+    for (auto& kv : zk->fold.abc_rows) if (kv.second.d) (void)hipFree(kv.second.d);
+    if (zk->fold.d_abc_tmpl) (void)hipFree(zk->fold.d_abc_tmpl);
     for (void* q : {(void*)zk->fold.d_foldA, (void*)zk->fold.d_foldB1, (void*)zk->fold.d_foldC, (void*)zk->fold.d_foldB2}) if (q) (void)hipFree(q);
     if (zk->h_depths) (void)hipHostFree(zk->h_depths);
     for (auto& c : zk->call) { for (void* q : {(void*)c.d_rs, (void*)c.d_proofs, (void*)c.d_flags, (void*)c.d_status3}) if (q) (void)hipFree(q); if (c.h_flags) (void)hipHostFree(c.h_flags); if (c.h_out) (void)hipHostFree(c.h_out); if (c.h_rs) (void)hipHostFree(c.h_rs); if (c.h_xyzz) (void)hipHostFree(c.h_xyzz); if (c.h_early) (void)hipHostFree(c.h_early); if (c.d_xyzz) (void)hipFree(c.d_xyzz); for (hipEvent_t e : c.ev_done) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : c.ev_chunk) (void)hipEventDestroy(e); }
@@ -252,6 +272,15 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
         ZKC_UP(zk->d_perm, perm.data(), nrows * 4); ZKC_UP(zk->d_rowlen, rowlen.data(), nrows * 4); ZKC_UP(zk->d_jdptr, jdptr.data(), jdptr.size() * 4);
         ZKC_UP(zk->d_col, jcol.data(), jcol.size() * 4);
         ZKC_UP(zk->d_val, jval.data(), jval.size() * sizeof(Fr));
+        // [abc fold] a key that folds: which of its rows a voter can change (zkc_abc_rows.h); the rows stay on the host for the per-depth lists (abc_rows)
+        if (zk->nLevels >= 0 && sw::on<sw::ZKC_ABC_FOLD>()) {
+            const WitnessLayout WL = WitnessLayout::make(zk->nLevels);
+            const std::vector<std::pair<int, int>> rg[2] = {abc::fold_group_ranges(WL, 0), abc::fold_group_ranges(WL, 1)};
+            zk->fold.abc_cls = abc::classify_rows(nrows, rowptr.data(), col.data(), abc::wire_groups(nv, rg), WL.n);
+            zk->fold.abc_rowptr = std::move(rowptr); zk->fold.abc_col = std::move(col); zk->fold.abc_perm = perm;
+            if (sw::on<sw::ZKC_TRACE_HOST>()) { const abc::RowCounts rc0 = abc::row_counts(zk->fold.abc_cls);
+                fprintf(stderr, "[zkc host] abc rows: %zu of %zu A/B rows never constant, %zu constant when every level folds\n", rc0.never, nrows, rc0.constant_at_0); }
+        }
     }
     // ---- twiddles and the coset/1-over-n scale ----
     {
@@ -364,15 +393,7 @@ extern "C" int zkc_zkey_info(const zkc_zkey* zk, uint32_t* nVars, uint32_t* nPub
 }
 
 // ---- constant folding tables: per-level sums of template_value * base for every section, then suffix sums ----
-static std::vector<std::pair<int, int>> fold_group_ranges(const WitnessLayout& L, int tree) {   // [start, end) wire ranges, groups 0..n-1
-    std::vector<std::pair<int, int>> r; const int n = L.n, blk = tree == 0 ? L.off_census : L.off_sikver;
-    for (int g = 0; g < n - 1; g++) {
-        const int nctrl = (g == n - 3) + (g > 0 && g < n - 2) + 1;
-        r.push_back({blk + L.lvl_off(g) + nctrl, blk + (g + 1 < n - 1 ? L.lvl_off(g + 1) : L.lvl_off(n - 1))});
-    }
-    r.push_back({blk + L.off_n2bold, blk + L.off_n2bold + 253 + 127 + 133});
-    return r;
-}
+static std::vector<std::pair<int, int>> fold_group_ranges(const WitnessLayout& L, int tree) { return abc::fold_group_ranges(L, tree); }   // [start, end) wire ranges, groups 0..n-1 (zkc_abc_rows.h)
 template <class X> static void suffix_sums(std::vector<X>& suf, const X* g, int n) {   // suf[D] = sum_{k >= D} g[k], k < n-1 ; suf[n-1] = inf
     suf.assign(n, X::inf());
     for (int D = n - 2; D >= 0; D--) suf[D] = xyzz_add(suf[D + 1], g[D]);
@@ -485,20 +506,51 @@ static int nofold_vmap(zkc_zkey* zk, zkc_zkey::Fold::VMap* out) {
     return ZKC_OK;
 }
 
+// [abc fold] the template's abc, once per key at its first folded call: buildABC's own kernels (matvec_launch, the form every pass takes) over the template witness, so a row
+// copied from here holds the very bits the pass would have computed for it.  Ends with ctx->stream synchronised: the lanes' streams may read the block afterwards
+static int abc_template(zkc_zkey* zk, const uint32_t* tmpl) {
+    if (zk->fold.d_abc_tmpl) return ZKC_OK;
+    zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n; Fr *d_abc = nullptr, *d_wm = nullptr; int rc;
+    if ((rc = dmalloc(ctx, &d_abc, 3 * (size_t)n))) return rc;
+    if ((rc = dmalloc(ctx, &d_wm, 3 * (size_t)n))) { (void)hipFree(d_abc); return rc; }
+    matvec_launch(zk, d_abc, d_wm, tmpl, 1, ctx->stream);
+    hipError_t e = hipGetLastError(); if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_wm);
+    if (e != hipSuccess) { (void)hipFree(d_abc); return zkc_fail(ctx, ZKC_ERR_HIP, std::string("abc_template: ") + hipGetErrorString(e)); }
+    zk->fold.d_abc_tmpl = d_abc;
+    return ZKC_OK;
+}
+// [abc fold] the voter rows of a pass whose proofs fold at depths up to (Dc, Ds), cached per pair like the wire lists above
+static int abc_rows(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::AbcRows* out) {
+    auto& f = zk->fold;
+    auto it = f.abc_rows.find({Dc, Ds});
+    if (it != f.abc_rows.end()) { *out = it->second; return ZKC_OK; }
+    zkc_ctx* ctx = zk->ctx;
+    const abc::VoterRows v = abc::voter_rows(f.abc_cls, f.abc_perm.data(), zk->nlong, zk->n, f.abc_rowptr.data(), f.abc_col.data(), zk->nVars, Dc, Ds);
+    zkc_zkey::Fold::AbcRows m; m.nrows = (uint32_t)v.rows.size(); m.nlong = v.nlong; m.offC = m.nrows; m.nC = (uint32_t)v.crows.size(); m.offW = m.offC + m.nC; m.nW = (uint32_t)v.wires.size();
+    std::vector<uint32_t> all(v.rows); all.insert(all.end(), v.crows.begin(), v.crows.end()); all.insert(all.end(), v.wires.begin(), v.wires.end());
+    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&m.d, all.size() * 4 + 4));
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, all.data(), all.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (sw::on<sw::ZKC_TRACE_HOST>()) fprintf(stderr, "[zkc host] abc rows at depths (%d, %d): %u of %zu A/B rows listed (%u long), %u C rows, %u wires\n", Dc, Ds, m.nrows, f.abc_cls.size(), m.nlong, m.nC, m.nW);
+    f.abc_rows[{Dc, Ds}] = m; *out = m;
+    return ZKC_OK;
+}
+
 // stages a2..a4 for `nb` proofs: leaves (A'B' - C') on the odd coset in d_p[q] (standard form), q < nb
-// buildABC (a2) for `nb` proofs on stream `mv`: A_w, B_w by the jagged-diagonal mat-vec, C_w = A_w o B_w
-static int h_matvec_dev(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv) {
+// buildABC (a2) for `nb` proofs on stream `mv`: A_w, B_w by the jagged-diagonal mat-vec, C_w = A_w o B_w (al: over the voter rows of a folded pass only, matvec_launch)
+static int h_matvec_dev(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr) {
     zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n, nv = zk->nVars;
     zkc_prof_scope _ps(ctx, ZKC_PROF_MATVEC, (uint64_t)nb * ((uint64_t)zk->nCoeffs * 68 + 3ull * n * 32), mv);
-    matvec_launch(zk, L, d_wtns0, nb, mv);
+    matvec_launch(zk, L.d_abc, L.d_t, d_wtns0, nb, mv, al);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     return ZKC_OK;
 }
 // stages a2..a4 for `nb` proofs: leaves (A'B' - C') on the odd coset in d_p[q] (standard form), q < nb.  with_matvec = false: buildABC has been
 // run already (on another stream; L.st has been made to wait for it)
-static int h_evals_dev(zkc_zkey* zk, zkc_lane& L, hipStream_t st, const uint32_t* d_wtns0, int nb, bool with_matvec = true) {
+static int h_evals_dev(zkc_zkey* zk, zkc_lane& L, hipStream_t st, const uint32_t* d_wtns0, int nb, bool with_matvec = true, const zkc_zkey::Fold::AbcRows* al = nullptr) {
     zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n;
-    if (with_matvec) { int rc0 = h_matvec_dev(zk, L, d_wtns0, nb, st); if (rc0) return rc0; }
+    if (with_matvec) { int rc0 = h_matvec_dev(zk, L, d_wtns0, nb, st, al); if (rc0) return rc0; }
     zkc_prof_scope _pn(ctx, ZKC_PROF_NTT, (uint64_t)nb * (6ull * 2 * n * 32 + 4ull * n * 32), st);   // 6 transforms r+w, joinABC
     int rc;
     if (!sw::on<sw::ZKC_NTT_SEPARATE>() && zk->logn >= 12 && zk->logn <= 27) {      // (the switch is diagnostics: the round-1 path, two full transforms, four HBM round trips)
@@ -520,7 +572,7 @@ extern "C" int zkc_debug_stage(zkc_zkey* zk, const void* d_wtns, int stage, void
     { int rc0 = lanes_ensure(zk, 1, 0, 1); if (rc0) return rc0; }
     zkc_lane& L0 = ctx->lanes[0]; const hipStream_t st0 = lane_st(zk, L0).st;
     if (stage == 0) {
-        matvec_launch(zk, L0, (const uint32_t*)d_wtns, 1, st0);
+        matvec_launch(zk, L0.d_abc, L0.d_t, (const uint32_t*)d_wtns, 1, st0);
         ZKC_HIP_CHECK(ctx, hipGetLastError());
         ZKC_HIP_CHECK(ctx, hipMemcpyAsync(host_out, L0.d_abc, 96ull * n, hipMemcpyDeviceToHost, st0));
     } else {
@@ -601,6 +653,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         L = WitnessLayout::make(zk->nLevels);
         if ((rc = fold_prepare(zk))) return rc;
         tmpl = zkc_get_template(ctx, zk->nLevels); if (!tmpl) return ZKC_ERR_HIP;
+        if (!zk->fold.abc_cls.empty() && (rc = abc_template(zk, tmpl))) return rc;
         const size_t nflags = (size_t)B * 2 * L.n;
         if (CS.flags_cap < nflags) {                                   // (the slot is idle: nothing reads its old buffers)
             if (CS.d_flags) { ZKC_HIP_CHECK(ctx, hipFree(CS.d_flags)); ZKC_HIP_CHECK(ctx, hipHostFree(CS.h_flags)); CS.d_flags = CS.h_flags = nullptr; CS.flags_cap = 0; }
@@ -712,7 +765,13 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         if (mv_done) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_mv, 0));
         // (tried for passes of a few proofs while their G2 side was the longer chain: G2 enqueued first and its accumulation not held for the transforms -- its 1024 fat waves
         // then slowed buildABC and the first transform kernel threefold; with the 8-bit-window G2 table the G1 side is the longer one and goes first again)
-        if ((rc = h_evals_dev(zk, LN, st, w0, nb, !mv_done))) return rc;
+        // [abc fold] a folded pass: buildABC over the rows a voter of the pass' depths can change, the rest copied from the template.  (Dc, Ds) = the deepest proof of the pass per
+        // tree, so a listed-out row is constant for every proof of it.  A pass laid out early takes it too: its depths are its inputs', and prove_batch_finish refuses the call
+        // unless every accepted voter's witness folds at least that far (old-key flag clear, depth <= the early one <= the pass').  The prefetched buildABC of a one-lane call
+        // (below) is enqueued before its pass' depths are on the host and computes every row as before.
+        zkc_zkey::Fold::AbcRows ar; const bool abc_fold = fold && !mv_done && !zk->fold.abc_cls.empty() && zk->fold.d_abc_tmpl != nullptr;
+        if (abc_fold) { int Dc = 0, Ds = 0; for (int q = 0; q < nb; q++) { Dc = std::max(Dc, (int)dcq[q]); Ds = std::max(Ds, (int)dsq[q]); } if ((rc = abc_rows(zk, Dc, Ds, &ar))) return rc; }
+        if ((rc = h_evals_dev(zk, LN, st, w0, nb, !mv_done, abc_fold ? &ar : nullptr))) return rc;
         ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_ntt, st));
         tr[2] = now_ms();
         static thread_local MsmJobList j1, j2;     // 6 KB each: kept off the stack frame of a C-ABI entry point

@@ -3,6 +3,7 @@
 #include <cstring>
 #include "zkc_internal.h"
 #include "zkc_curve.h"
+#include "zkc_abc_rows.h"
 
 namespace zkc {
 // Pippenger window bits per section (signed digits).  Because the bases are pre-shifted per window (T[w][i] = 2^(c w) P_i), a
@@ -244,6 +245,13 @@ struct zkc_zkey {
         std::vector<uint8_t> infA, infB, infC;                                                  // base point is the point at infinity (zero polynomial)
         zkc::G1XYZZ *d_foldA = nullptr, *d_foldB1 = nullptr, *d_foldC = nullptr; zkc::G2XYZZ* d_foldB2 = nullptr;    // [1 + 2 n] each: base, suf[0][], suf[1][]
         bool ready = false;
+        // [abc fold] buildABC of a folded pass: the rows a voter cannot change are copied from the template's abc (zkc_abc_rows.h).  Host side, made at key load: the class of
+        // every A / B row and the rows themselves (compressed-row form by input row, the jagged-diagonal permutation); device side, at first use: the template's [3][n] block,
+        // made by buildABC's own kernels, and per pair of pass depths one allocation [voter rows as sorted positions | constraints whose C is formed | wires those rows read]
+        std::vector<zkc::abc::RowClass> abc_cls; std::vector<uint32_t> abc_rowptr, abc_col, abc_perm;
+        zkc::Fr* d_abc_tmpl = nullptr;
+        struct AbcRows { uint32_t* d = nullptr; uint32_t nrows = 0, nlong = 0, offC = 0, nC = 0, offW = 0, nW = 0; };
+        std::map<std::pair<int, int>, AbcRows> abc_rows;
     } fold;
 };
 

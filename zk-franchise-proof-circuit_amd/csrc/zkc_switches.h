@@ -68,7 +68,8 @@ constexpr long long ANY = LLONG_MIN;      // no bound on this side of a clamp
     X(ZKC_ACC_CHAIN,            OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: the G1 accumulations of a context's lanes are not chained one behind the other")                           \
     X(ZKC_REDUCE_STREAM,        ON_IF_ONE,   ANY, ANY,   PROCESS, "=1: the bucket reduction of a full pass runs on a stream of its own (the lanes then get that stream)")         \
     X(ZKC_MATVEC_UNITS,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: buildABC multiplies by its +-1 coefficients instead of adding the wire")                                   \
-    X(ZKC_MATVEC_INLINE,        SET,         ANY, ANY,   PROCESS, "set (any value, 0 included): buildABC of the next pass is not prefetched on the blinding stream")              \
+    X(ZKC_ABC_FOLD,             OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: buildABC of a folded pass computes every row instead of copying the voter-independent ones from the template") \
+    X(ZKC_MATVEC_INLINE,        SET,        ANY, ANY,   PROCESS, "set (any value, 0 included): buildABC of the next pass is not prefetched on the blinding stream")              \
     X(ZKC_MV_PREFETCH_AT_NTT,   ON_IF_ONE,   ANY, ANY,   PROCESS, "=1: that prefetch starts beside the pass' bucketing instead of beside its accumulation")                       \
     X(ZKC_EARLY_LAYOUT,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: one-pass calls of more than two voters wait for their fold flags instead of reading the depths off the inputs") \
     X(ZKC_NOFOLD_LISTS,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: unfolded passes keep the wires whose bases are at infinity")                                               \
