@@ -65,10 +65,14 @@ __device__ G1XYZZ var_mul29_g(const G1XYZZ& P, const uint32_t k[8], Acc29* __res
 }
 
 // the voter-independent part of a section's MSM for proof q (constant folding, zkc_prove.hip): base + sum over the folded levels of both trees
+// [top fold] ... plus the sums of the slots that stand for the proof's top levels of either tree (slots: the key's table of this section, FinalizeArgs::tc / ts)
 template <class P>
-__device__ P fold_const(const P* __restrict__ tab, const FinalizeArgs& a, int q) {
+__device__ P fold_const(const P* __restrict__ tab, const P* __restrict__ slots, const FinalizeArgs& a, int q) {
     if (a.dc[q] == 255) return P::inf();
-    return xyzz_add(tab[0], xyzz_add(tab[1 + a.dc[q]], tab[1 + a.fold_n + a.ds[q]]));
+    P k = xyzz_add(tab[0], xyzz_add(tab[1 + a.dc[q]], tab[1 + a.fold_n + a.ds[q]]));
+    if (a.tc[q] != top::NO_SLOT) k = xyzz_add(k, slots[a.tc[q]]);
+    if (a.ts[q] != top::NO_SLOT) k = xyzz_add(k, slots[a.ts[q]]);
+    return k;
 }
 // One workgroup of four waves per proof, one task per wave so that the three independent latency chains run side by side:
 //   wave 0: s A' and r B1' (lanes 0, 1; variable base), then piC once everything else has arrived
@@ -86,7 +90,7 @@ zkc_finalize(FinalizeArgs a) {
     const int nq = gridDim.x;                         // results of a pass: H_0 .. H_{nq-1}, then A_q, B1_q, C_q per proof
     uint8_t* out = a.out + 256 * (size_t)q;
     if (wave == 0 && lane < 2) {
-        const G1XYZZ P = lane == 0 ? xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a, q)) : xyzz_add(a.r1[nq + 3 * q + 1], fold_const(a.foldB1, a, q));
+        const G1XYZZ P = lane == 0 ? xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a.topA, a, q)) : xyzz_add(a.r1[nq + 3 * q + 1], fold_const(a.foldB1, a.topB1, a, q));
         sh[lane] = var_mul29(P, lane == 0 ? s : r, tab[lane]);                                 // s A' , r B1'
     } else if (wave == 1 && lane < 5) {
         uint32_t k[8];
@@ -99,18 +103,18 @@ zkc_finalize(FinalizeArgs a) {
         const G1XYZZ v = fb_mul<Fq>(tb, k);
         sh[2 + lane] = v;
         if (lane == 0) {        // piA = A' + alpha + r delta
-            const G1XYZZ A = xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a, q));
+            const G1XYZZ A = xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a.topA, a, q));
             G1Affine p = xyzz_to_affine(xyzz_add(xyzz_add_affine(A, a.alpha1), v));
             store_fq_std(out, p.x); store_fq_std(out + 32, p.y);
         }
     } else if (wave == 2 && lane == 0) {     // piB = B2' + beta2 + s delta2
         const G2XYZZ sd = fb_mul<Fq2>(a.tblDelta2, s);
-        G2Affine p = xyzz_to_affine(xyzz_add(xyzz_add_affine(xyzz_add(a.r2[q], fold_const(a.foldB2, a, q)), a.beta2), sd));
+        G2Affine p = xyzz_to_affine(xyzz_add(xyzz_add_affine(xyzz_add(a.r2[q], fold_const(a.foldB2, a.topB2, a, q)), a.beta2), sd));
         store_fq_std(out + 64, p.x.c0); store_fq_std(out + 96, p.x.c1); store_fq_std(out + 128, p.y.c0); store_fq_std(out + 160, p.y.c1);
     }
     __syncthreads();
     if (threadIdx.x == 0) {     // piC = C' + H + s A' + s alpha + r B1' + r beta1 + rs delta
-        G1XYZZ c = xyzz_add(xyzz_add(a.r1[nq + 3 * q + 2], fold_const(a.foldC, a, q)), a.r1[q]);
+        G1XYZZ c = xyzz_add(xyzz_add(a.r1[nq + 3 * q + 2], fold_const(a.foldC, a.topC, a, q)), a.r1[q]);
         c = xyzz_add(c, sh[0]); c = xyzz_add(c, sh[5]); c = xyzz_add(c, sh[1]); c = xyzz_add(c, sh[6]); c = xyzz_add(c, sh[4]);
         G1Affine p = xyzz_to_affine(c);
         store_fq_std(out + 192, p.x); store_fq_std(out + 224, p.y);
@@ -135,7 +139,7 @@ zkc_finalize_products(FinalizeArgs a, int nq) {
     G2XYZZ* res2 = reinterpret_cast<G2XYZZ*>(res1 + 7 * (size_t)nq);
     Acc29* tabs = reinterpret_cast<Acc29*>(res2 + nq);
     if (task < 2) {
-        const G1XYZZ P = task == 0 ? xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a, q)) : xyzz_add(a.r1[nq + 3 * q + 1], fold_const(a.foldB1, a, q));
+        const G1XYZZ P = task == 0 ? xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a.topA, a, q)) : xyzz_add(a.r1[nq + 3 * q + 1], fold_const(a.foldB1, a.topB1, a, q));
         res1[(size_t)task * nq + q] = var_mul29_g(P, task == 0 ? s : r, tabs + ((size_t)task * nq + q) * 16);                 // s A' , r B1'
     } else if (task == 3) {
         return;                                                            // s delta in G1 is not part of any proof element (slot kept so that the task numbers read like the formula)
@@ -160,17 +164,17 @@ zkc_finalize_combine(FinalizeArgs a, int nq) {
     const G2XYZZ* res2 = reinterpret_cast<const G2XYZZ*>(res1 + 7 * (size_t)nq);
     uint8_t* out = a.out + 256 * (size_t)q;
     if (role == 0) {            // piA = A' + alpha + r delta
-        const G1XYZZ A = xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a, q));
+        const G1XYZZ A = xyzz_add(a.r1[nq + 3 * q + 0], fold_const(a.foldA, a.topA, a, q));
         G1Affine p = xyzz_to_affine(xyzz_add(xyzz_add_affine(A, a.alpha1), res1[2 * (size_t)nq + q]));
         store_fq_std(out, p.x); store_fq_std(out + 32, p.y);
     } else if (role == 1) {     // piC = C' + H + s A' + s alpha + r B1' + r beta1 + rs delta     (same order of additions as the one-wave-per-task kernel)
-        G1XYZZ c = xyzz_add(xyzz_add(a.r1[nq + 3 * q + 2], fold_const(a.foldC, a, q)), a.r1[q]);
+        G1XYZZ c = xyzz_add(xyzz_add(a.r1[nq + 3 * q + 2], fold_const(a.foldC, a.topC, a, q)), a.r1[q]);
         c = xyzz_add(c, res1[0 * (size_t)nq + q]); c = xyzz_add(c, res1[5 * (size_t)nq + q]); c = xyzz_add(c, res1[1 * (size_t)nq + q]);
         c = xyzz_add(c, res1[6 * (size_t)nq + q]); c = xyzz_add(c, res1[4 * (size_t)nq + q]);
         G1Affine p = xyzz_to_affine(c);
         store_fq_std(out + 192, p.x); store_fq_std(out + 224, p.y);
     } else {                    // piB = B2' + beta2 + s delta2
-        G2Affine p = xyzz_to_affine(xyzz_add(xyzz_add_affine(xyzz_add(a.r2[q], fold_const(a.foldB2, a, q)), a.beta2), res2[q]));
+        G2Affine p = xyzz_to_affine(xyzz_add(xyzz_add_affine(xyzz_add(a.r2[q], fold_const(a.foldB2, a.topB2, a, q)), a.beta2), res2[q]));
         store_fq_std(out + 64, p.x.c0); store_fq_std(out + 96, p.x.c1); store_fq_std(out + 128, p.y.c0); store_fq_std(out + 160, p.y.c1);
     }
 }

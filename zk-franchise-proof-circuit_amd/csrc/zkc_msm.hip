@@ -545,13 +545,14 @@ __device__ __forceinline__ uint32_t limb_of(const uint32_t k[8], int i) {
 template <class F>
 __global__ void __launch_bounds__(64)
 zkc_fold_mul(const Affine<F>* __restrict__ tbl, const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ wires, uint32_t nw,
-             int32_t pt_shift, XYZZ<F>* __restrict__ out) {
+             int32_t pt_shift, XYZZ<F>* __restrict__ out, uint32_t pt_mod) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nw) return;
     const uint32_t wire = wires[i];
     const uint4* sp = reinterpret_cast<const uint4*>(scalars + 8 * (size_t)wire); uint4 a = sp[0], b = sp[1];
     const uint32_t k[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    Affine<F> p = PointIO<F>::load(tbl + (uint32_t)((int32_t)wire - pt_shift));
+    // [top fold] pt_mod != 0: the scalars are several witnesses of pt_mod wires in a row, the point is that of the wire inside its witness
+    Affine<F> p = PointIO<F>::load(tbl + (uint32_t)((int32_t)(pt_mod ? wire % pt_mod : wire) - pt_shift));
     XYZZ<F> r = XYZZ<F>::inf();
     int top = -1;                                                    // the batch verifier's weights are 128 bits wide: start at the scalar's own top bit
 #pragma unroll
@@ -573,23 +574,24 @@ zkc_fold_gsum(const XYZZ<F>* __restrict__ in, const uint32_t* __restrict__ gstar
 }
 template <class F>
 static int fold_group_sums(zkc_ctx* ctx, const Affine<F>* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
-                           const uint32_t* d_gstart, uint32_t ngroups, XYZZ<F>* h_out) {
+                           const uint32_t* d_gstart, uint32_t ngroups, XYZZ<F>* h_out, uint32_t pt_mod, hipStream_t st) {
     DevBuf tmp, out; int rc;
+    if (!st) st = ctx->stream;
     if ((rc = tmp.alloc(ctx, (size_t)nw * sizeof(XYZZ<F>))) || (rc = out.alloc(ctx, (size_t)ngroups * sizeof(XYZZ<F>)))) return rc;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<F>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, d_scalars, d_wires, nw, pt_shift, tmp.as<XYZZ<F>>());
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<F>), dim3((nw + 63) / 64), dim3(64), 0, st, tbl, d_scalars, d_wires, nw, pt_shift, tmp.as<XYZZ<F>>(), pt_mod);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<F>), dim3((ngroups + 63) / 64), dim3(64), 0, ctx->stream, tmp.as<XYZZ<F>>(), d_gstart, ngroups, out.as<XYZZ<F>>());
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<F>), dim3((ngroups + 63) / 64), dim3(64), 0, st, tmp.as<XYZZ<F>>(), d_gstart, ngroups, out.as<XYZZ<F>>());
     ZKC_HIP_CHECK(ctx, hipGetLastError());
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, out.p, (size_t)ngroups * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, out.p, (size_t)ngroups * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, st));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
     return ZKC_OK;
 }
-int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G1XYZZ* o) {
-    return fold_group_sums<Fq>(ctx, tbl, s, w, nw, sh, gs, ng, o);
+int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G1XYZZ* o, uint32_t pt_mod, hipStream_t st) {
+    return fold_group_sums<Fq>(ctx, tbl, s, w, nw, sh, gs, ng, o, pt_mod, st);
 }
 // the batch verifier's form: scratch and sums in buffers of the caller's (the context's verifier work space), the sums left on the device for the Miller kernels and copied to h_out
 int fold_group_sums_g1_ws(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, const uint32_t* gs, uint32_t ng, G1XYZZ* d_tmp, G1XYZZ* d_out, G1XYZZ* h_out) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<Fq>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, s, w, nw, 0, d_tmp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<Fq>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, s, w, nw, 0, d_tmp, 0u);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<Fq>), dim3((ng + 63) / 64), dim3(64), 0, ctx->stream, d_tmp, gs, ng, d_out);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
@@ -597,8 +599,8 @@ int fold_group_sums_g1_ws(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, 
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKC_OK;
 }
-int fold_group_sums_g2(zkc_ctx* ctx, const G2Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G2XYZZ* o) {
-    return fold_group_sums<Fq2>(ctx, tbl, s, w, nw, sh, gs, ng, o);
+int fold_group_sums_g2(zkc_ctx* ctx, const G2Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G2XYZZ* o, uint32_t pt_mod, hipStream_t st) {
+    return fold_group_sums<Fq2>(ctx, tbl, s, w, nw, sh, gs, ng, o, pt_mod, st);
 }
 
 // ---- work space ----

@@ -56,7 +56,7 @@ template <class T> int dmalloc(zkc_ctx* ctx, T** p, size_t count) { ZKC_HIP_CHEC
 // ---- fold check: for every proof and every foldable group, does the witness equal the template there? ----
 // group g of a tree block = level g's non-control wires (g < n-1) ; group n-1 = the n2bOld block
 extern "C" __global__ void __launch_bounds__(64)
-zkc_fold_check(WitnessLayout L, const uint32_t* __restrict__ wtns, const uint32_t* __restrict__ tmpl, uint32_t* __restrict__ flags, int B) {
+zkc_fold_check(WitnessLayout L, const uint32_t* __restrict__ wtns, const uint32_t* __restrict__ tmpl, uint32_t* __restrict__ flags, int B, int stride) {
     const int n = L.n, g = blockIdx.x, tree = blockIdx.y, b = blockIdx.z;
     const int blk = tree == 0 ? L.off_census : L.off_sikver;
     int start, end;
@@ -75,7 +75,37 @@ zkc_fold_check(WitnessLayout L, const uint32_t* __restrict__ wtns, const uint32_
         diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
     }
     const unsigned long long any = __ballot(diff != 0);
-    if (threadIdx.x == 0) flags[((size_t)b * 2 + tree) * n + g] = any ? 1u : 0u;
+    if (threadIdx.x == 0) flags[(size_t)b * stride + (size_t)tree * n + g] = any ? 1u : 0u;      // per proof: [2][n] flags, then the two words of zkc_top_check
+}
+
+// ---- [top fold] for every proof and tree: which slot of the key's top-of-tree table do the groups 0 .. K-1 of this witness land on, and does the slot hold these very
+// wires?  The slot index is a hash of a few words of those groups -- an index only: "hit" is said after EVERY wire of the groups has been compared with the slot's copy (one
+// workgroup, an OR over its threads).  out = flags + 2 n of the proof's flag row: out[tree] = slot | hit << 31.  A slot is written once and its valid flag last
+// (top_seed), so a slot seen valid is complete and stays what it is. ----
+extern "C" __global__ void __launch_bounds__(256)
+zkc_top_check(TopCheckArgs a, const uint32_t* __restrict__ wtns, uint32_t* __restrict__ flags, int stride, int off) {
+    __shared__ uint32_t s_valid;
+    const int tree = blockIdx.x, b = blockIdx.y;
+    const uint32_t* w = wtns + (size_t)b * a.nWires * 8;
+    uint32_t h = 2166136261u;
+    for (int i = 0; i < top::HASH_PER_GROUP * a.K; i++) h = (h ^ w[8 * (size_t)a.hw[tree][i]]) * 16777619u;
+    h ^= h >> 15;
+    const uint32_t slot = h % a.nslots;
+    if (threadIdx.x == 0) s_valid = __atomic_load_n(a.valid + (size_t)tree * a.nslots + slot, __ATOMIC_RELAXED);      // one read for the workgroup: a slot may be published meanwhile
+    __syncthreads();
+    int differs = 1;
+    if (s_valid) {
+        const uint4* c = reinterpret_cast<const uint4*>(a.copy[tree] + (size_t)slot * a.spanw[tree] * 8);
+        uint32_t diff = 0;
+        for (int g = 0; g < a.K; g++) {
+            const uint4* x = reinterpret_cast<const uint4*>(w) + 2 * (size_t)a.gs[tree][g];
+            const uint4* y = c + 2 * (size_t)(a.gs[tree][g] - a.span0[tree]);
+            const int cnt = 2 * (int)(a.ge[tree][g] - a.gs[tree][g]);
+            for (int i = threadIdx.x; i < cnt; i += 256) { const uint4 p = x[i], q = y[i]; diff |= (p.x ^ q.x) | (p.y ^ q.y) | (p.z ^ q.z) | (p.w ^ q.w); }
+        }
+        differs = __syncthreads_or(diff != 0);
+    }
+    if (threadIdx.x == 0) flags[(size_t)b * stride + off + tree] = slot | (differs ? 0u : 0x80000000u);
 }
 
 // ---- [r3] the folding depths of a voter straight from its inputs: 1 + the index of its last non-zero sibling, per tree.  That is where SMTLevIns puts the leaf, and every level
@@ -105,6 +135,7 @@ extern "C" void zkc_zkey_free(zkc_zkey* zk) {
     for (auto& kv : zk->fold.vmaps) if (kv.second.d) (void)hipFree(kv.second.d);
     for (auto& kv : zk->fold.abc_rows) if (kv.second.d) (void)hipFree(kv.second.d);
     if (zk->fold.d_abc_tmpl) (void)hipFree(zk->fold.d_abc_tmpl);
+    { auto& tp = zk->fold.top; for (void* q : {(void*)tp.d_copy[0], (void*)tp.d_copy[1], (void*)tp.d_valid, (void*)tp.d_A, (void*)tp.d_B1, (void*)tp.d_C, (void*)tp.d_B2}) if (q) (void)hipFree(q); }
     for (void* q : {(void*)zk->fold.d_foldA, (void*)zk->fold.d_foldB1, (void*)zk->fold.d_foldC, (void*)zk->fold.d_foldB2}) if (q) (void)hipFree(q);
     if (zk->h_depths) (void)hipHostFree(zk->h_depths);
     for (auto& c : zk->call) { for (void* q : {(void*)c.d_rs, (void*)c.d_proofs, (void*)c.d_flags, (void*)c.d_status3}) if (q) (void)hipFree(q); if (c.h_flags) (void)hipHostFree(c.h_flags); if (c.h_out) (void)hipHostFree(c.h_out); if (c.h_rs) (void)hipHostFree(c.h_rs); if (c.h_xyzz) (void)hipHostFree(c.h_xyzz); if (c.h_early) (void)hipHostFree(c.h_early); if (c.d_xyzz) (void)hipFree(c.d_xyzz); for (hipEvent_t e : c.ev_done) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : c.ev_chunk) (void)hipEventDestroy(e); }
@@ -114,6 +145,7 @@ extern "C" void zkc_zkey_free(zkc_zkey* zk) {
 
 static size_t dev_free_bytes() { size_t f = 0, t = 0; if (hipMemGetInfo(&f, &t) != hipSuccess) { (void)hipGetLastError(); return 0; } return f; }
 static int fold_prepare(zkc_zkey* zk);
+static int top_prepare(zkc_zkey* zk);
 static int fb4_prepare(zkc_zkey* zk);
 // ---- the pipeline lanes: the CONTEXT's (zkc_ctx::lanes), shared by every key of the context ----
 // what one lane must hold for `inflight` proofs of this key per pass
@@ -365,6 +397,7 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     ZKC_HIP_BAIL(hipStreamSynchronize(ctx->stream));
     // the folding tables of the voter-independent witness part are part of the key's one-time cost, not of the first proof
     if (zk->nLevels >= 0 && (rc = fold_prepare(zk))) return bail(rc);
+    if (zk->nLevels >= 0 && (rc = top_prepare(zk))) return bail(rc);      // [top fold] the (empty) table of top-of-tree sums
     if ((rc = fb4_prepare(zk))) return bail(rc);
     { const size_t f = dev_free_bytes(), grown = ctx_work_bytes(ctx) > work_at_entry ? ctx_work_bytes(ctx) - work_at_entry : 0; zk->bytes_tables = free_at_entry > f + grown ? free_at_entry - f - grown : 0; }
     *out = zk;
@@ -464,24 +497,116 @@ static int fb4_prepare(zkc_zkey* zk) {
 }
 // device lists of the wires that stay in the MSMs of each section when levels >= Dc (census) / >= Ds (sik) and the n2bOld
 // blocks are folded into constants; wires whose base is the point at infinity are dropped per section
-static int fold_vmap(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::VMap* out) {
-    auto it = zk->fold.vmaps.find({Dc, Ds});
+// [top fold] ... and, where Tc / Ts = the key's K instead of 0, the groups below K of that tree are left out too: they come back as the sum of a slot of the key's
+// top-of-tree table (zkc_top_fold.h builds the lists; cached per 4-tuple)
+static int fold_vmap(zkc_zkey* zk, int Tc, int Dc, int Ts, int Ds, zkc_zkey::Fold::VMap* out) {
+    auto it = zk->fold.vmaps.find({Tc, Dc, Ts, Ds});
     if (it != zk->fold.vmaps.end()) { *out = it->second; return ZKC_OK; }
-    zkc_ctx* ctx = zk->ctx; const WitnessLayout L = WitnessLayout::make(zk->nLevels); const int n = L.n;
-    std::vector<uint8_t> folded(L.nWires, 0);
-    for (int tree = 0; tree < 2; tree++) {
-        auto rg = fold_group_ranges(L, tree); const int D = tree == 0 ? Dc : Ds;
-        for (int g = D; g < n - 1; g++) for (int w = rg[g].first; w < rg[g].second; w++) folded[w] = 1;
-        for (int w = rg[n - 1].first; w < rg[n - 1].second; w++) folded[w] = 1;
+    zkc_ctx* ctx = zk->ctx; const WitnessLayout L = WitnessLayout::make(zk->nLevels);
+    const top::Ranges rg[2] = {fold_group_ranges(L, 0), fold_group_ranges(L, 1)};
+    const top::Lists l = top::section_lists((size_t)L.nWires, zk->nPub, rg, L.n, zk->fold.infA.data(), zk->fold.infB.data(), zk->fold.infC.data(), Tc, Dc, Ts, Ds);
+    zkc_zkey::Fold::VMap m; m.offA = l.offA; m.nA = l.nA; m.offB = l.offB; m.nB = l.nB; m.offC = l.offC; m.nC = l.nC;
+    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&m.d, l.v.size() * 4 + 4));
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, l.v.data(), l.v.size() * 4, hipMemcpyHostToDevice, ctx->stream2));      // (the context's second stream: the first may hold a call's witness kernels)
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream2));
+    zk->fold.vmaps[{Tc, Dc, Ts, Ds}] = m; *out = m;
+    return ZKC_OK;
+}
+
+// [top fold] the key's top-of-tree table, made empty at key load: K = $ZKC_TOP_FOLD levels (default 8; at most n - 2, a proof folds its top only when its depth exceeds K),
+// 8 x 2^K slots per tree -- eight times the subtrees of one root, so that the voters of an election (one census root, one sik root) rarely share a slot.  Per slot a copy of the
+// wire span [first wire of group 0, last of group K-1] as it stands in a witness (~115 KB at K = 8) and the four section sums.
+static int top_prepare(zkc_zkey* zk) {
+    auto& tp = zk->fold.top; zkc_ctx* ctx = zk->ctx;
+    if (tp.K || !zk->fold.ready) return ZKC_OK;
+    const WitnessLayout L = WitnessLayout::make(zk->nLevels); const int n = L.n;
+    const int K = std::min((int)sw::value<sw::ZKC_TOP_FOLD>(8), std::min(top::MAX_K, n - 2));
+    if (K <= 0) return ZKC_OK;
+    const top::Ranges rg[2] = {fold_group_ranges(L, 0), fold_group_ranges(L, 1)};
+    for (int t = 0; t < 2; t++) for (int g = 0; g < K; g++) if (rg[t][g].second <= rg[t][g].first || (g && rg[t][g].first < rg[t][g - 1].second)) return ZKC_OK;      // (not the layout this relies on: off)
+    // direct-mapped by a hash: with S slots for the 2^K subtrees of one root, 1 - (1 - e^(-2^K / S)) S / 2^K of them find their slot taken and never fold (21 % at S = 2 x 2^K,
+    // 6 % at 8 x 2^K, the default up to K = 10: 2048 slots, 0.24 GB per tree at K = 8); at most 8192 slots, which is 2 x 2^K at K = 12 and keeps a slot index in 16 bits
+    const uint32_t nslots = (uint32_t)sw::value<sw::ZKC_TEST_TOP_SLOTS>(std::max(2ll << K, std::min(8ll << K, 8192ll)));
+    static_assert(2 * 8192 <= top::NO_SLOT && (2ll << top::MAX_K) <= 8192 && sw::rows[sw::ZKC_TEST_TOP_SLOTS].hi * 2 <= top::NO_SLOT && sw::rows[sw::ZKC_TOP_FOLD].hi == top::MAX_K, "zkc_switches.h: top fold");
+    TopCheckArgs& a = tp.args; a.K = K; a.nslots = nslots; a.nWires = zk->nVars;
+    for (int t = 0; t < 2; t++) {
+        a.span0[t] = (uint32_t)rg[t][0].first; a.spanw[t] = (uint32_t)(rg[t][K - 1].second - rg[t][0].first);
+        { const uint32_t padded = (a.spanw[t] + 3) & ~3u; if (a.span0[t] + padded <= zk->nVars) a.spanw[t] = padded; }      // whole 128-byte lines per slot: two slots share no cache line
+        for (int g = 0; g < K; g++) { a.gs[t][g] = (uint32_t)rg[t][g].first; a.ge[t][g] = (uint32_t)rg[t][g].second; }
+        const std::vector<uint32_t> hw = top::hash_wires(rg[t], K);
+        for (size_t i = 0; i < hw.size(); i++) a.hw[t][i] = hw[i];
+        for (int g = 0; g < K; g++) {
+            tp.gA[t].push_back((uint32_t)tp.wA[t].size()); top::slot_wires(rg[t], g, zk->fold.infA.data(), zk->nVars, 0, tp.wA[t]);
+            tp.gB[t].push_back((uint32_t)tp.wB[t].size()); top::slot_wires(rg[t], g, zk->fold.infB.data(), zk->nVars, 0, tp.wB[t]);
+            tp.gC[t].push_back((uint32_t)tp.wC[t].size()); top::slot_wires(rg[t], g, zk->fold.infC.data(), zk->nVars, zk->nPub + 1, tp.wC[t]);
+        }
+        tp.gA[t].push_back((uint32_t)tp.wA[t].size()); tp.gB[t].push_back((uint32_t)tp.wB[t].size()); tp.gC[t].push_back((uint32_t)tp.wC[t].size());
     }
-    std::vector<uint32_t> v; zkc_zkey::Fold::VMap m;
-    m.offA = 0; for (int w = 0; w < L.nWires; w++) if (!folded[w] && !zk->fold.infA[w]) v.push_back((uint32_t)w); m.nA = (uint32_t)v.size();
-    m.offB = (uint32_t)v.size(); for (int w = 0; w < L.nWires; w++) if (!folded[w] && !zk->fold.infB[w]) v.push_back((uint32_t)w); m.nB = (uint32_t)v.size() - m.offB;
-    m.offC = (uint32_t)v.size(); for (int w = (int)zk->nPub + 1; w < L.nWires; w++) if (!folded[w] && !zk->fold.infC[w]) v.push_back((uint32_t)w); m.nC = (uint32_t)v.size() - m.offC;
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&m.d, v.size() * 4 + 4));
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    int rc;
+    for (int t = 0; t < 2; t++) if ((rc = dmalloc(ctx, &tp.d_copy[t], (size_t)nslots * a.spanw[t] * 8))) return rc;
+    if ((rc = dmalloc(ctx, &tp.d_valid, 2 * (size_t)nslots)) || (rc = dmalloc(ctx, &tp.d_A, 2 * (size_t)nslots)) || (rc = dmalloc(ctx, &tp.d_B1, 2 * (size_t)nslots)) ||
+        (rc = dmalloc(ctx, &tp.d_C, 2 * (size_t)nslots)) || (rc = dmalloc(ctx, &tp.d_B2, 2 * (size_t)nslots))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemsetAsync(tp.d_valid, 0, 2 * (size_t)nslots * 4, ctx->stream));
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    zk->fold.vmaps[{Dc, Ds}] = m; *out = m;
+    a.copy[0] = tp.d_copy[0]; a.copy[1] = tp.d_copy[1]; a.valid = tp.d_valid;
+    tp.valid.assign(2 * (size_t)nslots, 0); tp.nslots = nslots;
+    tp.K = K;
+    return ZKC_OK;
+}
+// [top fold] writes empty slots from witnesses of a pass (w0: the pass' first witness): seed s takes groups 0 .. K-1 of tree s.tree of witness s.q into slot s.slot.  The sums
+// come from the routines fold_prepare uses, every seed of the pass in one launch per section and one group per (seed, level), added up here; then the sums and the copy of
+// the wires go to the device and, behind them on the same stream, the valid flags.  A slot is written once: nothing a kernel in flight may read is overwritten (a slot not
+// yet valid is read by nobody).  Synchronous, under the context lock the caller (prove_batch_begin) holds: a one-time cost per subtree and key, like abc_template.
+struct TopSeed { int q, tree; uint32_t slot; };
+static int top_seed(zkc_zkey* zk, const uint32_t* w0, const std::vector<TopSeed>& seeds) {
+    auto& tp = zk->fold.top; zkc_ctx* ctx = zk->ctx; const int K = tp.K; const uint32_t nv = zk->nVars, ns = (uint32_t)seeds.size(), ng = ns * (uint32_t)K;
+    const hipStream_t st = ctx->stream2;
+    timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
+    std::vector<G1XYZZ> sum1[3]; std::vector<G2XYZZ> sum2(ns, G2XYZZ::inf());
+    uint32_t *d_w = nullptr, *d_g = nullptr; int rc = ZKC_OK;
+    for (int sec = 0; sec < 3 && !rc; sec++) {            // A, B (B1 and B2), C
+        const std::vector<uint32_t>* W = sec == 0 ? tp.wA : sec == 1 ? tp.wB : tp.wC; const std::vector<uint32_t>* G = sec == 0 ? tp.gA : sec == 1 ? tp.gB : tp.gC;
+        std::vector<uint32_t> wires, gstart;
+        for (const TopSeed& s : seeds) for (int g = 0; g < K; g++) {
+            gstart.push_back((uint32_t)wires.size());
+            for (uint32_t i = G[s.tree][g]; i < G[s.tree][g + 1]; i++) wires.push_back((uint32_t)s.q * nv + W[s.tree][i]);
+        }
+        gstart.push_back((uint32_t)wires.size());
+        sum1[sec].assign(ns, G1XYZZ::inf());
+        if (wires.empty()) continue;
+        hipError_t e = hipMalloc((void**)&d_w, wires.size() * 4); if (e == hipSuccess) e = hipMalloc((void**)&d_g, gstart.size() * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_w, wires.data(), wires.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_g, gstart.data(), gstart.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = zkc_fail(ctx, ZKC_ERR_HIP, std::string("top_seed: ") + hipGetErrorString(e));
+        std::vector<G1XYZZ> g1(ng); std::vector<G2XYZZ> g2(sec == 1 ? ng : 0);
+        const G1Affine* tbl = zk->d_g1 + (sec == 0 ? zk->offA : sec == 1 ? zk->offB1 : zk->offC);
+        if (!rc) rc = fold_group_sums_g1(ctx, tbl, w0, d_w, (uint32_t)wires.size(), sec == 2 ? (int32_t)zk->nPub + 1 : 0, d_g, ng, g1.data(), nv, st);
+        if (!rc && sec == 1) rc = fold_group_sums_g2(ctx, zk->d_g2, w0, d_w, (uint32_t)wires.size(), 0, d_g, ng, g2.data(), nv, st);
+        if (!rc) for (uint32_t s = 0; s < ns; s++) for (int g = 0; g < K; g++) {
+            sum1[sec][s] = xyzz_add(sum1[sec][s], g1[(size_t)s * K + g]);
+            if (sec == 1) sum2[s] = xyzz_add(sum2[s], g2[(size_t)s * K + g]);
+        }
+        if (d_w) { (void)hipFree(d_w); d_w = nullptr; } if (d_g) { (void)hipFree(d_g); d_g = nullptr; }
+    }
+    if (rc) return rc;
+    for (uint32_t s = 0; s < ns; s++) {
+        const TopSeed& sd = seeds[s]; const size_t idx = (size_t)sd.tree * tp.nslots + sd.slot, span = (size_t)tp.args.spanw[sd.tree] * 8;
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_A + idx, &sum1[0][s], sizeof(G1XYZZ), hipMemcpyHostToDevice, st));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_B1 + idx, &sum1[1][s], sizeof(G1XYZZ), hipMemcpyHostToDevice, st));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_C + idx, &sum1[2][s], sizeof(G1XYZZ), hipMemcpyHostToDevice, st));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_B2 + idx, &sum2[s], sizeof(G2XYZZ), hipMemcpyHostToDevice, st));
+        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_copy[sd.tree] + (size_t)sd.slot * span, w0 + ((size_t)sd.q * nv + tp.args.span0[sd.tree]) * 8, span * 4, hipMemcpyDeviceToDevice, st));
+    }
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    static const uint32_t one = 1;
+    for (const TopSeed& sd : seeds) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_valid + (size_t)sd.tree * tp.nslots + sd.slot, &one, 4, hipMemcpyHostToDevice, st));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    for (const TopSeed& sd : seeds) tp.valid[(size_t)sd.tree * tp.nslots + sd.slot] = 1;
+    tp.seeded += ns;
+    timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1);
+    const double ms = (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) * 1e-6; tp.seed_ms += ms;
+    if (sw::on<sw::ZKC_TRACE_HOST>()) fprintf(stderr, "[zkc host] top fold: %u slots seeded in %.2f ms (%llu slots, %.1f ms so far)\n", ns, ms, (unsigned long long)tp.seeded, tp.seed_ms);
     return ZKC_OK;
 }
 
@@ -490,7 +615,7 @@ static int fold_vmap(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::VMap* out) {
 // digit extraction, bucketing and the gathers only to skip them inside the accumulation, where a skipped entry still costs its wave an addition's time.  out->d == nullptr:
 // the key has no such wires, the pass indexes the sections directly.
 static int nofold_vmap(zkc_zkey* zk, zkc_zkey::Fold::VMap* out) {
-    auto it = zk->fold.vmaps.find({-1, -1});
+    auto it = zk->fold.vmaps.find({-1, -1, -1, -1});
     if (it != zk->fold.vmaps.end()) { *out = it->second; return ZKC_OK; }
     zkc_ctx* ctx = zk->ctx; const uint32_t nv = zk->nVars, np = zk->nPub;
     std::vector<uint32_t> v; zkc_zkey::Fold::VMap m;
@@ -502,7 +627,7 @@ static int nofold_vmap(zkc_zkey* zk, zkc_zkey::Fold::VMap* out) {
         ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    zk->fold.vmaps[{-1, -1}] = m; *out = m;
+    zk->fold.vmaps[{-1, -1, -1, -1}] = m; *out = m;
     return ZKC_OK;
 }
 
@@ -648,16 +773,16 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.d_rs, CS.h_rs, 64 * (size_t)B, hipMemcpyHostToDevice, st0));
     // per pass (chunk of max_inflight proofs), all enqueued now on st0: [witness kernels] -> fold check (which levels of the witness differ
     // from the voter-independent template?) -> flags to the host -> event.  The pass loop below waits for a chunk's event only.
-    uint32_t* tmpl = nullptr;
+    uint32_t* tmpl = nullptr; size_t fstride = 0;                                  // words per proof of the fold flags: [2][n], then the two words of zkc_top_check
     if (can_fold) {
-        L = WitnessLayout::make(zk->nLevels);
+        L = WitnessLayout::make(zk->nLevels); fstride = 2 * (size_t)L.n + 2;
         if ((rc = fold_prepare(zk))) return rc;
         tmpl = zkc_get_template(ctx, zk->nLevels); if (!tmpl) return ZKC_ERR_HIP;
         if (!zk->fold.abc_cls.empty() && (rc = abc_template(zk, tmpl))) return rc;
-        const size_t nflags = (size_t)B * 2 * L.n;
+        const size_t nflags = (size_t)B * fstride;
         if (CS.flags_cap < nflags) {                                   // (the slot is idle: nothing reads its old buffers)
             if (CS.d_flags) { ZKC_HIP_CHECK(ctx, hipFree(CS.d_flags)); ZKC_HIP_CHECK(ctx, hipHostFree(CS.h_flags)); CS.d_flags = CS.h_flags = nullptr; CS.flags_cap = 0; }
-            const size_t want = std::max(nflags, (size_t)256 * 2 * L.n);
+            const size_t want = std::max(nflags, (size_t)256 * fstride);
             ZKC_HIP_CHECK(ctx, hipMalloc((void**)&CS.d_flags, want * 4)); ZKC_HIP_CHECK(ctx, hipHostMalloc((void**)&CS.h_flags, want * 4)); CS.flags_cap = want;
         }
     }
@@ -708,15 +833,17 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
             if (gn > 0 && (rc = zkc_witness_chunk_async(ctx, zk->nLevels, (const uint8_t*)d_inputs + (size_t)g0 * L.nInputs * 32, gn, wc, d_status3 + 3 * (size_t)g0, d_status + g0, st0))) return rc;
         }
         if (can_fold) {
-            uint32_t* fl = CS.d_flags + (size_t)p0 * 2 * L.n;
-            hipLaunchKernelGGL(zkc_fold_check, dim3(L.n, 2, nb), dim3(64), 0, st0, L, (const uint32_t*)wc, tmpl, fl, nb);
+            uint32_t* fl = CS.d_flags + (size_t)p0 * fstride;
+            hipLaunchKernelGGL(zkc_fold_check, dim3(L.n, 2, nb), dim3(64), 0, st0, L, (const uint32_t*)wc, tmpl, fl, nb, (int)fstride);
+            // [top fold] right behind it: which slot of the key's top-of-tree table each witness lands on, and whether it holds these very wires
+            if (zk->fold.top.K) hipLaunchKernelGGL(zkc_top_check, dim3(2, nb), dim3(256), 0, st0, zk->fold.top.args, (const uint32_t*)wc, fl, (int)fstride, 2 * L.n);
             ZKC_HIP_CHECK(ctx, hipGetLastError());
-            ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_flags + (size_t)p0 * 2 * L.n, fl, (size_t)nb * 2 * L.n * 4, hipMemcpyDeviceToHost, st0));
+            ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_flags + (size_t)p0 * fstride, fl, (size_t)nb * fstride * 4, hipMemcpyDeviceToHost, st0));
         }
         if (CS.early_n) {            // the early layout's evidence for finish, in this call's own pinned memory
             if (d_status) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_early, d_status, 4 * (size_t)B, hipMemcpyDeviceToHost, st0));
             else memset(CS.h_early, 0, 4 * (size_t)B);                             // witnesses given: nobody was rejected here
-            ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_early + CS.early_cap, CS.d_flags + (size_t)p0 * 2 * L.n, (size_t)nb * 2 * L.n * 4, hipMemcpyDeviceToHost, st0));
+            ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_early + CS.early_cap, CS.d_flags + (size_t)p0 * fstride, (size_t)nb * fstride * 4, hipMemcpyDeviceToHost, st0));
         }
         ZKC_HIP_CHECK(ctx, hipEventRecord(CS.ev_chunk[c], st0));                // wtns of this chunk (and rs) ready, flags on the host
     }
@@ -743,13 +870,29 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         uint8_t dcq[MSM_MAX_JOBS / 4], dsq[MSM_MAX_JOBS / 4]; bool fold = can_fold;
         if (early) for (int q = 0; q < nb; q++) { dcq[q] = CS.early_depth[2 * q]; dsq[q] = CS.early_depth[2 * q + 1]; }
         else for (int q = 0; q < nb && fold; q++) for (int t = 0; t < 2; t++) {
-            const uint32_t* f = CS.h_flags + ((size_t)(p0 + q) * 2 + t) * L.n;
+            const uint32_t* f = CS.h_flags + (size_t)(p0 + q) * fstride + (size_t)t * L.n;
             if (f[L.n - 1]) { fold = false; break; }                              // n2bOld block differs: not one of our witnesses
             int D = 0; for (int g = 0; g < L.n - 1; g++) if (f[g]) D = g + 1;
             (t == 0 ? dcq : dsq)[q] = (uint8_t)D;
         }
         static thread_local zkc_zkey::Fold::VMap vms[MSM_MAX_JOBS / 4];
-        if (fold) for (int q = 0; q < nb; q++) if ((rc = fold_vmap(zk, dcq[q], dsq[q], &vms[q]))) return rc;
+        // [top fold] a proof whose groups 0 .. K-1 of a tree are the very wires a slot of the key's table holds (zkc_top_check: hit) and whose depth in that tree exceeds K leaves
+        // them out of its MSMs; the blinding kernel adds the slot's sums (FinalizeArgs::tc / ts).  Not in a pass laid out early (no flags yet), not in a pass of one or two proofs
+        // (the tree form of the blinding has no fixed-base rows for these sums).  A proof that misses is proved as before, and if its slot is empty its witness fills it (top_seed)
+        uint16_t tcq[MSM_MAX_JOBS / 4], tsq[MSM_MAX_JOBS / 4]; for (int q = 0; q < nb; q++) tcq[q] = tsq[q] = top::NO_SLOT;
+        const auto& tp = zk->fold.top; const int TK = tp.K;
+        if (fold && TK && !early && nb > 2) {
+            std::vector<TopSeed> seeds;
+            for (int q = 0; q < nb; q++) for (int t = 0; t < 2; t++) {
+                if ((int)(t == 0 ? dcq : dsq)[q] <= TK) continue;
+                const uint32_t word = CS.h_flags[(size_t)(p0 + q) * fstride + 2 * (size_t)L.n + t], slot = word & 0x7fffffffu; const size_t idx = (size_t)t * tp.nslots + slot;
+                if (slot >= tp.nslots) continue;
+                if (word >> 31) (t == 0 ? tcq : tsq)[q] = (uint16_t)idx;
+                else if (!tp.valid[idx] && std::none_of(seeds.begin(), seeds.end(), [&](const TopSeed& s) { return s.tree == t && s.slot == slot; })) seeds.push_back({q, t, slot});
+            }
+            if (!seeds.empty() && (rc = top_seed(zk, (const uint32_t*)d_wtns + (size_t)p0 * nv * 8, seeds))) return rc;
+        }
+        if (fold) for (int q = 0; q < nb; q++) if ((rc = fold_vmap(zk, tcq[q] != top::NO_SLOT ? TK : 0, dcq[q], tsq[q] != top::NO_SLOT ? TK : 0, dsq[q], &vms[q]))) return rc;
         const bool nofold_lists = sw::on<sw::ZKC_NOFOLD_LISTS>();
         if (!fold && nofold_lists) {                        // an unfolded pass still leaves out the wires whose bases are at infinity (one list set per key)
             zkc_zkey::Fold::VMap nf; if ((rc = nofold_vmap(zk, &nf))) return rc;
@@ -830,7 +973,8 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         FinalizeArgs fa{};
         fa.r1 = (const G1XYZZ*)LN.w1.results + (size_t)slot * LN.w1.max_jobs; fa.r2 = (const G2XYZZ*)LN.w2.results + (size_t)slot * LN.w2.max_jobs;
         fa.foldA = zk->fold.d_foldA; fa.foldB1 = zk->fold.d_foldB1; fa.foldC = zk->fold.d_foldC; fa.foldB2 = zk->fold.d_foldB2; fa.fold_n = can_fold ? L.n : 0;
-        for (int q = 0; q < nb; q++) { fa.dc[q] = fold ? dcq[q] : (uint8_t)255; fa.ds[q] = fold ? dsq[q] : (uint8_t)255; }
+        for (int q = 0; q < nb; q++) { fa.dc[q] = fold ? dcq[q] : (uint8_t)255; fa.ds[q] = fold ? dsq[q] : (uint8_t)255; fa.tc[q] = tcq[q]; fa.ts[q] = tsq[q]; }
+        fa.topA = tp.d_A; fa.topB1 = tp.d_B1; fa.topC = tp.d_C; fa.topB2 = tp.d_B2;
         fa.tblDelta1 = zk->d_tblDelta1; fa.tblAlpha1 = zk->d_tblAlpha1; fa.tblBeta1 = zk->d_tblBeta1; fa.tblDelta2 = zk->d_tblDelta2;
         fa.alpha1 = zk->alpha1; fa.beta2 = zk->beta2; fa.rs = CS.d_rs + 64 * (size_t)p0; fa.out = CS.d_proofs + 256 * (size_t)p0; fa.scratch = LN.d_fin;
         fa.per = tree ? 5 : 3; fa.fb4 = zk->d_fb4; fa.fb4g2 = zk->d_fb4g2; fa.out_xyzz = CS.d_xyzz + 512 * (size_t)p0;
@@ -925,7 +1069,7 @@ int zkc::prove_batch_finish(zkc_zkey* zk, int cs, uint8_t* proofs, uint8_t* publ
         for (int q = 0; q < CS.early_n; q++) {
             if ((int32_t)CS.h_early[q] != ZKC_W_OK) continue;                   // a rejected voter: its proof is discarded whatever it is
             for (int t = 0; t < 2; t++) {
-                const uint32_t* f = CS.h_early + CS.early_cap + ((size_t)q * 2 + t) * L.n;
+                const uint32_t* f = CS.h_early + CS.early_cap + (size_t)q * (2 * (size_t)L.n + 2) + (size_t)t * L.n;
                 int D = 0; for (int g = 0; g < L.n - 1; g++) if (f[g]) D = g + 1;
                 if (f[L.n - 1] || D > (int)CS.early_depth[2 * q + t]) {
                     // a witness that was computed elsewhere and does not carry the template below its own sibling depth (a valid witness of this circuit always does): nothing

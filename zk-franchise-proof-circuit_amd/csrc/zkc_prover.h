@@ -4,6 +4,8 @@
 #include "zkc_internal.h"
 #include "zkc_curve.h"
 #include "zkc_abc_rows.h"
+#include "zkc_top_fold.h"
+#include <array>
 
 namespace zkc {
 // Pippenger window bits per section (signed digits).  Because the bases are pre-shifted per window (T[w][i] = 2^(c w) P_i), a
@@ -74,6 +76,9 @@ struct FinalizeArgs {
     // a section is tab[0] + tab[1 + dc] + tab[1 + fold_n + ds] with tab = [base | suffix sums census tree | suffix sums sik tree] (device)
     const G1XYZZ *foldA, *foldB1, *foldC; const G2XYZZ* foldB2; int fold_n;
     uint8_t dc[MSM_MAX_JOBS / 4], ds[MSM_MAX_JOBS / 4];
+    // [top fold] ... plus, per tree, the sum of one slot of the key's top-of-tree table (zkc_zkey::Fold::Top): top?[tc[q]] and top?[ts[q]], top::NO_SLOT: none.  The proof's
+    // lists then leave out the groups below K of that tree (fold_vmap); zkc_top_check has compared every wire of them with the slot's copy
+    const G1XYZZ *topA, *topB1, *topC; const G2XYZZ* topB2; uint16_t tc[MSM_MAX_JOBS / 4], ts[MSM_MAX_JOBS / 4];
     const G1Affine *tblDelta1, *tblAlpha1, *tblBeta1; const G2Affine* tblDelta2;   // 32 x 255 fixed-base tables
     G1Affine alpha1; G2Affine beta2;
     const uint8_t* rs; uint8_t* out;                    // device: nproofs x 64 (r || s) -> nproofs x 256 proof bytes
@@ -82,6 +87,12 @@ struct FinalizeArgs {
     // and 4-bit fixed-base tables of delta1, alpha1, beta1 and every folding constant of A and B1 (fb4), of delta2 (fb4g2)
     int per; const G1XYZZ* fb4; const G2XYZZ* fb4g2;
     uint8_t* out_xyzz;                                  // device: nproofs x 512 bytes, piA (G1XYZZ) | piB (G2XYZZ) | piC (G1XYZZ): the host makes them affine (prove_batch_finish)
+};
+// zkc_top_check (zkc_prove.hip): per tree the wire ranges of groups 0 .. K-1, the wires hashed into the slot index, the slots' witness copies (each the span
+// [span0, span0 + spanw) of wires) and valid flags
+struct TopCheckArgs {
+    int K; uint32_t nslots, nWires; uint32_t gs[2][top::MAX_K], ge[2][top::MAX_K], span0[2], spanw[2], hw[2][top::MAX_K * top::HASH_PER_GROUP];
+    const uint32_t* copy[2]; const uint32_t* valid;
 };
 constexpr int FB4_WIN = 64, FB4_ROW = 15;              // windows per base, multiples per window: T[base][w][d - 1] = d 16^w base
 // zkc_blind_scalars: per proof q of a small pass, out[q][0][idx] = s w[idx] over the A list and out[q][1][idx] = r w[idx] over the B list (nullptr list: every wire)
@@ -241,7 +252,7 @@ struct zkc_zkey {
         std::vector<zkc::G1XYZZ> baseA, baseB1, baseC; std::vector<zkc::G2XYZZ> baseB2;        // [1]
         std::vector<zkc::G1XYZZ> sufA[2], sufB1[2], sufC[2]; std::vector<zkc::G2XYZZ> sufB2[2];   // [tree][D] = sum over levels >= D
         struct VMap { uint32_t* d = nullptr; uint32_t offA = 0, nA = 0, offB = 0, nB = 0, offC = 0, nC = 0; };   // three lists in one allocation
-        std::map<std::pair<int, int>, VMap> vmaps;                                              // (Dc, Ds) -> surviving wires per section
+        std::map<std::array<int, 4>, VMap> vmaps;                                               // (Tc, Dc, Ts, Ds) -> surviving wires per section: groups [T, D) of each tree, T = 0 or top.K
         std::vector<uint8_t> infA, infB, infC;                                                  // base point is the point at infinity (zero polynomial)
         zkc::G1XYZZ *d_foldA = nullptr, *d_foldB1 = nullptr, *d_foldC = nullptr; zkc::G2XYZZ* d_foldB2 = nullptr;    // [1 + 2 n] each: base, suf[0][], suf[1][]
         bool ready = false;
@@ -252,6 +263,17 @@ struct zkc_zkey {
         zkc::Fr* d_abc_tmpl = nullptr;
         struct AbcRows { uint32_t* d = nullptr; uint32_t nrows = 0, nlong = 0, offC = 0, nC = 0, offW = 0, nW = 0; };
         std::map<std::pair<int, int>, AbcRows> abc_rows;
+        // [top fold] the levels between the root and depth K of a tree are the same bits for every voter below one depth-K node: a direct-mapped table of such subtrees
+        // per tree, each slot written ONCE (by the first witness that lands on it while it is empty, top_seed) and kept for the life of the key.  K = 0: off
+        struct Top {
+            int K = 0; uint32_t nslots = 0;                                  // levels folded per tree ($ZKC_TOP_FOLD at key load), slots per tree
+            zkc::TopCheckArgs args{};                                        // what zkc_top_check reads (args.copy[t]: [nslots][spanw x 8] words, args.valid: [2][nslots])
+            uint32_t *d_copy[2] = {nullptr, nullptr}, *d_valid = nullptr;
+            zkc::G1XYZZ *d_A = nullptr, *d_B1 = nullptr, *d_C = nullptr; zkc::G2XYZZ* d_B2 = nullptr;     // [2][nslots]: the slot's sum per section
+            std::vector<uint8_t> valid;                                      // host mirror of d_valid (under the context lock)
+            std::vector<uint32_t> wA[2], wB[2], wC[2], gA[2], gB[2], gC[2];  // per tree and section: the wires a slot sums, group by group (g?[t][g] .. g?[t][g + 1])
+            uint64_t seeded = 0; double seed_ms = 0;                         // slots written so far, host time spent writing them
+        } top;
     } fold;
 };
 
@@ -306,10 +328,11 @@ int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c);  
 int msm_precompute_g2(zkc_ctx* ctx, uint32_t count, G2Affine* d_table, int c);
 int msm_g2_table29(zkc_ctx* ctx, const G2Affine* d_table, uint32_t* d_out, size_t count);       // d_out: 60 words per point
 // out[i] = scalar[wires[i]] * P[wires[i] - pt_shift] (window-0 table), then per-group sums: gsum[g] = sum out[gstart[g]..gstart[g+1])
+// pt_mod != 0: d_scalars holds several witnesses of pt_mod wires each and wires[i] = witness * pt_mod + wire (the point is P[wire - pt_shift]); st: the stream (nullptr: the context's)
 int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
-                       const uint32_t* d_gstart, uint32_t ngroups, G1XYZZ* h_out);
+                       const uint32_t* d_gstart, uint32_t ngroups, G1XYZZ* h_out, uint32_t pt_mod = 0, hipStream_t st = nullptr);
 int fold_group_sums_g1_ws(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, const uint32_t* d_gstart, uint32_t ngroups,
                           G1XYZZ* d_tmp /* nw */, G1XYZZ* d_out /* ngroups */, G1XYZZ* h_out);
 int fold_group_sums_g2(zkc_ctx* ctx, const G2Affine* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
-                       const uint32_t* d_gstart, uint32_t ngroups, G2XYZZ* h_out);
+                       const uint32_t* d_gstart, uint32_t ngroups, G2XYZZ* h_out, uint32_t pt_mod = 0, hipStream_t st = nullptr);
 }

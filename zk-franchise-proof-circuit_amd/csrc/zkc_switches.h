@@ -69,6 +69,7 @@ constexpr long long ANY = LLONG_MIN;      // no bound on this side of a clamp
     X(ZKC_REDUCE_STREAM,        ON_IF_ONE,   ANY, ANY,   PROCESS, "=1: the bucket reduction of a full pass runs on a stream of its own (the lanes then get that stream)")         \
     X(ZKC_MATVEC_UNITS,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: buildABC multiplies by its +-1 coefficients instead of adding the wire")                                   \
     X(ZKC_ABC_FOLD,             OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: buildABC of a folded pass computes every row instead of copying the voter-independent ones from the template") \
+    X(ZKC_TOP_FOLD,             NUMBER,      0,   12,    LIVE,    "key load: census tree levels below the root whose MSM terms are summed once per subtree instead of per voter (8; 0: off)") \
     X(ZKC_MATVEC_INLINE,        SET,        ANY, ANY,   PROCESS, "set (any value, 0 included): buildABC of the next pass is not prefetched on the blinding stream")              \
     X(ZKC_MV_PREFETCH_AT_NTT,   ON_IF_ONE,   ANY, ANY,   PROCESS, "=1: that prefetch starts beside the pass' bucketing instead of beside its accumulation")                       \
     X(ZKC_EARLY_LAYOUT,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: one-pass calls of more than two voters wait for their fold flags instead of reading the depths off the inputs") \
@@ -83,6 +84,7 @@ constexpr long long ANY = LLONG_MIN;      // no bound on this side of a clamp
     X(ZKC_DEBUG_SYNC,           SET,         ANY, ANY,   PROCESS, "set (any value, 0 included): synchronises after and logs every MSM launch; read when the library is loaded")   \
     /* ---- test hooks ---- */                                                                                                                                            \
     X(ZKC_TEST_FAIL_ALLOC,      NUMBER,      ANY, ANY,   LIVE,    "lane growth: the work-space allocation for this many proofs in flight or more fails")                          \
+    X(ZKC_TEST_TOP_SLOTS,       NUMBER,      1,   16384, LIVE,    "key load: slots per tree of the top-of-tree table instead of 8 x 2^K (1: every subtree lands on one slot)")    \
     X(ZKC_TEST_FAIL_KEY_LOADS,  NUMBER,      ANY, ANY,   LIVE,    "service key load: fails as out of memory while the device holds this many keys or more")
 
 enum Id {
