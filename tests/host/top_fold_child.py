@@ -12,7 +12,7 @@ from zkcensus_amd.r1cs import Layout
 import oracle_lib as ol
 
 NL = 10
-C_SEC, NW_SEC = 12, 22                                  # window bits and windows of a census key's witness sections (zkc_prover.h: MSM_C_SMALL, msm_nw)
+C_SEC, NW_SEC = 12, 22                                  # window bits and windows of a census key's witness sections (zkc_prover.h: MSM_C_SMALL; zkc_pass_plan.h: msm_nw)
 K = int(os.environ.get('ZKC_TOP_FOLD', '8'))
 _, zp, _ = setup.ensure_test_artifacts(NL)
 zk = open(zp, 'rb').read()

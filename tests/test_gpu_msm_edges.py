@@ -28,7 +28,7 @@ def c_for(n):                                       # csrc/zkc_prover.h msm_c_fo
     return 12 if n < 12000 else 13 if n < 22000 else 15 if n < 90000 else 16 if n < 180000 else 17
 
 
-def nw_for(c):                                      # csrc/zkc_prover.h msm_nw
+def nw_for(c):                                      # csrc/zkc_pass_plan.h msm_nw
     return (254 + c) // c
 
 

@@ -1,4 +1,4 @@
-"""GPU: the census tree's top levels summed once per subtree and key (ZKC_TOP_FOLD, csrc/zkc_prove.hip: zkc_top_check, top_seed, fold_vmap; csrc/zkc_finalize.hip: fold_const).
+"""GPU: the census tree's top levels summed once per subtree and key (ZKC_TOP_FOLD, csrc/zkc_fold.hip: zkc_top_check, top_seed, fold_vmap; csrc/zkc_pass_plan.h: top_fold; csrc/zkc_finalize.hip: fold_const).
 The switch is read at key load and every other test keeps its default, so each configuration runs tests/host/top_fold_child.py as a child process: nLevels = 10, the public
 prove calls, every proof and public-signal block compared with the CPU oracle's in the child.  Here: that every call was byte-equal, and that the G1 additions the device counted
 (zkc_profile_read, category 7) fell by exactly the non-zero window digits of the wires that slots stood for -- which says which proofs folded which tree, and which did not."""

@@ -1,7 +1,7 @@
 // zkc_abc_rows.h -- which rows of a census key's A and B matrices a voter can change, and the lists buildABC runs over when the rest is copied from the template (product code).
-// Plain C++17, no HIP: zkc_prove.hip builds a key's lists through it, tests/host/abc_rows_host.cc builds it with g++ under ASan/UBSan.
+// Plain C++17, no HIP: zkc_prove.hip (key load) and zkc_fold.hip (abc_rows) build a key's lists through it, tests/host/abc_rows_host.cc builds it with g++ under ASan/UBSan.
 //
-// The ONLY thing a row's constancy rests on is what zkc_fold_check (zkc_prove.hip) verifies, per proof: the witness equals the template on the wires of group (tree, g), for
+// The ONLY thing a row's constancy rests on is what zkc_fold_check (zkc_fold.hip) verifies, per proof: the witness equals the template on the wires of group (tree, g), for
 // g < n-1 the non-control wires of level g, for g = n-1 the old-key block; wire 0 is compared with the old-key block of the census tree.  A pass is folded when no proof's
 // old-key flag is set, and a proof's depth per tree is 1 + its highest level group that differs: every level group g >= depth then holds template values.  Hence
 //   a row is constant for the depths (Dc, Ds) of a folded pass  <=>  every wire of the row is wire 0 or lies in a level group g of the census tree with g >= Dc or of

@@ -64,7 +64,7 @@ __device__ G1XYZZ var_mul29_g(const G1XYZZ& P, const uint32_t k[8], Acc29* __res
     return f29_pt_is_inf(acc) ? G1XYZZ::inf() : f29_pt_to_xyzz(acc);
 }
 
-// the voter-independent part of a section's MSM for proof q (constant folding, zkc_prove.hip): base + sum over the folded levels of both trees
+// the voter-independent part of a section's MSM for proof q (constant folding, zkc_fold.hip): base + sum over the folded levels of both trees
 // [top fold] ... plus the sums of the slots that stand for the proof's top levels of either tree (slots: the key's table of this section, FinalizeArgs::tc / ts)
 template <class P>
 __device__ P fold_const(const P* __restrict__ tab, const P* __restrict__ slots, const FinalizeArgs& a, int q) {

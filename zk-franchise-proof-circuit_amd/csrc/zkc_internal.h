@@ -88,6 +88,7 @@ int zkc_ensure(zkc_ctx* ctx, void** p, size_t* cur, size_t need);
 namespace zkc {
 // A device allocation owned by a scope and freed on every way out of it.  For the temporaries of load-time and tool code only: hipFree waits for the whole device, so
 // nothing on the proving, service or lane paths owns memory this way, and what lives as long as a key, a context, a lane or a tree stays a raw pointer with its free function.
+// One-time seeding counts as load-time work: top_seed (zkc_fold.hip) writes a slot of a key's top-of-tree table once per subtree and key, synchronously, from inside a call.
 struct DevBuf {
     void* p = nullptr;
     DevBuf() = default;

@@ -36,6 +36,12 @@ extern "C" __global__ void zkc_matvec_jds(const uint32_t* perm, const uint32_t* 
 extern "C" __global__ void zkc_pointwise_mul(Fr* abc, int n, const uint32_t* list, uint32_t count);
 extern "C" __global__ void zkc_join_abc(const Fr* abc, uint32_t* p_std, int n);
 
+// ---- zkc_fold.hip: a call's witnesses against the template and the top-of-tree table, depths off the inputs (launched from zkc_prove.hip) ----
+struct TopCheckArgs;      // zkc_prover.h, which both files include
+extern "C" __global__ void zkc_fold_check(WitnessLayout L, const uint32_t* wtns, const uint32_t* tmpl, uint32_t* flags, int B, int stride);
+extern "C" __global__ void zkc_top_check(TopCheckArgs a, const uint32_t* wtns, uint32_t* flags, int stride, int off);
+extern "C" __global__ void zkc_input_depths(const uint32_t* inputs, int nInputs, int n, uint32_t* out);
+
 // ---- zkc_witness.hip: witness generation and batched Poseidon (launched from zkc_api.hip) ----
 extern "C" __global__ void zkc_witness_chains(WitnessLayout L, PoseidonTable tab, const uint32_t* inputs, uint32_t* wtns, int32_t* status, int B, int tmpl_mode);
 extern "C" __global__ void zkc_witness_chains_wave(WitnessLayout L, PoseidonTable tab, const uint32_t* inputs, uint32_t* wtns, int32_t* status, int B, int tmpl_mode);

@@ -22,8 +22,8 @@ using namespace zkc;
 // buildABC for `nb` proofs on stream `mv` (zkc_ntt.hip): unit coefficients add the wire's Montgomery form, made once per wire in the lane's transform scratch (d_t is idle here:
 // the pair runs in place, the two-transform form writes it afterwards) when it is large enough for nVars elements per proof
 // [abc fold] d_abc / d_wm: where the products and the wires' Montgomery forms go (a lane's d_abc and d_t; the key's template buffers once, abc_template).  al != nullptr (a folded
-// pass, abc_rows below): every proof's block is first the key's template abc, then the SAME three kernels run over the voter rows of the pass' depths and the wires those read
-static void matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr) {
+// pass, abc_rows): every proof's block is first the key's template abc, then the SAME three kernels run over the voter rows of the pass' depths and the wires those read
+void zkc::matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al) {
     const uint32_t n = zk->n, nv = zk->nVars;
     const bool units = zk->n_unit_coeffs > 0 && nv <= 3 * (size_t)n && sw::on<sw::ZKC_MATVEC_UNITS>();
     const Fr* wm = units ? (const Fr*)d_wm : (const Fr*)nullptr;
@@ -49,80 +49,7 @@ uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
 // the points of a key's header and section 3 as stored: zkey_check has never looked at their coordinates and neither does the load (no key is refused for them)
 G1Affine rd_g1(const uint8_t* p) { G1Affine a; (void)rd_g1_mont(a, p); return a; }
 G2Affine rd_g2(const uint8_t* p) { G2Affine a; (void)rd_g2_mont(a, p); return a; }
-template <class T> int dmalloc(zkc_ctx* ctx, T** p, size_t count) { ZKC_HIP_CHECK(ctx, hipMalloc((void**)p, count * sizeof(T))); return ZKC_OK; }
 }  // namespace
-
-
-// ---- fold check: for every proof and every foldable group, does the witness equal the template there? ----
-// group g of a tree block = level g's non-control wires (g < n-1) ; group n-1 = the n2bOld block
-extern "C" __global__ void __launch_bounds__(64)
-zkc_fold_check(WitnessLayout L, const uint32_t* __restrict__ wtns, const uint32_t* __restrict__ tmpl, uint32_t* __restrict__ flags, int B, int stride) {
-    const int n = L.n, g = blockIdx.x, tree = blockIdx.y, b = blockIdx.z;
-    const int blk = tree == 0 ? L.off_census : L.off_sikver;
-    int start, end;
-    if (g < n - 1) {
-        const int nctrl = (g == n - 3) + (g > 0 && g < n - 2) + 1;
-        start = blk + L.lvl_off(g) + nctrl; end = blk + (g + 1 < n - 1 ? L.lvl_off(g + 1) : L.lvl_off(n - 1));
-    } else { start = blk + L.off_n2bold; end = start + 253 + 127 + 133; }
-    const uint4* w = reinterpret_cast<const uint4*>(wtns + (size_t)b * L.nWires * 8) + 2 * (size_t)start;
-    const uint4* t = reinterpret_cast<const uint4*>(tmpl) + 2 * (size_t)start;
-    uint32_t diff = 0;
-    for (int i = threadIdx.x; i < 2 * (end - start); i += 64) { uint4 x = w[i], y = t[i]; diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w); }
-    // [abc fold] wire 0 (the constant 1) counts with the census tree's old-key block: a witness that carries anything else there is a foreign one and unfolds its pass, so a
-    // row over wire 0 and folded levels alone is the template's row (zkc_abc_rows.h)
-    if (g == n - 1 && tree == 0 && threadIdx.x < 2) {
-        const uint4 x = reinterpret_cast<const uint4*>(wtns + (size_t)b * L.nWires * 8)[threadIdx.x], y = reinterpret_cast<const uint4*>(tmpl)[threadIdx.x];
-        diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
-    }
-    const unsigned long long any = __ballot(diff != 0);
-    if (threadIdx.x == 0) flags[(size_t)b * stride + (size_t)tree * n + g] = any ? 1u : 0u;      // per proof: [2][n] flags, then the two words of zkc_top_check
-}
-
-// ---- [top fold] for every proof and tree: which slot of the key's top-of-tree table do the groups 0 .. K-1 of this witness land on, and does the slot hold these very
-// wires?  The slot index is a hash of a few words of those groups -- an index only: "hit" is said after EVERY wire of the groups has been compared with the slot's copy (one
-// workgroup, an OR over its threads).  out = flags + 2 n of the proof's flag row: out[tree] = slot | hit << 31.  A slot is written once and its valid flag last
-// (top_seed), so a slot seen valid is complete and stays what it is. ----
-extern "C" __global__ void __launch_bounds__(256)
-zkc_top_check(TopCheckArgs a, const uint32_t* __restrict__ wtns, uint32_t* __restrict__ flags, int stride, int off) {
-    __shared__ uint32_t s_valid;
-    const int tree = blockIdx.x, b = blockIdx.y;
-    const uint32_t* w = wtns + (size_t)b * a.nWires * 8;
-    uint32_t h = 2166136261u;
-    for (int i = 0; i < top::HASH_PER_GROUP * a.K; i++) h = (h ^ w[8 * (size_t)a.hw[tree][i]]) * 16777619u;
-    h ^= h >> 15;
-    const uint32_t slot = h % a.nslots;
-    if (threadIdx.x == 0) s_valid = __atomic_load_n(a.valid + (size_t)tree * a.nslots + slot, __ATOMIC_RELAXED);      // one read for the workgroup: a slot may be published meanwhile
-    __syncthreads();
-    int differs = 1;
-    if (s_valid) {
-        const uint4* c = reinterpret_cast<const uint4*>(a.copy[tree] + (size_t)slot * a.spanw[tree] * 8);
-        uint32_t diff = 0;
-        for (int g = 0; g < a.K; g++) {
-            const uint4* x = reinterpret_cast<const uint4*>(w) + 2 * (size_t)a.gs[tree][g];
-            const uint4* y = c + 2 * (size_t)(a.gs[tree][g] - a.span0[tree]);
-            const int cnt = 2 * (int)(a.ge[tree][g] - a.gs[tree][g]);
-            for (int i = threadIdx.x; i < cnt; i += 256) { const uint4 p = x[i], q = y[i]; diff |= (p.x ^ q.x) | (p.y ^ q.y) | (p.z ^ q.z) | (p.w ^ q.w); }
-        }
-        differs = __syncthreads_or(diff != 0);
-    }
-    if (threadIdx.x == 0) flags[(size_t)b * stride + off + tree] = slot | (differs ? 0u : 0x80000000u);
-}
-
-// ---- [r3] the folding depths of a voter straight from its inputs: 1 + the index of its last non-zero sibling, per tree.  That is where SMTLevIns puts the leaf, and every level
-// from there down carries the voter-independent trace.  A call of one or two voters reads these BEFORE its witness kernel has run, so that everything behind the witness can be
-// enqueued while it runs; zkc_fold_check still compares the finished witness with the template, and prove_batch_finish refuses the call if the two disagree for an accepted voter. ----
-extern "C" __global__ void __launch_bounds__(64)
-zkc_input_depths(const uint32_t* __restrict__ inputs, int nInputs, int n, uint32_t* __restrict__ out) {
-    const int b = blockIdx.x, tree = blockIdx.y;
-    const uint32_t* sib = inputs + ((size_t)b * nInputs + 12 + (size_t)tree * n) * 8;
-    int d = 0;
-    for (int i = threadIdx.x; i < n; i += 64) {
-        const uint4* q = reinterpret_cast<const uint4*>(sib + 8 * (size_t)i); const uint4 x = q[0], y = q[1];
-        if (x.x | x.y | x.z | x.w | y.x | y.y | y.z | y.w) d = i + 1;
-    }
-    for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(d, m, 64); d = o > d ? o : d; }
-    if (threadIdx.x == 0) out[2 * b + tree] = (uint32_t)d;
-}
 
 extern "C" void zkc_zkey_free(zkc_zkey* zk) {
     if (!zk) return;
@@ -132,11 +59,7 @@ extern "C" void zkc_zkey_free(zkc_zkey* zk) {
     void* ptrs[] = {zk->d_perm, zk->d_rowlen, zk->d_jdptr, zk->d_col, zk->d_val, zk->d_tw_fwd, zk->d_tw_inv, zk->d_tw_fwd29, zk->d_tw_inv29, zk->d_coset, zk->d_coset_br, zk->d_g1, zk->d_g2, zk->d_g2_29, zk->d_g2_29_lone, zk->d_g2_29_deep,
                     zk->d_tblDelta1, zk->d_tblAlpha1, zk->d_tblBeta1, zk->d_tblDelta2, zk->d_fb4, zk->d_fb4g2, zk->d_depths};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& kv : zk->fold.vmaps) if (kv.second.d) (void)hipFree(kv.second.d);
-    for (auto& kv : zk->fold.abc_rows) if (kv.second.d) (void)hipFree(kv.second.d);
-    if (zk->fold.d_abc_tmpl) (void)hipFree(zk->fold.d_abc_tmpl);
-    { auto& tp = zk->fold.top; for (void* q : {(void*)tp.d_copy[0], (void*)tp.d_copy[1], (void*)tp.d_valid, (void*)tp.d_A, (void*)tp.d_B1, (void*)tp.d_C, (void*)tp.d_B2}) if (q) (void)hipFree(q); }
-    for (void* q : {(void*)zk->fold.d_foldA, (void*)zk->fold.d_foldB1, (void*)zk->fold.d_foldC, (void*)zk->fold.d_foldB2}) if (q) (void)hipFree(q);
+    fold_free(zk);
     if (zk->h_depths) (void)hipHostFree(zk->h_depths);
     for (auto& c : zk->call) { for (void* q : {(void*)c.d_rs, (void*)c.d_proofs, (void*)c.d_flags, (void*)c.d_status3}) if (q) (void)hipFree(q); if (c.h_flags) (void)hipHostFree(c.h_flags); if (c.h_out) (void)hipHostFree(c.h_out); if (c.h_rs) (void)hipHostFree(c.h_rs); if (c.h_xyzz) (void)hipHostFree(c.h_xyzz); if (c.h_early) (void)hipHostFree(c.h_early); if (c.d_xyzz) (void)hipFree(c.d_xyzz); for (hipEvent_t e : c.ev_done) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : c.ev_chunk) (void)hipEventDestroy(e); }
     if (zk->ctx->lanes) for (int l = 0; l < zk->nlanes; l++) for (hipStream_t q : {zk->ctx->lanes[l].st, zk->ctx->lanes[l].st2, zk->ctx->lanes[l].fin, zk->ctx->lanes[l].red}) if (q) (void)hipStreamSynchronize(q);      // (lanes, streams and work space are the context's and stay)
@@ -144,9 +67,6 @@ extern "C" void zkc_zkey_free(zkc_zkey* zk) {
 }
 
 static size_t dev_free_bytes() { size_t f = 0, t = 0; if (hipMemGetInfo(&f, &t) != hipSuccess) { (void)hipGetLastError(); return 0; } return f; }
-static int fold_prepare(zkc_zkey* zk);
-static int top_prepare(zkc_zkey* zk);
-static int fb4_prepare(zkc_zkey* zk);
 // ---- the pipeline lanes: the CONTEXT's (zkc_ctx::lanes), shared by every key of the context ----
 // what one lane must hold for `inflight` proofs of this key per pass
 struct LaneNeed { size_t abc, p, fin, bs, e1, b1, e2, b2; int j1, j2; };
@@ -425,243 +345,6 @@ extern "C" int zkc_zkey_info(const zkc_zkey* zk, uint32_t* nVars, uint32_t* nPub
     return ZKC_OK;
 }
 
-// ---- constant folding tables: per-level sums of template_value * base for every section, then suffix sums ----
-static std::vector<std::pair<int, int>> fold_group_ranges(const WitnessLayout& L, int tree) { return abc::fold_group_ranges(L, tree); }   // [start, end) wire ranges, groups 0..n-1 (zkc_abc_rows.h)
-template <class X> static void suffix_sums(std::vector<X>& suf, const X* g, int n) {   // suf[D] = sum_{k >= D} g[k], k < n-1 ; suf[n-1] = inf
-    suf.assign(n, X::inf());
-    for (int D = n - 2; D >= 0; D--) suf[D] = xyzz_add(suf[D + 1], g[D]);
-}
-template <class PT> static int fold_upload(zkc_ctx* ctx, PT** d, const std::vector<PT>& b, const std::vector<PT>* suf) {
-    std::vector<PT> t; t.push_back(b[0]); t.insert(t.end(), suf[0].begin(), suf[0].end()); t.insert(t.end(), suf[1].begin(), suf[1].end());
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)d, t.size() * sizeof(PT)));
-    ZKC_HIP_CHECK(ctx, hipMemcpy(*d, t.data(), t.size() * sizeof(PT), hipMemcpyHostToDevice));
-    return ZKC_OK;
-}
-static int fold_prepare(zkc_zkey* zk) {
-    if (zk->fold.ready) return ZKC_OK;
-    zkc_ctx* ctx = zk->ctx; const WitnessLayout L = WitnessLayout::make(zk->nLevels); const int n = L.n;
-    uint32_t* tmpl = zkc_get_template(ctx, zk->nLevels); if (!tmpl) return ZKC_ERR_HIP;
-    std::vector<uint32_t> wires, gstart;
-    for (int tree = 0; tree < 2; tree++) for (auto& rg : fold_group_ranges(L, tree)) { gstart.push_back((uint32_t)wires.size()); for (int w = rg.first; w < rg.second; w++) wires.push_back((uint32_t)w); }
-    gstart.push_back((uint32_t)wires.size());
-    const uint32_t ng = 2 * n;
-    uint32_t *d_w = nullptr, *d_g = nullptr;
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&d_w, wires.size() * 4)); ZKC_HIP_CHECK(ctx, hipMalloc((void**)&d_g, gstart.size() * 4));
-    ZKC_HIP_CHECK(ctx, hipMemcpy(d_w, wires.data(), wires.size() * 4, hipMemcpyHostToDevice));
-    ZKC_HIP_CHECK(ctx, hipMemcpy(d_g, gstart.data(), gstart.size() * 4, hipMemcpyHostToDevice));
-    std::vector<G1XYZZ> gA(ng), gB1(ng), gC(ng); std::vector<G2XYZZ> gB2(ng);
-    int rc;
-    if ((rc = fold_group_sums_g1(ctx, zk->d_g1 + zk->offA, tmpl, d_w, (uint32_t)wires.size(), 0, d_g, ng, gA.data())) ||
-        (rc = fold_group_sums_g1(ctx, zk->d_g1 + zk->offB1, tmpl, d_w, (uint32_t)wires.size(), 0, d_g, ng, gB1.data())) ||
-        (rc = fold_group_sums_g1(ctx, zk->d_g1 + zk->offC, tmpl, d_w, (uint32_t)wires.size(), (int32_t)zk->nPub + 1, d_g, ng, gC.data())) ||
-        (rc = fold_group_sums_g2(ctx, zk->d_g2, tmpl, d_w, (uint32_t)wires.size(), 0, d_g, ng, gB2.data()))) return rc;
-    ZKC_HIP_CHECK(ctx, hipFree(d_w)); ZKC_HIP_CHECK(ctx, hipFree(d_g));
-    auto& f = zk->fold;
-    for (int t = 0; t < 2; t++) {
-        suffix_sums(f.sufA[t], gA.data() + t * n, n); suffix_sums(f.sufB1[t], gB1.data() + t * n, n);
-        suffix_sums(f.sufC[t], gC.data() + t * n, n); suffix_sums(f.sufB2[t], gB2.data() + t * n, n);
-    }
-    f.baseA = {xyzz_add(gA[n - 1], gA[2 * n - 1])}; f.baseB1 = {xyzz_add(gB1[n - 1], gB1[2 * n - 1])};
-    f.baseC = {xyzz_add(gC[n - 1], gC[2 * n - 1])}; f.baseB2 = {xyzz_add(gB2[n - 1], gB2[2 * n - 1])};
-    // device tables for the blinding kernel: [base | suf[0][0..n) | suf[1][0..n)]
-    if ((rc = fold_upload(ctx, &f.d_foldA, f.baseA, f.sufA)) || (rc = fold_upload(ctx, &f.d_foldB1, f.baseB1, f.sufB1)) || (rc = fold_upload(ctx, &f.d_foldC, f.baseC, f.sufC)) ||
-        (rc = fold_upload(ctx, &f.d_foldB2, f.baseB2, f.sufB2))) return rc;
-    f.ready = true;
-    return ZKC_OK;
-}
-// 4-bit fixed-base tables of everything the blinding of a small pass multiplies by r or s (zkc_finalize.hip): delta1, alpha1, beta1, and -- with folding -- alpha1 and beta1
-// plus the base constants of A and B1 and the per-depth suffix constants of both trees.  960 points per base: 80 MB at nLevels = 160, built on the device in about a millisecond.
-static int fb4_prepare(zkc_zkey* zk) {
-    if (!sw::on<sw::ZKC_BLIND_TREE>() || zk->d_fb4) return ZKC_OK;      // = 0 at key load: this key's small passes take the general blinding kernels (A/B, tests)
-    zkc_ctx* ctx = zk->ctx;
-    std::vector<G1XYZZ> bases = {G1XYZZ::from_affine(zk->delta1), G1XYZZ::from_affine(zk->alpha1), G1XYZZ::from_affine(zk->beta1)};
-    const auto& f = zk->fold;
-    if (f.ready) {
-        bases.push_back(xyzz_add_affine(f.baseA[0], zk->alpha1)); bases.push_back(xyzz_add_affine(f.baseB1[0], zk->beta1));
-        for (int t = 0; t < 2; t++) bases.insert(bases.end(), f.sufA[t].begin(), f.sufA[t].end());
-        for (int t = 0; t < 2; t++) bases.insert(bases.end(), f.sufB1[t].begin(), f.sufB1[t].end());
-    }
-    G1XYZZ* d_bases = nullptr; int rc;
-    if ((rc = dmalloc(ctx, &d_bases, bases.size()))) return rc;
-    if ((rc = dmalloc(ctx, &zk->d_fb4, bases.size() * FB4_WIN * FB4_ROW)) || (rc = dmalloc(ctx, &zk->d_fb4g2, (size_t)FB4_WIN * FB4_ROW + 2))) { (void)hipFree(d_bases); return rc; }
-    hipError_t e = hipMemcpyAsync(d_bases, bases.data(), bases.size() * sizeof(G1XYZZ), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { rc = fb4_build(ctx, ctx->stream, d_bases, (int)bases.size(), zk->d_fb4, G2XYZZ::from_affine(zk->delta2), G2XYZZ::from_affine(zk->beta2),
-                                             f.ready ? xyzz_add_affine(f.baseB2[0], zk->beta2) : G2XYZZ::from_affine(zk->beta2), zk->d_fb4g2); if (!rc) e = hipStreamSynchronize(ctx->stream); }
-    (void)hipFree(d_bases);
-    if (rc || e != hipSuccess) {
-        (void)hipFree(zk->d_fb4); (void)hipFree(zk->d_fb4g2); zk->d_fb4 = nullptr; zk->d_fb4g2 = nullptr;
-        return rc ? rc : zkc_fail(ctx, ZKC_ERR_HIP, std::string("fb4_prepare: ") + hipGetErrorString(e));
-    }
-    zk->fb4_bases = (int)bases.size();
-    return ZKC_OK;
-}
-// device lists of the wires that stay in the MSMs of each section when levels >= Dc (census) / >= Ds (sik) and the n2bOld
-// blocks are folded into constants; wires whose base is the point at infinity are dropped per section
-// [top fold] ... and, where Tc / Ts = the key's K instead of 0, the groups below K of that tree are left out too: they come back as the sum of a slot of the key's
-// top-of-tree table (zkc_top_fold.h builds the lists; cached per 4-tuple)
-static int fold_vmap(zkc_zkey* zk, int Tc, int Dc, int Ts, int Ds, zkc_zkey::Fold::VMap* out) {
-    auto it = zk->fold.vmaps.find({Tc, Dc, Ts, Ds});
-    if (it != zk->fold.vmaps.end()) { *out = it->second; return ZKC_OK; }
-    zkc_ctx* ctx = zk->ctx; const WitnessLayout L = WitnessLayout::make(zk->nLevels);
-    const top::Ranges rg[2] = {fold_group_ranges(L, 0), fold_group_ranges(L, 1)};
-    const top::Lists l = top::section_lists((size_t)L.nWires, zk->nPub, rg, L.n, zk->fold.infA.data(), zk->fold.infB.data(), zk->fold.infC.data(), Tc, Dc, Ts, Ds);
-    zkc_zkey::Fold::VMap m; m.offA = l.offA; m.nA = l.nA; m.offB = l.offB; m.nB = l.nB; m.offC = l.offC; m.nC = l.nC;
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&m.d, l.v.size() * 4 + 4));
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, l.v.data(), l.v.size() * 4, hipMemcpyHostToDevice, ctx->stream2));      // (the context's second stream: the first may hold a call's witness kernels)
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream2));
-    zk->fold.vmaps[{Tc, Dc, Ts, Ds}] = m; *out = m;
-    return ZKC_OK;
-}
-
-// [top fold] the key's top-of-tree table, made empty at key load: K = $ZKC_TOP_FOLD levels (default 8; at most n - 2, a proof folds its top only when its depth exceeds K),
-// 8 x 2^K slots per tree -- eight times the subtrees of one root, so that the voters of an election (one census root, one sik root) rarely share a slot.  Per slot a copy of the
-// wire span [first wire of group 0, last of group K-1] as it stands in a witness (~115 KB at K = 8) and the four section sums.
-static int top_prepare(zkc_zkey* zk) {
-    auto& tp = zk->fold.top; zkc_ctx* ctx = zk->ctx;
-    if (tp.K || !zk->fold.ready) return ZKC_OK;
-    const WitnessLayout L = WitnessLayout::make(zk->nLevels); const int n = L.n;
-    const int K = std::min((int)sw::value<sw::ZKC_TOP_FOLD>(8), std::min(top::MAX_K, n - 2));
-    if (K <= 0) return ZKC_OK;
-    const top::Ranges rg[2] = {fold_group_ranges(L, 0), fold_group_ranges(L, 1)};
-    for (int t = 0; t < 2; t++) for (int g = 0; g < K; g++) if (rg[t][g].second <= rg[t][g].first || (g && rg[t][g].first < rg[t][g - 1].second)) return ZKC_OK;      // (not the layout this relies on: off)
-    // direct-mapped by a hash: with S slots for the 2^K subtrees of one root, 1 - (1 - e^(-2^K / S)) S / 2^K of them find their slot taken and never fold (21 % at S = 2 x 2^K,
-    // 6 % at 8 x 2^K, the default up to K = 10: 2048 slots, 0.24 GB per tree at K = 8); at most 8192 slots, which is 2 x 2^K at K = 12 and keeps a slot index in 16 bits
-    const uint32_t nslots = (uint32_t)sw::value<sw::ZKC_TEST_TOP_SLOTS>(std::max(2ll << K, std::min(8ll << K, 8192ll)));
-    static_assert(2 * 8192 <= top::NO_SLOT && (2ll << top::MAX_K) <= 8192 && sw::rows[sw::ZKC_TEST_TOP_SLOTS].hi * 2 <= top::NO_SLOT && sw::rows[sw::ZKC_TOP_FOLD].hi == top::MAX_K, "zkc_switches.h: top fold");
-    TopCheckArgs& a = tp.args; a.K = K; a.nslots = nslots; a.nWires = zk->nVars;
-    for (int t = 0; t < 2; t++) {
-        a.span0[t] = (uint32_t)rg[t][0].first; a.spanw[t] = (uint32_t)(rg[t][K - 1].second - rg[t][0].first);
-        { const uint32_t padded = (a.spanw[t] + 3) & ~3u; if (a.span0[t] + padded <= zk->nVars) a.spanw[t] = padded; }      // whole 128-byte lines per slot: two slots share no cache line
-        for (int g = 0; g < K; g++) { a.gs[t][g] = (uint32_t)rg[t][g].first; a.ge[t][g] = (uint32_t)rg[t][g].second; }
-        const std::vector<uint32_t> hw = top::hash_wires(rg[t], K);
-        for (size_t i = 0; i < hw.size(); i++) a.hw[t][i] = hw[i];
-        for (int g = 0; g < K; g++) {
-            tp.gA[t].push_back((uint32_t)tp.wA[t].size()); top::slot_wires(rg[t], g, zk->fold.infA.data(), zk->nVars, 0, tp.wA[t]);
-            tp.gB[t].push_back((uint32_t)tp.wB[t].size()); top::slot_wires(rg[t], g, zk->fold.infB.data(), zk->nVars, 0, tp.wB[t]);
-            tp.gC[t].push_back((uint32_t)tp.wC[t].size()); top::slot_wires(rg[t], g, zk->fold.infC.data(), zk->nVars, zk->nPub + 1, tp.wC[t]);
-        }
-        tp.gA[t].push_back((uint32_t)tp.wA[t].size()); tp.gB[t].push_back((uint32_t)tp.wB[t].size()); tp.gC[t].push_back((uint32_t)tp.wC[t].size());
-    }
-    int rc;
-    for (int t = 0; t < 2; t++) if ((rc = dmalloc(ctx, &tp.d_copy[t], (size_t)nslots * a.spanw[t] * 8))) return rc;
-    if ((rc = dmalloc(ctx, &tp.d_valid, 2 * (size_t)nslots)) || (rc = dmalloc(ctx, &tp.d_A, 2 * (size_t)nslots)) || (rc = dmalloc(ctx, &tp.d_B1, 2 * (size_t)nslots)) ||
-        (rc = dmalloc(ctx, &tp.d_C, 2 * (size_t)nslots)) || (rc = dmalloc(ctx, &tp.d_B2, 2 * (size_t)nslots))) return rc;
-    ZKC_HIP_CHECK(ctx, hipMemsetAsync(tp.d_valid, 0, 2 * (size_t)nslots * 4, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    a.copy[0] = tp.d_copy[0]; a.copy[1] = tp.d_copy[1]; a.valid = tp.d_valid;
-    tp.valid.assign(2 * (size_t)nslots, 0); tp.nslots = nslots;
-    tp.K = K;
-    return ZKC_OK;
-}
-// [top fold] writes empty slots from witnesses of a pass (w0: the pass' first witness): seed s takes groups 0 .. K-1 of tree s.tree of witness s.q into slot s.slot.  The sums
-// come from the routines fold_prepare uses, every seed of the pass in one launch per section and one group per (seed, level), added up here; then the sums and the copy of
-// the wires go to the device and, behind them on the same stream, the valid flags.  A slot is written once: nothing a kernel in flight may read is overwritten (a slot not
-// yet valid is read by nobody).  Synchronous, under the context lock the caller (prove_batch_begin) holds: a one-time cost per subtree and key, like abc_template.
-struct TopSeed { int q, tree; uint32_t slot; };
-static int top_seed(zkc_zkey* zk, const uint32_t* w0, const std::vector<TopSeed>& seeds) {
-    auto& tp = zk->fold.top; zkc_ctx* ctx = zk->ctx; const int K = tp.K; const uint32_t nv = zk->nVars, ns = (uint32_t)seeds.size(), ng = ns * (uint32_t)K;
-    const hipStream_t st = ctx->stream2;
-    timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
-    std::vector<G1XYZZ> sum1[3]; std::vector<G2XYZZ> sum2(ns, G2XYZZ::inf());
-    uint32_t *d_w = nullptr, *d_g = nullptr; int rc = ZKC_OK;
-    for (int sec = 0; sec < 3 && !rc; sec++) {            // A, B (B1 and B2), C
-        const std::vector<uint32_t>* W = sec == 0 ? tp.wA : sec == 1 ? tp.wB : tp.wC; const std::vector<uint32_t>* G = sec == 0 ? tp.gA : sec == 1 ? tp.gB : tp.gC;
-        std::vector<uint32_t> wires, gstart;
-        for (const TopSeed& s : seeds) for (int g = 0; g < K; g++) {
-            gstart.push_back((uint32_t)wires.size());
-            for (uint32_t i = G[s.tree][g]; i < G[s.tree][g + 1]; i++) wires.push_back((uint32_t)s.q * nv + W[s.tree][i]);
-        }
-        gstart.push_back((uint32_t)wires.size());
-        sum1[sec].assign(ns, G1XYZZ::inf());
-        if (wires.empty()) continue;
-        hipError_t e = hipMalloc((void**)&d_w, wires.size() * 4); if (e == hipSuccess) e = hipMalloc((void**)&d_g, gstart.size() * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_w, wires.data(), wires.size() * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_g, gstart.data(), gstart.size() * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = zkc_fail(ctx, ZKC_ERR_HIP, std::string("top_seed: ") + hipGetErrorString(e));
-        std::vector<G1XYZZ> g1(ng); std::vector<G2XYZZ> g2(sec == 1 ? ng : 0);
-        const G1Affine* tbl = zk->d_g1 + (sec == 0 ? zk->offA : sec == 1 ? zk->offB1 : zk->offC);
-        if (!rc) rc = fold_group_sums_g1(ctx, tbl, w0, d_w, (uint32_t)wires.size(), sec == 2 ? (int32_t)zk->nPub + 1 : 0, d_g, ng, g1.data(), nv, st);
-        if (!rc && sec == 1) rc = fold_group_sums_g2(ctx, zk->d_g2, w0, d_w, (uint32_t)wires.size(), 0, d_g, ng, g2.data(), nv, st);
-        if (!rc) for (uint32_t s = 0; s < ns; s++) for (int g = 0; g < K; g++) {
-            sum1[sec][s] = xyzz_add(sum1[sec][s], g1[(size_t)s * K + g]);
-            if (sec == 1) sum2[s] = xyzz_add(sum2[s], g2[(size_t)s * K + g]);
-        }
-        if (d_w) { (void)hipFree(d_w); d_w = nullptr; } if (d_g) { (void)hipFree(d_g); d_g = nullptr; }
-    }
-    if (rc) return rc;
-    for (uint32_t s = 0; s < ns; s++) {
-        const TopSeed& sd = seeds[s]; const size_t idx = (size_t)sd.tree * tp.nslots + sd.slot, span = (size_t)tp.args.spanw[sd.tree] * 8;
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_A + idx, &sum1[0][s], sizeof(G1XYZZ), hipMemcpyHostToDevice, st));
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_B1 + idx, &sum1[1][s], sizeof(G1XYZZ), hipMemcpyHostToDevice, st));
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_C + idx, &sum1[2][s], sizeof(G1XYZZ), hipMemcpyHostToDevice, st));
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_B2 + idx, &sum2[s], sizeof(G2XYZZ), hipMemcpyHostToDevice, st));
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_copy[sd.tree] + (size_t)sd.slot * span, w0 + ((size_t)sd.q * nv + tp.args.span0[sd.tree]) * 8, span * 4, hipMemcpyDeviceToDevice, st));
-    }
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    static const uint32_t one = 1;
-    for (const TopSeed& sd : seeds) ZKC_HIP_CHECK(ctx, hipMemcpyAsync(tp.d_valid + (size_t)sd.tree * tp.nslots + sd.slot, &one, 4, hipMemcpyHostToDevice, st));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    for (const TopSeed& sd : seeds) tp.valid[(size_t)sd.tree * tp.nslots + sd.slot] = 1;
-    tp.seeded += ns;
-    timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1);
-    const double ms = (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) * 1e-6; tp.seed_ms += ms;
-    if (sw::on<sw::ZKC_TRACE_HOST>()) fprintf(stderr, "[zkc host] top fold: %u slots seeded in %.2f ms (%llu slots, %.1f ms so far)\n", ns, ms, (unsigned long long)tp.seeded, tp.seed_ms);
-    return ZKC_OK;
-}
-
-// [r4] the same three lists with NOTHING folded: every wire whose base is not the point at infinity.  A third of the census circuit's wires have a zero B polynomial (27 263 of
-// 82 754: B1 and B2 bases at infinity) and real R1CS are like that in general; an unfolded pass (a foreign circuit, a foreign witness, ZKC_NO_FOLD) used to carry them through
-// digit extraction, bucketing and the gathers only to skip them inside the accumulation, where a skipped entry still costs its wave an addition's time.  out->d == nullptr:
-// the key has no such wires, the pass indexes the sections directly.
-static int nofold_vmap(zkc_zkey* zk, zkc_zkey::Fold::VMap* out) {
-    auto it = zk->fold.vmaps.find({-1, -1, -1, -1});
-    if (it != zk->fold.vmaps.end()) { *out = it->second; return ZKC_OK; }
-    zkc_ctx* ctx = zk->ctx; const uint32_t nv = zk->nVars, np = zk->nPub;
-    std::vector<uint32_t> v; zkc_zkey::Fold::VMap m;
-    m.offA = 0; for (uint32_t w = 0; w < nv; w++) if (!zk->fold.infA[w]) v.push_back(w); m.nA = (uint32_t)v.size();
-    m.offB = (uint32_t)v.size(); for (uint32_t w = 0; w < nv; w++) if (!zk->fold.infB[w]) v.push_back(w); m.nB = (uint32_t)v.size() - m.offB;
-    m.offC = (uint32_t)v.size(); for (uint32_t w = np + 1; w < nv; w++) if (!zk->fold.infC[w]) v.push_back(w); m.nC = (uint32_t)v.size() - m.offC;
-    if ((size_t)m.nA + m.nB + m.nC + (size_t)nv / 50 < 3 * (size_t)nv - np - 1) {          // worth an indirection only when at least ~2 % of a section's entries drop out
-        ZKC_HIP_CHECK(ctx, hipMalloc((void**)&m.d, v.size() * 4 + 4));
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    zk->fold.vmaps[{-1, -1, -1, -1}] = m; *out = m;
-    return ZKC_OK;
-}
-
-// [abc fold] the template's abc, once per key at its first folded call: buildABC's own kernels (matvec_launch, the form every pass takes) over the template witness, so a row
-// copied from here holds the very bits the pass would have computed for it.  Ends with ctx->stream synchronised: the lanes' streams may read the block afterwards
-static int abc_template(zkc_zkey* zk, const uint32_t* tmpl) {
-    if (zk->fold.d_abc_tmpl) return ZKC_OK;
-    zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n; Fr *d_abc = nullptr, *d_wm = nullptr; int rc;
-    if ((rc = dmalloc(ctx, &d_abc, 3 * (size_t)n))) return rc;
-    if ((rc = dmalloc(ctx, &d_wm, 3 * (size_t)n))) { (void)hipFree(d_abc); return rc; }
-    matvec_launch(zk, d_abc, d_wm, tmpl, 1, ctx->stream);
-    hipError_t e = hipGetLastError(); if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_wm);
-    if (e != hipSuccess) { (void)hipFree(d_abc); return zkc_fail(ctx, ZKC_ERR_HIP, std::string("abc_template: ") + hipGetErrorString(e)); }
-    zk->fold.d_abc_tmpl = d_abc;
-    return ZKC_OK;
-}
-// [abc fold] the voter rows of a pass whose proofs fold at depths up to (Dc, Ds), cached per pair like the wire lists above
-static int abc_rows(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::AbcRows* out) {
-    auto& f = zk->fold;
-    auto it = f.abc_rows.find({Dc, Ds});
-    if (it != f.abc_rows.end()) { *out = it->second; return ZKC_OK; }
-    zkc_ctx* ctx = zk->ctx;
-    const abc::VoterRows v = abc::voter_rows(f.abc_cls, f.abc_perm.data(), zk->nlong, zk->n, f.abc_rowptr.data(), f.abc_col.data(), zk->nVars, Dc, Ds);
-    zkc_zkey::Fold::AbcRows m; m.nrows = (uint32_t)v.rows.size(); m.nlong = v.nlong; m.offC = m.nrows; m.nC = (uint32_t)v.crows.size(); m.offW = m.offC + m.nC; m.nW = (uint32_t)v.wires.size();
-    std::vector<uint32_t> all(v.rows); all.insert(all.end(), v.crows.begin(), v.crows.end()); all.insert(all.end(), v.wires.begin(), v.wires.end());
-    ZKC_HIP_CHECK(ctx, hipMalloc((void**)&m.d, all.size() * 4 + 4));
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(m.d, all.data(), all.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (sw::on<sw::ZKC_TRACE_HOST>()) fprintf(stderr, "[zkc host] abc rows at depths (%d, %d): %u of %zu A/B rows listed (%u long), %u C rows, %u wires\n", Dc, Ds, m.nrows, f.abc_cls.size(), m.nlong, m.nC, m.nW);
-    f.abc_rows[{Dc, Ds}] = m; *out = m;
-    return ZKC_OK;
-}
-
 // stages a2..a4 for `nb` proofs: leaves (A'B' - C') on the odd coset in d_p[q] (standard form), q < nb
 // buildABC (a2) for `nb` proofs on stream `mv`: A_w, B_w by the jagged-diagonal mat-vec, C_w = A_w o B_w (al: over the voter rows of a folded pass only, matvec_launch)
 static int h_matvec_dev(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr) {
@@ -737,7 +420,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     if (nWitness != zk->nVars) return zkc_fail(ctx, ZKC_ERR_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zk->nVars) + ", witness: " + std::to_string(nWitness));
     for (int b = 0; b < 2 * B; b++) { uint32_t t[8]; memcpy(t, rs + 32 * (size_t)b, 32); if (!fp_std_lt_p<FrParams>(t)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "r or s >= field order"); }
     ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint32_t nv = zk->nVars, np = zk->nPub, nc = nv - np - 1, n = zk->n;
+    const uint32_t nv = zk->nVars, np = zk->nPub, n = zk->n;
     const bool can_fold = zk->nLevels >= 0;
     // the stream of the call's witness kernels, fold check and small uploads: the context's for a call that may use every lane, the lane's own for a call that stays on one
     // (the proving service: the Poseidon chains of concurrent calls run side by side instead of queueing on one stream)
@@ -747,10 +430,8 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     WitnessLayout L{}; int rc;
     // the lanes this call lands on -- its one lane, or as many of the key's lanes as it has passes -- hold a pass of this key (they are the context's: grown here if another,
     // smaller key shaped them, or if this is the first call that needs them)
-    {
-        const int npasses0 = (B + zk->max_inflight - 1) / zk->max_inflight, per0 = (B + npasses0 - 1) / npasses0;
-        if ((rc = lanes_ensure(zk, per0, lane0 >= 0 ? lane0 : 0, lane0 >= 0 ? 1 : std::min(zk->nlanes, npasses0)))) return rc;
-    }
+    const plan::CallSplit split = plan::call_split(B, zk->max_inflight); const int npasses = split.npasses, per_pass = split.per_pass;
+    if ((rc = lanes_ensure(zk, per_pass, lane0 >= 0 ? lane0 : 0, lane0 >= 0 ? 1 : std::min(zk->nlanes, npasses)))) return rc;
     hipStream_t st0 = (lane0 >= 0 && !zk->serial_streams && B <= zk->max_inflight) ? ctx->lanes[lane0].st : ctx->stream;
     zkc_zkey::CallSlot& CS = zk->call[cs];
     if (CS.pending) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "prove_batch_begin: this call slot has a call in flight (finish it first)");
@@ -811,8 +492,6 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         bool ok = true; for (int i = 0; i < 2 * B; i++) ok = ok && hd[i] < (uint32_t)L.n;          // a non-zero LAST sibling fails SMTLevIns: no early path for that call
         if (ok) { CS.early_n = B; CS.early_depth.resize(2 * (size_t)B); for (int i = 0; i < 2 * B; i++) CS.early_depth[i] = (uint8_t)hd[i]; }
     }
-    const int npasses = (B + zk->max_inflight - 1) / zk->max_inflight;
-    const int per_pass = (B + npasses - 1) / npasses;       // passes of equal size (1024 -> 10 x 94 + 84, not 10 x 96 + 64): the last pass' fixed-latency tail is not spent on a stub
     while ((int)CS.ev_chunk.size() < npasses) { hipEvent_t e; ZKC_HIP_CHECK(ctx, hipEventCreateWithFlags(&e, ev_host_flags)); CS.ev_chunk.push_back(e); }      // per call slot: a call laid out early returns from begin before its event has fired, and the next call must not re-record it
     int32_t* d_status3 = nullptr;
     if (d_inputs) {
@@ -854,6 +533,13 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     const double t_begin = now_ms(); double tr[6] = {0};
     int pass = 0, done_on_st_lane = -1;
     const bool one_lane = lane0 >= 0 || zk->nlanes == 1;
+    // what the decisions of a pass (zkc_pass_plan.h) read of the key and of the switches
+    const plan::KeyShape KS{zk->c_sec, zk->c_h, zk->c_deep, nv, np, n, zk->offA, zk->offB1, zk->offC, zk->offA_deep, zk->offB1_deep, zk->offC_deep, zk->d_g2_29_lone != nullptr, zk->d_fb4 != nullptr};
+    plan::Switches SW;
+    SW.vw_big = (uint32_t)sw::value<sw::ZKC_VW_BIG>(0); SW.vw_small = (uint32_t)sw::value<sw::ZKC_VW_SMALL>(0); SW.vw_g2 = (uint32_t)sw::value<sw::ZKC_VW_G2>(0);
+    SW.deep_wires = (size_t)sw::value<sw::ZKC_DEEP_WIRES>(16000); SW.matvec_inline = sw::on<sw::ZKC_MATVEC_INLINE>(); SW.g2_acc_hold = sw::on<sw::ZKC_G2_ACC_HOLD>();
+    SW.g2_acc_early = sw::on<sw::ZKC_G2_ACC_EARLY>(); SW.reduce_stream = sw::on<sw::ZKC_REDUCE_STREAM>(); SW.serial_streams = zk->serial_streams;
+    std::vector<plan::TopSeed> seeds;
     for (int p0 = 0; p0 < B; p0 += per_pass, pass++) {
         const int nb = std::min(per_pass, B - p0);
         const int li = lane0 >= 0 ? lane0 : pass % zk->nlanes; CS.lanes_used |= 1u << li;
@@ -870,28 +556,16 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         uint8_t dcq[MSM_MAX_JOBS / 4], dsq[MSM_MAX_JOBS / 4]; bool fold = can_fold;
         if (early) for (int q = 0; q < nb; q++) { dcq[q] = CS.early_depth[2 * q]; dsq[q] = CS.early_depth[2 * q + 1]; }
         else for (int q = 0; q < nb && fold; q++) for (int t = 0; t < 2; t++) {
-            const uint32_t* f = CS.h_flags + (size_t)(p0 + q) * fstride + (size_t)t * L.n;
-            if (f[L.n - 1]) { fold = false; break; }                              // n2bOld block differs: not one of our witnesses
-            int D = 0; for (int g = 0; g < L.n - 1; g++) if (f[g]) D = g + 1;
+            const int D = plan::row_depth(CS.h_flags + (size_t)(p0 + q) * fstride + (size_t)t * L.n, L.n);
+            if (D == plan::FOREIGN) { fold = false; break; }
             (t == 0 ? dcq : dsq)[q] = (uint8_t)D;
         }
         static thread_local zkc_zkey::Fold::VMap vms[MSM_MAX_JOBS / 4];
-        // [top fold] a proof whose groups 0 .. K-1 of a tree are the very wires a slot of the key's table holds (zkc_top_check: hit) and whose depth in that tree exceeds K leaves
-        // them out of its MSMs; the blinding kernel adds the slot's sums (FinalizeArgs::tc / ts).  Not in a pass laid out early (no flags yet), not in a pass of one or two proofs
-        // (the tree form of the blinding has no fixed-base rows for these sums).  A proof that misses is proved as before, and if its slot is empty its witness fills it (top_seed)
-        uint16_t tcq[MSM_MAX_JOBS / 4], tsq[MSM_MAX_JOBS / 4]; for (int q = 0; q < nb; q++) tcq[q] = tsq[q] = top::NO_SLOT;
+        // [top fold] which slot of the key's top-of-tree table each proof takes per tree, and which empty slots the pass' witnesses fill first (top_seed)
+        uint16_t tcq[MSM_MAX_JOBS / 4], tsq[MSM_MAX_JOBS / 4];
         const auto& tp = zk->fold.top; const int TK = tp.K;
-        if (fold && TK && !early && nb > 2) {
-            std::vector<TopSeed> seeds;
-            for (int q = 0; q < nb; q++) for (int t = 0; t < 2; t++) {
-                if ((int)(t == 0 ? dcq : dsq)[q] <= TK) continue;
-                const uint32_t word = CS.h_flags[(size_t)(p0 + q) * fstride + 2 * (size_t)L.n + t], slot = word & 0x7fffffffu; const size_t idx = (size_t)t * tp.nslots + slot;
-                if (slot >= tp.nslots) continue;
-                if (word >> 31) (t == 0 ? tcq : tsq)[q] = (uint16_t)idx;
-                else if (!tp.valid[idx] && std::none_of(seeds.begin(), seeds.end(), [&](const TopSeed& s) { return s.tree == t && s.slot == slot; })) seeds.push_back({q, t, slot});
-            }
-            if (!seeds.empty() && (rc = top_seed(zk, (const uint32_t*)d_wtns + (size_t)p0 * nv * 8, seeds))) return rc;
-        }
+        plan::top_fold(dcq, dsq, CS.h_flags + (size_t)p0 * fstride + 2 * (size_t)L.n, fstride, fold ? TK : 0, tp.nslots, tp.valid.data(), early, nb, tcq, tsq, seeds);
+        if (!seeds.empty() && (rc = top_seed(zk, w0, seeds))) return rc;
         if (fold) for (int q = 0; q < nb; q++) if ((rc = fold_vmap(zk, tcq[q] != top::NO_SLOT ? TK : 0, dcq[q], tsq[q] != top::NO_SLOT ? TK : 0, dsq[q], &vms[q]))) return rc;
         const bool nofold_lists = sw::on<sw::ZKC_NOFOLD_LISTS>();
         if (!fold && nofold_lists) {                        // an unfolded pass still leaves out the wires whose bases are at infinity (one list set per key)
@@ -901,10 +575,10 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         const bool listed = fold || (nofold_lists && vms[0].d != nullptr);                      // the pass' jobs run over wire lists (vms) instead of whole sections
         if (LN.npass >= 2) { ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_fin[slot], 0)); ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st2, LN.ev_fin[slot], 0)); }   // slot still read by the blinding two passes back?
         LN.npass++;
-        // [r2] buildABC is gather-bound and needs only the witness: the one of pass p+1 is issued on the blinding stream as soon as the accumulation
-        // of pass p starts (VALU-bound, 15 ms) and is through long before the G1 stream gets there; only the first pass runs it in line
-        const bool mv_prefetch = !sw::on<sw::ZKC_MATVEC_INLINE>() && one_lane;
-        const bool mv_done = mv_prefetch && pass > 0;
+        // windows, tables and job counts of the pass, and where its stages go (zkc_pass_plan.h)
+        const plan::PassShape PS = plan::pass_shape(KS, nb, listed ? vms : (const zkc_zkey::Fold::VMap*)nullptr, plan::LaneCaps{LN.w1.max_entries, LN.w1.max_buckets, LN.w1.max_jobs, LN.w2.max_entries}, SW);
+        const plan::StreamOrder SO = plan::stream_order(nb, one_lane, pass, npasses, lane0, PS.tree, SW);
+        const bool tree = PS.tree, mv_done = SO.mv_done;
         if (mv_done) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_mv, 0));
         // (tried for passes of a few proofs while their G2 side was the longer chain: G2 enqueued first and its accumulation not held for the transforms -- its 1024 fat waves
         // then slowed buildABC and the first transform kernel threefold; with the 8-bit-window G2 table the G1 side is the longer one and goes first again)
@@ -918,55 +592,21 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_ntt, st));
         tr[2] = now_ms();
         static thread_local MsmJobList j1, j2;     // 6 KB each: kept off the stack frame of a C-ABI entry point
-        // buckets per wave of the bucket reduction ("virtual window"): a lane walks vw / 64 buckets with two full additions each, then the 64 lanes pay ~17 more for the scan and
-        // the tree -- fixed cost per wave, so a full pass wants large windows (fewer additions in all), a small one small windows (fewer in a row).  [r4] re-measured on the
-        // round-4 pipeline, one box, (H, sections): (1024, 256) 3195 / 3205 / 3212 / 3214 proofs/s -- round 1's optimum, the default until now -- (2048, 512) 3235 / 3238,
-        // (4096, 1024) 3229, (4096, 2048) 3248 / 3261 / 3264 / 3268 (+1.8 %), (8192, 1024) 3100.  Passes of fewer than 32 proofs keep the smaller windows (latency).
-        const uint32_t vwb_env = (uint32_t)sw::value<sw::ZKC_VW_BIG>(0), vws_env = (uint32_t)sw::value<sw::ZKC_VW_SMALL>(0);
-        const uint32_t vws = nb <= 4 ? 64u : vws_env ? vws_env : nb < 32 ? 256u : 2048u, vwb = nb <= 4 ? 256u : vwb_env ? vwb_env : nb < 32 ? 1024u : 4096u;
-        // the G2 section of one or two proofs takes the 8-bit-window table: 128 buckets per job, reduced by one wave (vw = 128), if the G2 work space holds 32 entries per scalar
-        size_t lone_entries = 0; for (int q = 0; q < nb; q++) lone_entries += (size_t)msm_nw(MSM_C_G2_LONE) * (listed ? vms[q].nB : nv);
-        // [r4] deep pass: the voters of this pass keep, on average, more than ZKC_DEEP_WIRES (16 000) wires per section in their MSMs (leaves far down the trees, or witnesses that
-        // do not fold): the sections take the key's second tables (c_deep bits: msm_c_for).  Per section of W full-width scalars: 22 W + 2048 x 4.2 additions at 12 bits,
-        // 17 W + 16384 x 4.2 at 15: break-even at W = 12 k by that count, at 14 k measured (profiles/r04_deep_pass_threshold.json: voters 30 levels down; +1.4 % at 40 levels,
-        // +16 % at 160); a census of 2^13 .. 2^20 voters keeps 6-9 k and stays at 12 bits (-3 % if forced over the second tables).
-        const size_t deep_wires = (size_t)sw::value<sw::ZKC_DEEP_WIRES>(16000);
-        size_t live_wires = 0; for (int q = 0; q < nb; q++) live_wires += listed ? (size_t)vms[q].nA + vms[q].nB + vms[q].nC : 2 * (size_t)nv + nc;
-        const bool deep = zk->c_deep != 0 && nb > 2 && live_wires >= 3 * deep_wires * (size_t)nb;
-        const int cw = deep ? zk->c_deep : zk->c_sec;                                                     // window bits of this pass' witness sections
-        const uint32_t oA = deep ? zk->offA_deep : zk->offA, oB1 = deep ? zk->offB1_deep : zk->offB1, oC = deep ? zk->offC_deep : zk->offC;
-        const int c2 = (nb <= 2 && zk->d_g2_29_lone && lone_entries <= LN.w2.max_entries) ? MSM_C_G2_LONE : cw;
-        const uint32_t vwg2_env = (uint32_t)sw::value<sw::ZKC_VW_G2>(0);      // A/B: the G2 jobs' window apart from the G1 sections'
-        j1.clear(vws, vwb, MSM_MAX_VW_G1); j2.clear(c2 == MSM_C_G2_LONE ? 128u : (vwg2_env && nb >= 32) ? vwg2_env : vws, 1024, MSM_MAX_VW_PER_JOB);
+        j1.clear(PS.vws, PS.vwb, MSM_MAX_VW_G1); j2.clear(PS.vw_g2, 1024, MSM_MAX_VW_PER_JOB);
         // job order of the G1 pass: the nb H jobs first (the 16-bit bucket sort wants the jobs with the larger bucket count in front), then
         // A, B1, C per proof.  zkc_finalize reads results[q] = H_q and results[nb + 3 q + {0, 1, 2}] = A_q, B1_q, C_q.
         for (int q = 0; q < nb; q++) j1.add(LN.d_p + 8 * (size_t)n * q, nullptr, n, zk->offH, n, 0, zk->c_h);
-        // [r3] a pass of one or two proofs carries its blinding's two variable-base products as two more MSM jobs each -- sum (s w_i) A_i and sum (r w_i) B1_i over the
-        // wires that stay in the proof's MSMs -- so that the blinding kernel is left with fixed-base products only (zkc_finalize.hip)
-        // (the lanes' work space is sized for max(4, passes of this key) proofs of 3 + 1 jobs each: two proofs of 5 + 1 fit unless ZKC_INFLIGHT made the passes smaller than that)
-        size_t tree_entries = 0; for (int q = 0; q < nb; q++) tree_entries += (size_t)msm_nw(zk->c_h) * n + (size_t)msm_nw(zk->c_sec) * (listed ? 2 * (size_t)vms[q].nA + 2 * (size_t)vms[q].nB + vms[q].nC : 4 * (size_t)nv + nc);
-        const bool tree = zk->d_fb4 != nullptr && nb <= 2 && 6 * nb <= LN.w1.max_jobs && tree_entries <= LN.w1.max_entries && (size_t)nb * (5 * msm_half(zk->c_sec) + msm_half(zk->c_h)) <= LN.w1.max_buckets;
+        // per proof: A, B1, C over its views (its wire lists, or the whole sections); in a small pass (tree) the same A and B1 again over the blinded scalars
+        auto add = [](MsmJobList& jl, const uint32_t* scalars, const plan::SectionView& v, int c) { jl.add(scalars, v.vmap, v.count, v.tbl_off, v.tbl_count, v.pt_shift, c); };
         BlindArgs ba{}; ba.rs = CS.d_rs + 64 * (size_t)p0; ba.nv = nv;
         for (int q = 0; q < nb; q++) {
             const uint32_t* w = w0 + (size_t)q * nv * 8;
             uint32_t* bs = tree ? LN.d_bs + (size_t)q * 2 * nv * 8 : nullptr;
-            if (tree) { ba.w[q] = w; ba.out[q] = bs; }
-            if (listed) {
-                const zkc_zkey::Fold::VMap& vm = vms[q];
-                j1.add(w, vm.d + vm.offA, vm.nA, oA, nv, 0, cw);
-                j1.add(w, vm.d + vm.offB, vm.nB, oB1, nv, 0, cw);
-                j1.add(w, vm.d + vm.offC, vm.nC, oC, nc, (int32_t)np + 1, cw);
-                if (tree) { j1.add(bs, vm.d + vm.offA, vm.nA, oA, nv, 0, cw); j1.add(bs + 8ull * nv, vm.d + vm.offB, vm.nB, oB1, nv, 0, cw); }
-                j2.add(w, vm.d + vm.offB, vm.nB, 0, nv, 0, c2);
-                if (tree) { ba.mapA[q] = vm.d + vm.offA; ba.nA[q] = vm.nA; ba.mapB[q] = vm.d + vm.offB; ba.nB[q] = vm.nB; }
-            } else {
-                j1.add(w, nullptr, nv, oA, nv, 0, cw);
-                j1.add(w, nullptr, nv, oB1, nv, 0, cw);
-                j1.add(w + 8ull * (np + 1), nullptr, nc, oC, nc, 0, cw);
-                if (tree) { j1.add(bs, nullptr, nv, oA, nv, 0, cw); j1.add(bs + 8ull * nv, nullptr, nv, oB1, nv, 0, cw); }
-                j2.add(w, nullptr, nv, 0, nv, 0, c2);
-                if (tree) { ba.mapA[q] = ba.mapB[q] = nullptr; ba.nA[q] = ba.nB[q] = nv; }
-            }
+            const plan::ProofViews v = plan::proof_views(KS, PS, w, listed ? &vms[q] : nullptr);
+            add(j1, v.A.scalars, v.A, PS.cw); add(j1, v.B1.scalars, v.B1, PS.cw); add(j1, v.C.scalars, v.C, PS.cw);
+            if (tree) { add(j1, bs, v.A, PS.cw); add(j1, bs + 8ull * nv, v.B1, PS.cw); }
+            j2.add(w, v.B1.vmap, v.B1.count, 0, nv, 0, PS.c2);
+            if (tree) { ba.w[q] = w; ba.out[q] = bs; ba.mapA[q] = v.A.vmap; ba.nA[q] = v.A.count; ba.mapB[q] = v.B1.vmap; ba.nB[q] = v.B1.count; }
         }
         if (tree && (rc = blind_scalars_launch(ctx, st, ba, nb))) return rc;                  // on the G1 stream, ahead of its bucketing (the witness and (r, s) are there: ev_chunk)
         // the blinding's arguments: piB of a small pass is written on the G2 stream right behind the G2 MSM, everything else on the blinding stream below
@@ -977,65 +617,47 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         fa.topA = tp.d_A; fa.topB1 = tp.d_B1; fa.topC = tp.d_C; fa.topB2 = tp.d_B2;
         fa.tblDelta1 = zk->d_tblDelta1; fa.tblAlpha1 = zk->d_tblAlpha1; fa.tblBeta1 = zk->d_tblBeta1; fa.tblDelta2 = zk->d_tblDelta2;
         fa.alpha1 = zk->alpha1; fa.beta2 = zk->beta2; fa.rs = CS.d_rs + 64 * (size_t)p0; fa.out = CS.d_proofs + 256 * (size_t)p0; fa.scratch = LN.d_fin;
-        fa.per = tree ? 5 : 3; fa.fb4 = zk->d_fb4; fa.fb4g2 = zk->d_fb4g2; fa.out_xyzz = CS.d_xyzz + 512 * (size_t)p0;
+        fa.per = PS.per; fa.fb4 = zk->d_fb4; fa.fb4g2 = zk->d_fb4g2; fa.out_xyzz = CS.d_xyzz + 512 * (size_t)p0;
         // The G2 MSM needs only the witness: by default it starts with the pass and runs beside buildABC/NTT/G1 sort.  ZKC_G2_LATE holds it back
         // until the G1 stream has finished its short kernels (they were seen to stall next to the G2 chain's low-occupancy kernels); the G2
         // kernels then starve behind the 13 ms G1 accumulation instead and spill into the next pass -- measured equal within noise.
         const bool g2_early = !sw::on<sw::ZKC_G2_LATE>();
-        // [r2] its bucketing starts with the pass, but its accumulation (VALU-bound, 3.3 ms alone) is held until the G1 stream leaves the NTT: it then
-        // runs beside the G1 bucketing and segment kernels, which wait on memory and LDS atomics, instead of beside the NTT, which is VALU-bound too
-        // [r4] ... which was right for round 2's pipeline and is not for this one: with the larger reduction windows the G2 side's tail is longer (one wave walks a job's 2048
-        // buckets: ~64 G2 additions in a row), and holding its accumulation back makes the blinding -- and with it the result slot the pass after next needs -- wait for it.
-        // Alternating on one box: 3160 / 3143 / 3160 / 3150 / 3151 proofs/s held back, 3205 / 3198 / 3206 / 3169 / 3206 started with the pass: +1.4 %.  ZKC_G2_ACC_HOLD=1: the old order.
-        // (Two pipeline lanes, -4 % in round 2, are +1.4 % now too -- 3202 / 3206 / 3197 / 3202 / 3201 -- but not on top of this (3107 / 3115 with both) and for twice the work space.)
-        // Passes of fewer than 32 proofs keep the hold: a lone proof's G2 kernels (1024 waves of 400 registers) slowed buildABC and the first transform kernel threefold when they were
-        // not held (round 3), and the twelve-proof passes of a 2^20-domain key run 140 proofs/s held against 136 early (their bucketing phase is 9 ms long: room for the G2 accumulation).
-        const bool g2_hold_env = sw::on<sw::ZKC_G2_ACC_HOLD>(), g2_early_env = sw::on<sw::ZKC_G2_ACC_EARLY>();
-        // [r5] ... and with the passes of a call rotating over four lanes the hold is right again for full passes: the G2 accumulation of lane k then lands beside lane k's own
-        // bucketing instead of beside another lane's transforms (alternating on one box: 3380 / 3386 proofs/s held, 3363 / 3363 started with the pass: +0.6 %)
-        const bool g2_acc_with_sort = g2_hold_env || ((nb < 32 || !one_lane) && !g2_early_env);
-        if (g2_early) {
-            if ((rc = msm_pass_g2(zk, LN.w2, j2, slot, false, st2, g2_acc_with_sort ? LN.ev_ntt : nullptr))) return rc;
+        // the G2 side of the pass on st2: its MSM (the accumulation held behind acc_after, if given), piB of a small pass right behind it
+        auto g2_side = [&](hipEvent_t acc_after) -> int {
+            if ((rc = msm_pass_g2(zk, LN.w2, j2, slot, false, st2, acc_after))) return rc;
             if (tree && (rc = finalize_tree_g2_launch(ctx, st2, fa, nb))) return rc;
             ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm2, st2));
-        }
+            return ZKC_OK;
+        };
+        if (g2_early && (rc = g2_side(SO.g2_acc_with_sort ? LN.ev_ntt : nullptr))) return rc;
         tr[3] = now_ms();
         // [r4] the work space of the G1 pass (segment lists, partial sums, job and window lists) is the previous pass' until its bucket reduction is through -- which, for a
         // full pass, runs on the lane's reduction stream beside THIS pass' buildABC and transforms (a no-op wait when the reduction ran on this stream)
         ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_red, 0));
-        // (measured, alternating on one box: 3102 / 3089 / 3083 proofs/s with the reduction on its own stream, 3074 / 3087 / 3097 without -- nothing: the pass is bound by the
-        // sum of its kernels' VALU work, and where the reduction's waves run does not change that sum.  Off unless ZKC_REDUCE_STREAM=1.)
-        const bool red_split = sw::on<sw::ZKC_REDUCE_STREAM>() && !zk->serial_streams && nb >= 32;
-        if ((rc = msm_pass_g1(zk, LN.w1, j1, slot, false, st, LN.ev_sorted, LN.ev_acc, (red_split && LS.red) ? LS.red : nullptr, LN.ev_red))) return rc;
+        if ((rc = msm_pass_g1(zk, LN.w1, j1, slot, false, st, LN.ev_sorted, LN.ev_acc, (SO.red_split && LS.red) ? LS.red : nullptr, LN.ev_red))) return rc;
         tr[4] = now_ms();
         if (!g2_early) {
             ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st2, LN.ev_sorted, 0));
-            if ((rc = msm_pass_g2(zk, LN.w2, j2, slot, false, st2))) return rc;
-            if (tree && (rc = finalize_tree_g2_launch(ctx, st2, fa, nb))) return rc;
-            ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm2, st2));
+            if ((rc = g2_side(nullptr))) return rc;
         }
         if (want_publics)       // wires 1..nPublic of every witness, one strided copy
             ZKC_HIP_CHECK(ctx, hipMemcpy2DAsync(h_pub + 32ull * np * p0, 32ull * np, w0 + 8, 32ull * nv, 32ull * np, nb, hipMemcpyDeviceToHost, st));
         ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm, st));
-        if (mv_prefetch && p0 + per_pass < B) {                                   // buildABC of the next pass, beside this pass' accumulation
+        if (SO.mv_prefetch && p0 + per_pass < B) {                                  // buildABC of the next pass, beside this pass' accumulation
             const int p1 = p0 + per_pass, nb1 = std::min(per_pass, B - p1);
             ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, sw::on<sw::ZKC_MV_PREFETCH_AT_NTT>() ? LN.ev_ntt : LN.ev_sorted, 0));         // this pass' NTT and joinABC are through (d_abc is free), its accumulation is next (waiting on ev_ntt instead, i.e. starting beside the bucketing, is 1 % slower: 3113 / 3093 against 3143 / 3137 proofs/s on one box)
             ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, CS.ev_chunk[pass + 1], 0));
             if ((rc = h_matvec_dev(zk, LN, (const uint32_t*)d_wtns + (size_t)p1 * nv * 8, nb1, fin))) return rc;
             ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_mv, fin));
         }
-        // a7 on the second stream: overlaps the next pass
-        // a call that is one small pass: its blinding and its copy go on the G1 stream itself -- nothing follows that they could overlap with, and a hop to the blinding stream is
-        // ~25 us of a 3.2 ms proof
-        // [r5] ... and so does every one-pass call that stays on its lane (the proving service): its blinding can only start when both MSM sides are through and nothing of the
-        // call follows it, so a stream of its own buys nothing and costs a hardware queue (a service of four lanes keeps 8 streams busy instead of 12)
-        hipStream_t bl = ((tree || lane0 >= 0) && npasses == 1) ? st : fin;
+        // a7 on the second stream: overlaps the next pass (a one-pass call that is small or stays on its lane: on the G1 stream itself, plan::stream_order)
+        hipStream_t bl = SO.blind_on_st ? st : fin;
         if (bl == fin) { ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, LN.ev_msm, 0)); ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, LN.ev_red, 0)); }      // ev_msm: the G1 stream up to the copy of the public signals; ev_red: the G1 results
         // [r4] ... but the blinding scratch (LN.d_fin) is the lane's, and the pass before this one -- the last pass of the PREVIOUS call, begun on the other call slot -- blinds on
         // `fin`: without this wait its lane-per-product kernels and this call's tree kernels could write the scratch at the same time (a wrong proof for one of the two callers,
         // seen once in tests/test_gpu_service.py::test_queue_spills_over_further_device_entries under a load of mixed batch sizes).  That pass' blinding is long over when
         // this call's MSMs are through, so the wait costs nothing.
-        else { if (LN.npass >= 2) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_fin[slot ^ 1], 0)); if (red_split) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_red, 0)); }
+        else { if (LN.npass >= 2) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_fin[slot ^ 1], 0)); if (SO.red_split) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_red, 0)); }
         if (!tree) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm2, 0));      // a small pass' piB is written on the G2 stream: piA and piC need not wait for it ...
         if ((rc = finalize_launch(ctx, bl, fa, nb))) return rc;
         if (tree) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm2, 0));        // ... only the copy of the finished proof does
@@ -1065,19 +687,12 @@ int zkc::prove_batch_finish(zkc_zkey* zk, int cs, uint8_t* proofs, uint8_t* publ
     CS.pending = false;
     if (e != hipSuccess) { ZKC_LOCK(zk->ctx); return zkc_fail(zk->ctx, ZKC_ERR_HIP, std::string("prove_batch_finish: ") + hipGetErrorString(e)); }
     if (CS.early_n) {                // the pass was laid out from the inputs' depths before its witness existed: the fold check of the finished witness has to agree
-        const WitnessLayout L = WitnessLayout::make(zk->nLevels);
-        for (int q = 0; q < CS.early_n; q++) {
-            if ((int32_t)CS.h_early[q] != ZKC_W_OK) continue;                   // a rejected voter: its proof is discarded whatever it is
-            for (int t = 0; t < 2; t++) {
-                const uint32_t* f = CS.h_early + CS.early_cap + (size_t)q * (2 * (size_t)L.n + 2) + (size_t)t * L.n;
-                int D = 0; for (int g = 0; g < L.n - 1; g++) if (f[g]) D = g + 1;
-                if (f[L.n - 1] || D > (int)CS.early_depth[2 * q + t]) {
-                    // a witness that was computed elsewhere and does not carry the template below its own sibling depth (a valid witness of this circuit always does): nothing
-                    // is wrong with the call, only with the shortcut -- the same call once more, laid out from its fold flags
-                    if (!CS.arg_inputs) { g_early_retries++; int rc = prove_batch_begin(zk, cs, CS.arg_wtns, CS.arg_nw, CS.B, CS.h_rs_copy.data(), CS.arg_publics, nullptr, nullptr, CS.arg_lane0, nullptr, nullptr, true); if (rc) return rc; return prove_batch_finish(zk, cs, proofs, publics); }
-                    ZKC_LOCK(zk->ctx); return zkc_fail(zk->ctx, ZKC_ERR_GENERIC, "prove_batch_finish: the witness does not fold at the depth its inputs gave (internal error)");
-                }
-            }
+        const int n = WitnessLayout::make(zk->nLevels).n;
+        if (plan::early_disagrees(CS.h_early, (uint32_t)ZKC_W_OK, CS.h_early + CS.early_cap, 2 * (size_t)n + 2, n, CS.early_depth.data(), CS.early_n) >= 0) {
+            // a witness that was computed elsewhere and does not carry the template below its own sibling depth (a valid witness of this circuit always does): nothing
+            // is wrong with the call, only with the shortcut -- the same call once more, laid out from its fold flags
+            if (!CS.arg_inputs) { g_early_retries++; int rc = prove_batch_begin(zk, cs, CS.arg_wtns, CS.arg_nw, CS.B, CS.h_rs_copy.data(), CS.arg_publics, nullptr, nullptr, CS.arg_lane0, nullptr, nullptr, true); if (rc) return rc; return prove_batch_finish(zk, cs, proofs, publics); }
+            ZKC_LOCK(zk->ctx); return zkc_fail(zk->ctx, ZKC_ERR_GENERIC, "prove_batch_finish: the witness does not fold at the depth its inputs gave (internal error)");
         }
     }
     memcpy(proofs, CS.h_out, 256ull * CS.B);

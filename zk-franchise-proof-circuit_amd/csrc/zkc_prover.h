@@ -5,6 +5,7 @@
 #include "zkc_curve.h"
 #include "zkc_abc_rows.h"
 #include "zkc_top_fold.h"
+#include "zkc_pass_plan.h"
 #include <array>
 
 namespace zkc {
@@ -14,9 +15,6 @@ namespace zkc {
 // C, B2 (8-11 k wires after constant folding): c = 12 -> 22 additions per scalar into 2048 buckets (same box: c = 14 -> 1798, 13 -> 1919,
 // 12 -> 1958, 11 -> ~1856 proofs/s; round 2, per-job bucketing: 12 -> 3030, 13 -> 2965).
 constexpr int MSM_C_BIG = 17, MSM_C_SMALL = 12;
-// [r3] the G2 section of a pass of one or two proofs: 8-bit windows -> 32 additions per scalar into 128 buckets.  A lone proof's B2 MSM is ~5 000 scalars and its latency is the
-// bucket REDUCTION (2048 buckets: ~30 of the ~55 G2 additions in a row); with 128 buckets one wave reduces the job.  Costs a second pre-shifted G2 table (0.6 GB at nLevels 160).
-constexpr int MSM_C_G2_LONE = 8;
 // [r4] the window for an MSM of W full-width scalars: W x ceil(254 / c) mixed additions plus ~4 per bucket for the reduction (2^(c-1) buckets, two full additions each,
 // latency-shaped), so the best c grows with W.  Measured on circuit-shaped random R1CS (tools/gpu/csec_sweep.sh: proofs/s for c = 12 .. 17 at 15 k / 31 k / 62 k / 123 k / 246 k
 // wires per section): best 13 / 15 / 15 / 16 / 17; the 12 of rounds 1-3 is 15 % behind at 62 k wires, 17 is 3 % behind at 123 k.
@@ -32,8 +30,6 @@ inline long long first_unreduced_wire(const void* w, size_t count) {
 }
 inline std::string unreduced_wire_msg(long long wire) { return "Witness value at wire " + std::to_string(wire) + " is not below the field order r"; }
 inline int msm_c_for(size_t W) { return W < 12000 ? 12 : W < 22000 ? 13 : W < 90000 ? 15 : W < 180000 ? 16 : 17; }
-constexpr int msm_nw(int c) { return (254 + c) / c; }          // 17 -> 15 windows (255 bits), 12 -> 22 windows (264 bits)
-constexpr int msm_half(int c) { return 1 << (c - 1); }         // buckets per job
 // buckets per workgroup of the reduction ("virtual window"): 1024 for H (64 waves per job; 512: 1496, 1024: 1548, 2048: 1505 proofs/s),
 // 256 for the witness sections (16 waves per job instead of 4: their reduction is a latency chain, not a throughput problem); passes of a few proofs take 256 and 64
 // (MsmJobList::vw_big / vw_small)
@@ -88,7 +84,7 @@ struct FinalizeArgs {
     int per; const G1XYZZ* fb4; const G2XYZZ* fb4g2;
     uint8_t* out_xyzz;                                  // device: nproofs x 512 bytes, piA (G1XYZZ) | piB (G2XYZZ) | piC (G1XYZZ): the host makes them affine (prove_batch_finish)
 };
-// zkc_top_check (zkc_prove.hip): per tree the wire ranges of groups 0 .. K-1, the wires hashed into the slot index, the slots' witness copies (each the span
+// zkc_top_check (zkc_fold.hip): per tree the wire ranges of groups 0 .. K-1, the wires hashed into the slot index, the slots' witness copies (each the span
 // [span0, span0 + spanw) of wires) and valid flags
 struct TopCheckArgs {
     int K; uint32_t nslots, nWires; uint32_t gs[2][top::MAX_K], ge[2][top::MAX_K], span0[2], spanw[2], hw[2][top::MAX_K * top::HASH_PER_GROUP];
@@ -309,6 +305,21 @@ int finalize_launch(zkc_ctx* ctx, hipStream_t st, const FinalizeArgs& a, int npr
 int finalize_tree_g2_launch(zkc_ctx* ctx, hipStream_t st, const FinalizeArgs& a, int nproofs);           // piB of a small pass, on the G2 stream
 int fb4_build(zkc_ctx* ctx, hipStream_t st, const G1XYZZ* d_bases, int nbases, G1XYZZ* d_out, const G2XYZZ& delta2, const G2XYZZ& beta2, const G2XYZZ& beta2_base, G2XYZZ* d_out2);   // d_out2: 64 x 15 + 2 points
 int blind_scalars_launch(zkc_ctx* ctx, hipStream_t st, const BlindArgs& a, int nproofs);
+template <class T> inline int dmalloc(zkc_ctx* ctx, T** p, size_t count) { ZKC_HIP_CHECK(ctx, hipMalloc((void**)p, count * sizeof(T))); return ZKC_OK; }
+// zkc_fold.hip -- the folding tables of a census key.  At key load: fold_prepare (suffix sums of the template's terms), top_prepare (the empty top-of-tree table), fb4_prepare
+// (fixed-base tables of the small-pass blinding); fold_free with the key.  From prove_batch_begin, under the context lock, each cached per key: the wire lists of a proof's
+// depths (fold_vmap; nofold_vmap: nothing folded), the slots a pass' witnesses fill (top_seed), the template's abc and the voter rows of a pass' depths (abc_template, abc_rows)
+int fold_prepare(zkc_zkey* zk);
+int top_prepare(zkc_zkey* zk);
+int fb4_prepare(zkc_zkey* zk);
+void fold_free(zkc_zkey* zk);
+int fold_vmap(zkc_zkey* zk, int Tc, int Dc, int Ts, int Ds, zkc_zkey::Fold::VMap* out);
+int nofold_vmap(zkc_zkey* zk, zkc_zkey::Fold::VMap* out);
+int top_seed(zkc_zkey* zk, const uint32_t* w0, const std::vector<plan::TopSeed>& seeds);
+int abc_template(zkc_zkey* zk, const uint32_t* tmpl);
+int abc_rows(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::AbcRows* out);
+// zkc_prove.hip -- buildABC's kernels for nb proofs on stream mv (al: over the voter rows of a folded pass only); abc_template runs them over the template witness
+void matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr);
 // a batch call in two halves (zkc_prove.hip; the public zkc_[full]prove_batch_dev are begin + finish on slot 0): begin validates, enqueues every pass and returns
 // without waiting for the GPU; finish waits for that call and copies proofs / public signals out.  cs = call slot 0 / 1; a slot must be finished before it is
 // begun again; d_wtns (and d_inputs, d_status) stay the caller's until finish returns.  d_inputs == nullptr: the witnesses are given.

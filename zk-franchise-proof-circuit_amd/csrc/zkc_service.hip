@@ -299,7 +299,7 @@ void process(zkc_service* s, zkc_service::Worker* w, std::vector<Req*>&& first) 
     const size_t nW = zh.nVars, nPub = zh.nPub, nIn = full ? (size_t)zkc_circuit_n_inputs(cls.nLevels) : 0;
     if (full && (nIn == 0 || (size_t)zkc_circuit_n_wires(cls.nLevels) != nW)) return fail_all(s, b, ZKC_ERR_BAD_ARG, "the key is not a ZkFranchiseProofCircuit(" + std::to_string(cls.nLevels) + ") key");
     // the folding depths of a voter from the host's copy of its inputs (sibling lists at entries 12 .. of the input block) or, for a witness computed elsewhere, from the sibling
-    // wires of the witness (wires 13 .. 13 + 2 nLevels: zkc_device.h WitnessLayout) -- what zkc_input_depths reads on the device, without the round trip
+    // wires of the witness (wires 13 .. 13 + 2 nLevels: zkc_device.h WitnessLayout) -- what the depth kernel of zkc_fold.hip reads on the device, without the round trip
     int shape_nl = cls.nLevels;
     if (!full) {
         std::lock_guard<std::mutex> g(s->img_mu);

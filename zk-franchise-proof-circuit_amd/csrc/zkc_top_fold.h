@@ -1,5 +1,5 @@
 // zkc_top_fold.h -- the wire lists behind the folding of a census tree's TOP levels (product code): which wires stay in a proof's MSMs, which are summed into a slot of the
-// key's top-of-tree table, which wires the slot index is hashed from.  Plain C++17, no HIP: zkc_prove.hip builds a key's lists through it, tests/host/top_fold_host.cc
+// key's top-of-tree table, which wires the slot index is hashed from.  Plain C++17, no HIP: zkc_fold.hip builds a key's lists through it, tests/host/top_fold_host.cc
 // builds it with g++ under ASan/UBSan.
 //
 // Nothing of the circuit is used beyond the group ranges of zkc_abc_rows.h (fold_group_ranges: group g < n-1 of a tree = the non-control wires of level g, group n-1 = the
