@@ -3,6 +3,7 @@ and whole proofs with injected (r, s) -- identical bytes, and accepted by the or
 import json, os, random, sys
 import pytest
 import oracle_lib as ol
+import msm_cases as mc
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(ol.ROOT, 'tools'))
@@ -72,11 +73,7 @@ def test_each_msm_nl10(env):
     for which, ptr, cnt, psz in sections:
         raw = ctypes.string_at(ptr, cnt * psz)         # Montgomery coordinates as stored in the zkey
         std = b''.join((int.from_bytes(raw[32 * i:32 * i + 32], 'little') * qinv % q).to_bytes(32, 'little') for i in range(len(raw) // 32))
-        # scalar mix: random field elements, witness-like small values, zeros, r-1
-        sc = [rng.randrange(R) for _ in range(cnt)]
-        for i in range(0, cnt, 7): sc[i] = rng.choice([0, 1, 2, R - 1, (1 << 128) - 1])
-        for i in range(cnt // 2, cnt // 2 + 600): sc[i % cnt] = 1          # a heavy bucket
-        scb = b''.join(x.to_bytes(32, 'little') for x in sc)
+        scb = mc.heavy_mix(cnt, rng)                    # random field elements, witness-like small values, zeros, r-1, a heavy bucket
         got = pk.msm_debug(which, dev_bytes(torch, scb).data_ptr(), cnt)
         exp = ol.msm_g2(std, scb) if which == 2 else ol.msm_g1(std, scb)
         assert got == exp, 'MSM section %d' % which
@@ -89,29 +86,13 @@ def test_msm_equal_and_opposite_bases_nl10(env):
     ctx, get, torch = env
     zk, pk, _ = get(10)
     z = ol.zkey_parse(zk)
-    import ctypes, collections
-    q, qinv = ol.Q, pow(1 << 256, -1, ol.Q)
     rng = random.Random(11)
-    for which, ptr, psz in ((0, z.pointsA, 64), (1, z.pointsB1, 64), (2, z.pointsB2, 128)):
+    for which in (0, 1, 2):
         cnt = pk.n_vars
-        raw = ctypes.string_at(ptr, cnt * psz)
-        std = b''.join((int.from_bytes(raw[32 * i:32 * i + 32], 'little') * qinv % q).to_bytes(32, 'little') for i in range(len(raw) // 32))
-        groups = collections.defaultdict(list)
-        for i in range(cnt):
-            pt = raw[psz * i:psz * i + psz]
-            if any(pt): groups[pt].append(i)
-        dup = max(groups.values(), key=len)
-        assert len(dup) >= 3, 'test key lost its duplicated base points'
-        a, b, c = dup[:3]
-        cases = [{a: 3, b: 3}, {a: 3, b: (1 << 13) - 3}, {a: 5, b: 5, c: 5}, {a: 7, b: R - 7}, {a: 1, b: 1, c: R - 1},
-                 {i: 9 for i in dup},                                         # a whole group in one bucket (doubling, then additions of 2P + P ...)
-                 {i: (9 if k % 2 else (1 << 13) - 9) for k, i in enumerate(dup)}]
-        base = [rng.randrange(R) for _ in range(cnt)]
-        cases.append(dict(enumerate(base)) | {i: base[dup[0]] for i in dup})   # random everywhere, the group shares one full-size scalar
-        for vals in cases:
-            sc = [0] * cnt
-            for k, v in vals.items(): sc[k] = v
-            scb = b''.join(x.to_bytes(32, 'little') for x in sc)
+        raw, std = mc.section_points(z, which, cnt)
+        dup = mc.largest_duplicate_group(raw, mc.SECTIONS[which][1], cnt)
+        for vals in mc.equal_opposite_cases(dup, cnt, rng):
+            scb = mc.scalar_bytes(cnt, vals)
             got = pk.msm_debug(which, dev_bytes(torch, scb).data_ptr(), cnt)
             exp = ol.msm_g2(std, scb) if which == 2 else ol.msm_g1(std, scb)
             assert got == exp, 'MSM section %d with equal bases' % which

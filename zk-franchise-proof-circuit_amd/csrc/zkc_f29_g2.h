@@ -101,6 +101,11 @@ ZKC_HD bool f29g2_madd(Acc29G2& acc, const F2x29& x2, const F2x29& y2, bool& sam
     return true;
 }
 
+// ---- the table row of the G2 bucket kernels: written by zkc_g2_table29 (zkc_msm.hip), read by the G2 accumulations there and by zkc_fixed_acc_g2
+// (zkc_fixedbase_dev.hip).  Three chunks of 20 words (80 bytes), x | y | -y: 9 + 9 limbs each, below 1.2 p in R' form, and two more words, of which word 18 of the
+// x chunk is 1 for the point at infinity and the other five are pad.  A signed digit only picks which y chunk is loaded beside x.
+constexpr int G2ROW_WORDS = 60, G2ROW_CHUNK = 20, G2ROW_Y = 20, G2ROW_NEG_Y = 40;
+
 // [r4] the same addition with its ten products in an order that keeps few values alive, and scheduling fences between them so that the compiler does not interleave
 // independent products (which is what holds ~330 registers in f29g2_madd: more instruction-level parallelism than ONE wave per SIMD can use, no room for a second wave).
 // Alive at the widest point (PPP = P PP): Y, ZZ, ZZZ, R, Q, P, PP, the product's 18 column sums and one negated operand: about 190 registers.  Same operations, same magnitudes.

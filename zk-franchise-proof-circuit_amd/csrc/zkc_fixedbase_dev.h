@@ -13,7 +13,7 @@ constexpr int FIXED_NWIN = 256 / FIXED_W;                           // 32 window
 constexpr int FIXED_ROWS = FIXED_NWIN * ((1 << FIXED_W) - 1);       // 8160 table rows: T[j][d - 1] = d 2^(8 j) P, d = 1 .. 255
 
 // The window table of one base, built on the host (FixedBase<F>, 32 x 255 affine points) and uploaded: G1 as 64-byte Montgomery points (522 240 B), G2 in the
-// radix-2^29 row format of the G2 MSM (zkc_g2_table29: 60 words = 240 B per row, 1 958 400 B).  Global memory; both tables stay in the L2 during a launch.
+// radix-2^29 row format of the G2 MSM (zkc_g2_table29, rows of G2ROW_WORDS words, zkc_f29_g2.h: 240 B per row, 1 958 400 B).  Global memory; both tables stay in the L2 during a launch.
 // host_ms (may be NULL): milliseconds of the host build.  Free with hipFree.  The context's lock is held by the caller; `base` is finite and on its curve.
 int fixed_table_g1(zkc_ctx* ctx, const G1Affine& base, G1Affine** d_table, double* host_ms);
 int fixed_table_g2(zkc_ctx* ctx, const G2Affine& base, uint32_t** d_table29, double* host_ms);

@@ -29,7 +29,6 @@ using namespace zkc;
 namespace {
 
 constexpr int FIXED_INV_CHUNK = 8;       // points per lane of zkc_fixed_affine
-constexpr int G2ROW = 60;                // words per row of the G2 table (zkc_msm.hip G2T29_WORDS): x | inf flag, pad | y | pad | -y | pad
 
 // the scalar of lane i as eight words of standard form
 __device__ __forceinline__ void load_scalar(uint32_t s[8], const uint32_t* __restrict__ scalars, uint32_t i, int scalars_mont) {
@@ -96,13 +95,13 @@ zkc_fixed_acc_g2(const uint32_t* __restrict__ table29, const uint32_t* __restric
     for (int j = 0; j < FIXED_NWIN; j++) {
         const uint32_t d = next_digit(s);
         if (!d) continue;
-        const uint4* q = reinterpret_cast<const uint4*>(table29 + ((size_t)j * ((1 << FIXED_W) - 1) + (d - 1)) * G2ROW);
+        const uint4* q = reinterpret_cast<const uint4*>(table29 + ((size_t)j * ((1 << FIXED_W) - 1) + (d - 1)) * G2ROW_WORDS);       // x and y, the first two chunks of a row (zkc_f29_g2.h)
         uint32_t w[40];
 #pragma unroll
         for (int k = 0; k < 10; k++) { const uint4 v = q[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
         F2x29 x2, y2;
 #pragma unroll
-        for (int k = 0; k < 9; k++) { x2.c0[k] = w[k]; x2.c1[k] = w[9 + k]; y2.c0[k] = w[20 + k]; y2.c1[k] = w[29 + k]; }
+        for (int k = 0; k < 9; k++) { x2.c0[k] = w[k]; x2.c1[k] = w[9 + k]; y2.c0[k] = w[G2ROW_Y + k]; y2.c1[k] = w[G2ROW_Y + 9 + k]; }
         if (inf) {
             acc.X = x2; acc.Y = y2;
 #pragma unroll

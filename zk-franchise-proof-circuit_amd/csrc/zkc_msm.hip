@@ -10,13 +10,14 @@
 //   K4  zkc_msm_sort.hip    scalar -> signed c-bit digits -> entries (sign | table row) grouped by bucket inside each job's own region
 //       (two counting passes per job, hand-written: no key array, no device-wide sort), bucket boundaries, segments of <= 128 entries
 //       and their order by decreasing length
-//   K5  zkc_msm_accumulate29[_g2]  one lane per SEGMENT (<= 128 entries of one bucket): XYZZ += affine (8M + 2S)
-//       in radix-2^29 coordinates (zkc_f29*.h) with 64-byte gathers from T.  Cutting buckets into segments keeps lanes
-//       balanced when many scalars repeat (witness bits; the circuit has only ~4.5k distinct values among 82k wires).
-//   K6  zkc_msm_merge       buckets of more than 8 segments: a wave each, shuffle tree
-//       zkc_msm_window[29]  one wave per virtual window (4096 / 2048 consecutive buckets of a job in a full pass, 1024 / 256 or 256 / 64 in smaller ones): per-lane running
-//       sums, a suffix scan across the 64 lanes in LDS, x per, tree sum  ->  W = sum_j j B_j and S = sum_j B_j
-//       zkc_msm_final       one workgroup per job: sum_k W_k + vw sum_k k S_k over its virtual windows.
+//   K5  zkc_msm_accumulate29<2> (G1), zkc_msm_accumulate29_g2<1> / zkc_msm_accumulate29_g2_dma<1 | 2> (G2)  one lane per SEGMENT (<= 128 entries of one bucket):
+//       XYZZ += affine (8M + 2S) in radix-2^29 coordinates (zkc_f29*.h) with 64-byte gathers from T.  Cutting buckets into segments keeps lanes balanced when many
+//       scalars repeat (witness bits; the circuit has only ~4.5k distinct values among 82k wires).  The three differ in how the next row is fetched.
+//       zkc_msm_bucketwave_g2  a small G2 pass instead: half a wave per bucket, no segments
+//   K6  zkc_msm_merge29<G>  buckets of more than 8 segments: a wave each, tree in LDS; G = G1Ops / G2Ops (zkc_point_ops.h)
+//       zkc_msm_window29 (G1) / zkc_msm_window29_g2  one wave per virtual window (4096 / 2048 consecutive buckets of a job in a full pass, 1024 / 256 or 256 / 64 in
+//       smaller ones): per-lane running sums, a suffix scan across the 64 lanes in LDS, x per, tree sum  ->  W = sum_j j B_j and S = sum_j B_j
+//       zkc_msm_final29 (G1) / zkc_msm_final29_g2  one workgroup per job: sum_k W_k + vw sum_k k S_k over its virtual windows.
 #include <cstdio>
 #include <cstddef>
 #include <ctime>
@@ -28,6 +29,7 @@
 #include "zkc_f29.h"
 #include "zkc_f29_g1.h"
 #include "zkc_f29_g2.h"
+#include "zkc_point_ops.h"
 
 namespace zkc {
 
@@ -105,19 +107,17 @@ zkc_msm_accumulate29(const Affine<Fq>* __restrict__ table_all, const MsmJobList*
 }
 
 // ---- K5, G2: radix-2^29 accumulator over Fq2 (zkc_f29_g2.h).  The table is a second copy of the pre-shifted G2 bases in R' form:
-// 60 words per point = x (9 + 9 limbs, word 18 = 1 for the point at infinity, word 19 pad), y, -y, so a signed digit only picks
-// which 80-byte chunk to load. ----
-constexpr int G2T29_WORDS = 60;
+// rows of G2ROW_WORDS words, x | y | -y (the layout and its offsets: zkc_f29_g2.h), so a signed digit only picks which 80-byte chunk to load. ----
 __global__ void __launch_bounds__(128)
 zkc_g2_table29(const Affine<Fq2>* __restrict__ tbl, uint32_t* __restrict__ out, size_t count) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const Affine<Fq2> a = PointIO<Fq2>::load(tbl + i);
-    uint32_t* o = out + i * G2T29_WORDS;
+    uint32_t* o = out + i * G2ROW_WORDS;
     const Fq2 ny = fp_neg(a.y);
     f29_enter_fq(o, a.x.c0.v); f29_enter_fq(o + 9, a.x.c1.v); o[18] = a.is_inf() ? 1u : 0u; o[19] = 0;
-    f29_enter_fq(o + 20, a.y.c0.v); f29_enter_fq(o + 29, a.y.c1.v); o[38] = o[39] = 0;
-    f29_enter_fq(o + 40, ny.c0.v); f29_enter_fq(o + 49, ny.c1.v); o[58] = o[59] = 0;
+    f29_enter_fq(o + G2ROW_Y, a.y.c0.v); f29_enter_fq(o + G2ROW_Y + 9, a.y.c1.v); o[G2ROW_Y + 18] = o[G2ROW_Y + 19] = 0;
+    f29_enter_fq(o + G2ROW_NEG_Y, ny.c0.v); f29_enter_fq(o + G2ROW_NEG_Y + 9, ny.c1.v); o[G2ROW_NEG_Y + 18] = o[G2ROW_NEG_Y + 19] = 0;
 }
 int msm_g2_table29(zkc_ctx* ctx, const G2Affine* d_table, uint32_t* d_out, size_t count) {
     hipLaunchKernelGGL(zkc_g2_table29, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, ctx->stream, d_table, d_out, count);
@@ -125,7 +125,7 @@ int msm_g2_table29(zkc_ctx* ctx, const G2Affine* d_table, uint32_t* d_out, size_
     if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("zkc_g2_table29: ") + hipGetErrorString(e));
     return ZKC_OK;
 }
-struct G2Chunk { uint32_t w[20]; };
+struct G2Chunk { uint32_t w[G2ROW_CHUNK]; };
 __device__ __forceinline__ G2Chunk g2_chunk_load(const uint32_t* p) {
     const uint4* q = reinterpret_cast<const uint4*>(p); G2Chunk c;
 #pragma unroll
@@ -145,16 +145,16 @@ zkc_msm_accumulate29_g2(const uint32_t* __restrict__ table29_all, const MsmJobLi
     uint32_t lo, hi; msm_seg_range(bcnt[b], segoff[b + 1] - segoff[b], s - segoff[b], lo, hi);
     const uint32_t start = off[b] + lo, end = off[b] + hi;
     uint32_t bd, bj; jlp->decode(b, bd, bj);
-    const uint32_t* __restrict__ table29 = table29_all + (size_t)jlp->job[bj].tbl_off * G2T29_WORDS;
+    const uint32_t* __restrict__ table29 = table29_all + (size_t)jlp->job[bj].tbl_off * G2ROW_WORDS;
     constexpr uint32_t rowmask = 0x7fffffffu;
     Acc29G2 acc; bool inf = true;
     uint32_t v = vals[start];
-    const uint32_t* pp = table29 + (size_t)(v & rowmask) * G2T29_WORDS;
-    G2Chunk cx = g2_chunk_load(pp), cy = g2_chunk_load(pp + ((v >> 31) ? 40 : 20));
+    const uint32_t* pp = table29 + (size_t)(v & rowmask) * G2ROW_WORDS;
+    G2Chunk cx = g2_chunk_load(pp), cy = g2_chunk_load(pp + ((v >> 31) ? G2ROW_NEG_Y : G2ROW_Y));
     for (uint32_t j = start; j < end; j++) {
         const uint32_t vn = (j + 1 < end) ? vals[j + 1] : v;
-        const uint32_t* pn = table29 + (size_t)(vn & rowmask) * G2T29_WORDS;
-        const G2Chunk nx = g2_chunk_load(pn), ny = g2_chunk_load(pn + ((vn >> 31) ? 40 : 20));      // next gather in flight during this addition
+        const uint32_t* pn = table29 + (size_t)(vn & rowmask) * G2ROW_WORDS;
+        const G2Chunk nx = g2_chunk_load(pn), ny = g2_chunk_load(pn + ((vn >> 31) ? G2ROW_NEG_Y : G2ROW_Y));      // next gather in flight during this addition
         if (!cx.w[18]) {
             F2x29 x2, y2;
 #pragma unroll
@@ -204,12 +204,12 @@ zkc_msm_accumulate29_g2_dma(const uint32_t* __restrict__ table29_all, const MsmJ
     uint32_t lo, hi; msm_seg_range(bcnt[b], segoff[b + 1] - segoff[b], s - segoff[b], lo, hi);
     const uint32_t start = off[b] + lo, end = off[b] + hi;
     uint32_t bd, bj; jlp->decode(b, bd, bj);
-    const uint32_t* __restrict__ table29 = table29_all + (size_t)jlp->job[bj].tbl_off * G2T29_WORDS;
+    const uint32_t* __restrict__ table29 = table29_all + (size_t)jlp->job[bj].tbl_off * G2ROW_WORDS;
     constexpr uint32_t rowmask = 0x7fffffffu;
     typedef const __attribute__((address_space(1))) void* gptr; typedef __attribute__((address_space(3))) void* lptr;
     auto fetch = [&](uint32_t v) {
-        const uint32_t* px = table29 + (size_t)(v & rowmask) * G2T29_WORDS;
-        const uint32_t* py = px + ((v >> 31) ? 40 : 20);
+        const uint32_t* px = table29 + (size_t)(v & rowmask) * G2ROW_WORDS;
+        const uint32_t* py = px + ((v >> 31) ? G2ROW_NEG_Y : G2ROW_Y);
 #pragma unroll
         for (int k = 0; k < 5; k++) __builtin_amdgcn_global_load_lds((gptr)(px + 4 * k), (lptr)&stage[k][0], 16, 0, 0);
 #pragma unroll
@@ -280,13 +280,13 @@ zkc_msm_bucketwave_g2(const uint32_t* __restrict__ table29_all, const MsmJobList
     if (__ballot(hi > lo) == 0) return;                                      // neither bucket of this wave has a slice y
     if (hi > lo) {
         uint32_t bd, bj; jlp->decode(b, bd, bj);
-        const uint32_t* __restrict__ table29 = table29_all + (size_t)jlp->job[bj].tbl_off * G2T29_WORDS;
+        const uint32_t* __restrict__ table29 = table29_all + (size_t)jlp->job[bj].tbl_off * G2ROW_WORDS;
         constexpr uint32_t rowmask = 0x7fffffffu;
         const uint32_t start = off[b];
         for (uint32_t e = lo + lane; e < hi; e += 32) {
             const uint32_t v = vals[start + e];
-            const uint32_t* pp = table29 + (size_t)(v & rowmask) * G2T29_WORDS;
-            const G2Chunk cx = g2_chunk_load(pp), cy = g2_chunk_load(pp + ((v >> 31) ? 40 : 20));
+            const uint32_t* pp = table29 + (size_t)(v & rowmask) * G2ROW_WORDS;
+            const G2Chunk cx = g2_chunk_load(pp), cy = g2_chunk_load(pp + ((v >> 31) ? G2ROW_NEG_Y : G2ROW_Y));
             if (cx.w[18]) continue;                        // base at infinity
             F2x29 x2, y2;
 #pragma unroll
@@ -310,24 +310,8 @@ zkc_msm_bucketwave_g2(const uint32_t* __restrict__ table29_all, const MsmJobList
 }
 
 // buckets with many segments (repeated witness values; every bucket of a 2^20-point job) are summed by one wave each: lanes stride over
-// the segments, then a tree over the lanes in LDS; the result replaces the bucket's first segment.  Radix-2^29 coordinates, one traits
-// struct per group.
-struct Merge29G1 {
-    typedef Fq F; typedef Acc29 Acc;
-    static __device__ __forceinline__ void set_inf(Acc& a) { f29_pt_set_inf(a); }
-    static __device__ __forceinline__ bool is_inf(const Acc& a) { return f29_pt_is_inf(a); }
-    static __device__ __forceinline__ Acc from(const XYZZ<F>& p) { return f29_pt_from_xyzz(p); }
-    static __device__ __forceinline__ XYZZ<F> to(const Acc& a) { return f29_pt_to_xyzz(a); }
-    static __device__ __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29_pt_add(r, a, b); }
-};
-struct Merge29G2 {
-    typedef Fq2 F; typedef Acc29G2 Acc;
-    static __device__ __forceinline__ void set_inf(Acc& a) { f29g2_pt_set_inf(a); }
-    static __device__ __forceinline__ bool is_inf(const Acc& a) { return f29g2_pt_is_inf(a); }
-    static __device__ __forceinline__ Acc from(const XYZZ<F>& p) { return f29g2_pt_from_xyzz(p); }
-    static __device__ __forceinline__ XYZZ<F> to(const Acc& a) { return f29g2_pt_to_xyzz(a); }
-    static __device__ __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29g2_pt_add(r, a, b); }
-};
+// the segments, then a tree over the lanes in LDS; the result replaces the bucket's first segment.  Radix-2^29 coordinates; G = G1Ops / G2Ops
+// (zkc_point_ops.h).
 template <class G>
 __global__ void __launch_bounds__(64)
 zkc_msm_merge29(XYZZ<typename G::F>* __restrict__ partial, const uint32_t* __restrict__ segoff, uint32_t* __restrict__ segcnt,
@@ -338,14 +322,14 @@ zkc_msm_merge29(XYZZ<typename G::F>* __restrict__ partial, const uint32_t* __res
         const uint32_t b = heavy[h], s0 = segoff[b];
         uint32_t s1 = s0 + segcnt[b]; if (s1 > max_segments) s1 = max_segments;
         typename G::Acc acc; G::set_inf(acc);
-        for (uint32_t s = s0 + threadIdx.x; s < s1; s += 64) { const XYZZ<typename G::F> p = partial[s]; if (!p.is_inf()) { const typename G::Acc q = G::from(p); G::add(acc, acc, q); } }
+        for (uint32_t s = s0 + threadIdx.x; s < s1; s += 64) { const XYZZ<typename G::F> p = partial[s]; if (!p.is_inf()) { const typename G::Acc q = G::from_xyzz(p); G::add(acc, acc, q); } }
         __syncthreads();
         sh[threadIdx.x] = acc; __syncthreads();
         for (int st = 32; st > 0; st >>= 1) {
             if ((int)threadIdx.x < st) { typename G::Acc t = sh[threadIdx.x]; G::add(t, t, sh[threadIdx.x + st]); sh[threadIdx.x] = t; }
             __syncthreads();
         }
-        if (threadIdx.x == 0) { partial[s0] = G::is_inf(sh[0]) ? XYZZ<typename G::F>::inf() : G::to(sh[0]); segcnt[b] = 1; }
+        if (threadIdx.x == 0) { partial[s0] = G::is_inf(sh[0]) ? XYZZ<typename G::F>::inf() : G::leave(sh[0]); segcnt[b] = 1; }
         __syncthreads();
     }
 }
@@ -519,7 +503,7 @@ int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c) { 
 int msm_precompute_g2(zkc_ctx* ctx, uint32_t count, G2Affine* d_table, int c) { return precompute<Fq2>(ctx, count, d_table, c); }
 int msm_g2_rows29(zkc_ctx* ctx, const G2Affine* d_points, size_t n, const char* what, uint32_t** out) {
     DevBuf rows; int rc;
-    if ((rc = rows.alloc(ctx, n * G2T29_WORDS * sizeof(uint32_t))) || (rc = msm_g2_table29(ctx, d_points, rows.as<uint32_t>(), n))) return rc;
+    if ((rc = rows.alloc(ctx, n * G2ROW_WORDS * sizeof(uint32_t))) || (rc = msm_g2_table29(ctx, d_points, rows.as<uint32_t>(), n))) return rc;
     const hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     *out = (uint32_t*)rows.release();
@@ -572,32 +556,31 @@ zkc_fold_gsum(const XYZZ<F>* __restrict__ in, const uint32_t* __restrict__ gstar
     for (uint32_t i = gstart[g], e = gstart[g + 1]; i < e; i++) acc = xyzz_add(acc, in[i]);
     out[g] = acc;
 }
+// tmp (nw points) and out (ngroups points) are device work space; the sums stay in `out` and are copied to h_out
+template <class F>
+static int fold_group_sums_ws(zkc_ctx* ctx, const Affine<F>* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
+                              const uint32_t* d_gstart, uint32_t ngroups, XYZZ<F>* tmp, XYZZ<F>* out, XYZZ<F>* h_out, uint32_t pt_mod, hipStream_t st) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<F>), dim3((nw + 63) / 64), dim3(64), 0, st, tbl, d_scalars, d_wires, nw, pt_shift, tmp, pt_mod);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<F>), dim3((ngroups + 63) / 64), dim3(64), 0, st, tmp, d_gstart, ngroups, out);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, out, (size_t)ngroups * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, st));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return ZKC_OK;
+}
 template <class F>
 static int fold_group_sums(zkc_ctx* ctx, const Affine<F>* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
                            const uint32_t* d_gstart, uint32_t ngroups, XYZZ<F>* h_out, uint32_t pt_mod, hipStream_t st) {
     DevBuf tmp, out; int rc;
-    if (!st) st = ctx->stream;
     if ((rc = tmp.alloc(ctx, (size_t)nw * sizeof(XYZZ<F>))) || (rc = out.alloc(ctx, (size_t)ngroups * sizeof(XYZZ<F>)))) return rc;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<F>), dim3((nw + 63) / 64), dim3(64), 0, st, tbl, d_scalars, d_wires, nw, pt_shift, tmp.as<XYZZ<F>>(), pt_mod);
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<F>), dim3((ngroups + 63) / 64), dim3(64), 0, st, tmp.as<XYZZ<F>>(), d_gstart, ngroups, out.as<XYZZ<F>>());
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, out.p, (size_t)ngroups * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, st));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    return ZKC_OK;
+    return fold_group_sums_ws<F>(ctx, tbl, d_scalars, d_wires, nw, pt_shift, d_gstart, ngroups, tmp.as<XYZZ<F>>(), out.as<XYZZ<F>>(), h_out, pt_mod, st ? st : ctx->stream);
 }
 int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G1XYZZ* o, uint32_t pt_mod, hipStream_t st) {
     return fold_group_sums<Fq>(ctx, tbl, s, w, nw, sh, gs, ng, o, pt_mod, st);
 }
 // the batch verifier's form: scratch and sums in buffers of the caller's (the context's verifier work space), the sums left on the device for the Miller kernels and copied to h_out
 int fold_group_sums_g1_ws(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, const uint32_t* gs, uint32_t ng, G1XYZZ* d_tmp, G1XYZZ* d_out, G1XYZZ* h_out) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<Fq>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, s, w, nw, 0, d_tmp, 0u);
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_gsum<Fq>), dim3((ng + 63) / 64), dim3(64), 0, ctx->stream, d_tmp, gs, ng, d_out);
-    ZKC_HIP_CHECK(ctx, hipGetLastError());
-    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_out, (size_t)ng * sizeof(G1XYZZ), hipMemcpyDeviceToHost, ctx->stream));
-    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return ZKC_OK;
+    return fold_group_sums_ws<Fq>(ctx, tbl, s, w, nw, 0, gs, ng, d_tmp, d_out, h_out, 0u, ctx->stream);
 }
 int fold_group_sums_g2(zkc_ctx* ctx, const G2Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G2XYZZ* o, uint32_t pt_mod, hipStream_t st) {
     return fold_group_sums<Fq2>(ctx, tbl, s, w, nw, sh, gs, ng, o, pt_mod, st);
@@ -684,7 +667,7 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
     // entries per accumulation lane: long segments mean fewer partial sums to reduce (best for a full pass), but a lane walks its segment
     // serially, so a small pass (one proof) wants short ones: aim at ~2 waves per SIMD
     const uint32_t seg = (uint32_t)std::min<size_t>(MSM_SEG, std::max<size_t>(MSM_SEG_MIN, total / 131072));
-    constexpr bool kG2 = sizeof(F) == sizeof(Fq2);
+    typedef typename GroupOf<F>::Ops G; constexpr bool kG2 = GroupOf<F>::g2;
     const uint32_t bw_slices = (uint32_t)std::min<size_t>(32, w.max_segments / std::max<uint32_t>(nb, 1u));      // slices a heavy bucket may be cut into: nb x slices partial sums must fit
     const uint32_t* const g2_table29 = (kG2 && jl.job[0].c == (uint32_t)MSM_C_G2_LONE) ? zk->d_g2_29_lone : (kG2 && zk->c_deep && jl.job[0].c == (uint32_t)zk->c_deep) ? zk->d_g2_29_deep : zk->d_g2_29;       // a G2 pass is of one window size
     const bool bucket_wave = kG2 && sw::on<sw::ZKC_G2_BUCKET_WAVE>() && nb <= 8192 && bw_slices >= 1;         // a small G2 pass: half a wave per bucket (zkc_msm_bucketwave_g2), no segment lists
@@ -742,14 +725,9 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
           }
           else {
             const int g2_form = (int)sw::value<sw::ZKC_G2_ACC>(0);      // 0: registers hold the next row (one wave per SIMD); 1 / 2: LDS-DMA prefetch at one / two waves per SIMD
-            if (g2_form == 2)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_accumulate29_g2_dma<2>), dim3((unsigned)((seg_bound + G2DMA_T - 1) / G2DMA_T)), dim3(G2DMA_T), 0, st,
-                                   g2_table29, (const MsmJobList*)w.d_jobs, w.vals2, w.off, w.bcnt, w.segoff, w.seg2bucket, w.perm, nb, reinterpret_cast<XYZZ<Fq2>*>(partial), (uint32_t)w.max_segments);
-            else if (g2_form == 1)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_accumulate29_g2_dma<1>), dim3((unsigned)((seg_bound + G2DMA_T - 1) / G2DMA_T)), dim3(G2DMA_T), 0, st,
-                                   g2_table29, (const MsmJobList*)w.d_jobs, w.vals2, w.off, w.bcnt, w.segoff, w.seg2bucket, w.perm, nb, reinterpret_cast<XYZZ<Fq2>*>(partial), (uint32_t)w.max_segments);
-            else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_accumulate29_g2<1>), dim3((unsigned)((seg_bound + 127) / 128)), dim3(128), 0, st,
+            auto* const kernel = g2_form == 2 ? zkc_msm_accumulate29_g2_dma<2> : g2_form == 1 ? zkc_msm_accumulate29_g2_dma<1> : zkc_msm_accumulate29_g2<1>;
+            const unsigned T = g2_form == 1 || g2_form == 2 ? G2DMA_T : 128;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((seg_bound + T - 1) / T)), dim3(T), 0, st,
                                g2_table29, (const MsmJobList*)w.d_jobs, w.vals2, w.off, w.bcnt, w.segoff, w.seg2bucket, w.perm, nb, reinterpret_cast<XYZZ<Fq2>*>(partial), (uint32_t)w.max_segments);
           }
         } else {  // G1: same layout, field type with the inlined product.  160 VGPRs = 3 waves per SIMD; capped at 128 (4 waves) the accumulator spills and the kernel is 3.6x slower
@@ -770,12 +748,7 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
     }
     {
         zkc_prof_scope _pr(ctx, ZKC_PROF_MSM_REDUCE, 0, st);
-        if constexpr (kG2) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_merge29<Merge29G2>), dim3(1024), dim3(64), 0, st, reinterpret_cast<XYZZ<Fq2>*>(partial), w.segoff, w.segcnt, w.heavy,
-                               w.heavy + MSM_MAX_HEAVY, (uint32_t)w.max_segments);
-        } else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_merge29<Merge29G1>), dim3(1024), dim3(64), 0, st, reinterpret_cast<XYZZ<Fq>*>(partial), w.segoff, w.segcnt, w.heavy,
-                               w.heavy + MSM_MAX_HEAVY, (uint32_t)w.max_segments);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_merge29<G>), dim3(1024), dim3(64), 0, st, partial, w.segoff, w.segcnt, w.heavy, w.heavy + MSM_MAX_HEAVY, (uint32_t)w.max_segments);
         ZKC_LAUNCH_CHECK(ctx, "zkc_msm_merge");
         if constexpr (kG2)
             hipLaunchKernelGGL(zkc_msm_window29_g2, dim3(jl.total_windows), dim3(64), 0, st, reinterpret_cast<const XYZZ<Fq2>*>(partial), w.segoff, w.segcnt,

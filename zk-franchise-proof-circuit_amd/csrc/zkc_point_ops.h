@@ -1,7 +1,8 @@
 // zkc_point_ops.h -- G1 and G2 behind one interface for the kernels that work on the points of a file (zkc_phase2.hip: one scalar times many points; zkc_setup_ptau.hip:
 // a sparse matrix times a vector of points; zkc_ecntt.hip: a transform over points): the check of such a point, an accumulator in radix 2^29, set from / added to by an
 // affine point in Montgomery words, the complete additions of two such accumulators, and the trait by which host code that is generic in the field picks the group
-// (GroupOf).  The operations are device only and the header needs hipcc: a plain C++ host program (tests/host/*.cc) cannot include it.  Product code.
+// (GroupOf).  The merge kernel of the MSM's bucket reduction (zkc_msm_merge29, zkc_msm.hip) is instantiated with the same two structs, for the complete addition and the
+// way in and out of the accumulator (from_xyzz, add, is_inf, set_inf, leave).  The operations are device only and the header needs hipcc: a plain C++ host program (tests/host/*.cc) cannot include it.  Product code.
 //
 // The additions.  Unlike a prover's bases these points are an adversary's, or merely unlucky, and an addition can meet equal points, opposite points and infinity.  So:
 // an all-zero point is skipped, an accumulator at infinity is set rather than added to, and f29_madd's `false` return is taken at every mixed addition -- equal: double
@@ -66,6 +67,7 @@ struct G1Ops {
     __device__ static __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29_pt_add(r, a, b); }
     __device__ static __forceinline__ void pt_dbl(Acc& r, const Acc& a) { f29_pt_dbl(r, a); }
     __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29_pt_is_inf(a); }
+    __device__ static __forceinline__ void set_inf(Acc& a) { f29_pt_set_inf(a); }
 };
 struct G2Ops {
     static constexpr int W = 32;
@@ -91,6 +93,7 @@ struct G2Ops {
     __device__ static __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { f29g2_pt_add(r, a, b); }
     __device__ static __forceinline__ void pt_dbl(Acc& r, const Acc& a) { f29g2_pt_dbl(r, a); }
     __device__ static __forceinline__ bool is_inf(const Acc& a) { return f29g2_pt_is_inf(a); }
+    __device__ static __forceinline__ void set_inf(Acc& a) { f29g2_pt_set_inf(a); }
 };
 
 // field -> group, for host code that is generic in F: the operations its kernels are instantiated with, and the words its messages need

@@ -11,6 +11,7 @@
 #include "zkc_hostparse.h"
 #include "zkc_host_util.h"
 #include "zkc_kernels.h"
+#include "zkc_f29_g2.h"
 #include <cstring>
 #include <ctime>
 #include <cstdio>
@@ -273,7 +274,7 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     if ((rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offA, zk->c_sec)) || (rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offB1, zk->c_sec)) ||
         (rc = msm_precompute_g1(ctx, nc, zk->d_g1 + zk->offC, zk->c_sec)) || (rc = msm_precompute_g1(ctx, n, zk->d_g1 + zk->offH, zk->c_h)) ||
         (rc = msm_precompute_g2(ctx, nv, zk->d_g2, zk->c_sec))) return bail(rc);
-    if ((rc = dmalloc(ctx, &zk->d_g2_29, 60 * (size_t)NWS * nv)) || (rc = msm_g2_table29(ctx, zk->d_g2, zk->d_g2_29, (size_t)NWS * nv))) return bail(rc);
+    if ((rc = dmalloc(ctx, &zk->d_g2_29, G2ROW_WORDS * (size_t)NWS * nv)) || (rc = msm_g2_table29(ctx, zk->d_g2, zk->d_g2_29, (size_t)NWS * nv))) return bail(rc);
     if (zk->c_deep) {   // the sections again for c_deep-bit windows (at nLevels = 160: 15 bits, 17 x 64 B per wire and G1 section, 17 x 240 B for G2: 0.6 GB beside the 0.8 GB of the 12-bit tables)
         ZKC_UP(zk->d_g1 + zk->offA_deep, sec[5], 64ull * nv); ZKC_UP(zk->d_g1 + zk->offB1_deep, sec[6], 64ull * nv); ZKC_UP(zk->d_g1 + zk->offC_deep, sec[8], 64ull * nc);
         if ((rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offA_deep, zk->c_deep)) || (rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offB1_deep, zk->c_deep)) ||

@@ -208,7 +208,7 @@ struct zkc_zkey {
     uint32_t *d_tw_fwd29 = nullptr, *d_tw_inv29 = nullptr;                  // the twiddles in radix 2^29 (what the NTT passes read)
     // pre-shifted base tables, one allocation per group: G1 = [A | B1 | C | H], G2 = [B2]; T[w][i] = 2^(c*w) * P_i
     zkc::G1Affine* d_g1 = nullptr; zkc::G2Affine* d_g2 = nullptr;
-    uint32_t* d_g2_29 = nullptr;                                            // the G2 table again in radix 2^29 (60 words per point: x, y, -y), read by the accumulation
+    uint32_t* d_g2_29 = nullptr;                                            // the G2 table again in radix 2^29 (G2ROW_WORDS per point: x, y, -y; zkc_f29_g2.h), read by the accumulation
     uint32_t* d_g2_29_lone = nullptr;                                       // the same bases pre-shifted for MSM_C_G2_LONE (32 windows), radix 2^29 only; nullptr: not built (ZKC_G2_LONE_TABLE=0)
     uint32_t offA = 0, offB1 = 0, offC = 0, offH = 0;                       // table offsets inside d_g1 (points)
     // [r4] a census key of 2^16 wires and more keeps its witness sections a second time, pre-shifted for c_deep = 17-bit windows: a pass whose voters sit deep in the trees (or
@@ -280,7 +280,7 @@ int ntt_make_tw29(zkc_ctx* ctx, const Fr* d_tw, uint32_t count, uint32_t** out);
 struct TwiddleTables { Fr *fwd = nullptr, *inv = nullptr; uint32_t *fwd29 = nullptr, *inv29 = nullptr; };
 // with_29 = false (and keep_fr): the Fr tables alone, fwd29 / inv29 stay nullptr and no conversion kernel runs (zkc_ecntt.hip reads scalars, not limbs)
 int ntt_twiddle_tables(zkc_ctx* ctx, int logn, bool keep_fr, TwiddleTables* out, bool with_29 = true);
-// the window-c table of `count` G2 bases (device, window 0 = the bases as a .zkey stores them) in the accumulation's row form, 60 words per point: a copy of the bases is
+// the window-c table of `count` G2 bases (device, window 0 = the bases as a .zkey stores them) in the accumulation's row form, G2ROW_WORDS per point (zkc_f29_g2.h): a copy of the bases is
 // shifted to msm_nw(c) windows, converted and dropped.  *out is written on success only; ends with ctx->stream synchronised
 int msm_g2_window_table29(zkc_ctx* ctx, const G2Affine* d_bases, uint32_t count, int c, const char* what, uint32_t** out);
 // n affine G2 points (device) -> a fresh table of their rows; the stream is synchronised, so the caller may drop the points
@@ -337,7 +337,7 @@ size_t zkey_device_bytes(const zkc_zkey* zk, size_t* tables, size_t* work);     
 size_t finalize_scratch_bytes(int nproofs);
 int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c);   // d_table[0..count) = base on entry
 int msm_precompute_g2(zkc_ctx* ctx, uint32_t count, G2Affine* d_table, int c);
-int msm_g2_table29(zkc_ctx* ctx, const G2Affine* d_table, uint32_t* d_out, size_t count);       // d_out: 60 words per point
+int msm_g2_table29(zkc_ctx* ctx, const G2Affine* d_table, uint32_t* d_out, size_t count);       // d_out: G2ROW_WORDS per point (zkc_f29_g2.h)
 // out[i] = scalar[wires[i]] * P[wires[i] - pt_shift] (window-0 table), then per-group sums: gsum[g] = sum out[gstart[g]..gstart[g+1])
 // pt_mod != 0: d_scalars holds several witnesses of pt_mod wires each and wires[i] = witness * pt_mod + wire (the point is P[wire - pt_shift]); st: the stream (nullptr: the context's)
 int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, int32_t pt_shift,
