@@ -1,6 +1,6 @@
 """Scalar sets for the MSM sections of a key (zkc_msm_debug), shared by tests/test_gpu_prover.py and tests/test_00_gpu_msm_forms.py (with its child
-tests/host/msm_forms_child.py): a mix with a heavy bucket, and sets that put equal and opposite points into one bucket.  No GPU, no library: the oracle's
-zkey_parse and plain Python."""
+tests/host/msm_forms_child.py): a mix with a heavy bucket, and sets that put equal and opposite points into one bucket.  No GPU: the oracle's
+zkey_parse and plain Python; edge_key alone calls the library's host-side key generator, once per directory."""
 import collections, ctypes
 import oracle_lib as ol
 
@@ -82,3 +82,48 @@ def forms_scalars(z, which):
     assert len(dup) > 96, 'the largest group of equal points no longer fills four blocks of 32 entries: form_cases has lost its point'
     sets = [scalar_bytes(cnt, v) for v in equal_opposite_cases(dup, cnt, random.Random(11)) + form_cases(dup)]
     return std, sets + [heavy_mix(cnt, random.Random(3))]
+
+
+# ---- a generic key whose point sections hold bases with coordinates at the edges of the field (tests/edge_points.py) ----
+EDGE_KEY = (5000, 3000, 8)               # constraints, wires, public signals of the random circuit: a 12-bit window, a G2 section of half a wave per bucket
+EDGE_KEY_SEEDS = (3000, 68, 21)          # circuit, toxic waste, patch
+EDGE_KEY_FILE = 'edge_points_3000.zkey'
+
+
+def edge_key_dir(tmp_path_factory):
+    """one directory per test session, so that every module (and every child) that wants the key shares one image"""
+    d = tmp_path_factory.getbasetemp() / 'edge_key'
+    d.mkdir(exist_ok=True)
+    return d
+
+
+def edge_key(directory):
+    """The patched image: made on the host and written to `directory` on first use, read from there afterwards (the bytes are the same either way).  A random R1CS
+    key of 3 000 wires, its sections A, B1, B2 and C overwritten with pool points by edge_points.patch_zkey -- the key loader takes a section's points as they are."""
+    import os, pathlib
+    import edge_points as ep
+    path = os.path.join(str(directory), EDGE_KEY_FILE)
+    if not os.path.exists(path):
+        from test_generic_circuit import random_instance, setup_key
+        r1, _ = random_instance(pathlib.Path(str(directory)), *EDGE_KEY, seed=EDGE_KEY_SEEDS[0])
+        zk, _ = setup_key(r1, EDGE_KEY_SEEDS[1])
+        img, _ = ep.patch_zkey(zk, ([e.point for e in ep.g1_pool()], [e.point for e in ep.g2_pool()]), EDGE_KEY_SEEDS[2])
+        with open(path + '.tmp%d' % os.getpid(), 'wb') as fh:
+            fh.write(img)
+        os.replace(path + '.tmp%d' % os.getpid(), path)
+    return open(path, 'rb').read()
+
+
+def low_window(cnt, rng, c=12):
+    """every scalar inside the lowest window: each addition then takes a window-0 table row, which is the key's own coordinates"""
+    return b''.join(rng.randrange(1, 1 << c).to_bytes(32, 'little') for _ in range(cnt))
+
+
+def edge_forms_scalars(z, which):
+    """(std points of the section of the parsed edge key, its scalar sets in the order the child runs them): low window, uniform, heavy mix"""
+    import random
+    cnt = z.nVars
+    _, std = section_points(z, which, cnt)
+    rng = random.Random(40 + which)
+    uniform = b''.join(rng.randrange(R).to_bytes(32, 'little') for _ in range(cnt))
+    return std, [low_window(cnt, rng), uniform, heavy_mix(cnt, random.Random(5))]
