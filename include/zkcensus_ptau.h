@@ -17,6 +17,8 @@
  * The file is not trusted: every point read is checked for coordinates < q and for being on its curve, and before anything is written:
  *   sum_c L_c = G1, sum_c L2_c = G2, sum_c La_c = alpha1, sum_c Lb_c = beta1 (the Lagrange basis is a partition of unity: a wrong block, offset or byte order fails
  *   here), and sameRatio(G1, beta1; G2, beta2).
+ * That ties the key to the Lagrange sections; zkc_ptau_check_prepared (zkcensus_ptau_prepare.h) ties those to the monomial sections 2 .. 5, and zkc_ptau_verify
+ * (zkcensus_ptau_verify.h) checks that the monomial sections are the powers of one tau, alpha, beta: the three together are what "not trusted" means for a downloaded file.
  * Only the ranges the circuit needs are read (the section table first, then pread at 64-bit offsets): a 2^28 file serves a 2^17 circuit.
  *
  * Section 10 of the key written opens with csHash = BLAKE2b-512 over, in this order,

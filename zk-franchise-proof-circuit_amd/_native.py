@@ -155,6 +155,11 @@ def load():
     L.zkc_ptau_prepare.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz]
     L.zkc_ptau_check_prepared.argtypes = [vp, ctypes.c_char_p, u32p, u64p, ctypes.c_char_p, sz]
     L.zkc_ptau_prepare_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.zkc_g1_wsum_pair_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_char_p]
+    L.zkc_g2_wsum_pair_dev.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_char_p]
+    L.zkc_ptau_verify.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, u32p, u32p, u64p, ctypes.c_char_p, sz]
+    L.zkc_ptau_verify_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.zkc_debug_ptau_verify.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_char_p, u32p, u32p, u64p, ctypes.c_char_p, sz]
     _lib = L
     return L
 

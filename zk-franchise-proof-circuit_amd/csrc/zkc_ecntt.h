@@ -18,6 +18,9 @@ int ecntt_twiddles(zkc_ctx* ctx, uint32_t logn, Fr** d_tw);
 // logn < 2).  d_out may be d_pts.  Launches on ctx->stream, has synchronised and freed its work space on return; the context's lock is held by the caller.  ms (may be NULL):
 // += [0] the transform, [1] to affine.
 template <class F> int ecntt(zkc_ctx* ctx, const void* d_pts, uint32_t logn, const Fr* d_tw, uint32_t tw_logn, void* d_out, bool out_mont, double* ms);
+// ncoord coordinates of 32 B in standard form at d_in -> Montgomery form at d_out, on ctx->stream and not waited for (the engines' mont = 0 inputs: zkc_g1_lagrange_dev,
+// zkc_g1_wsum_pair_dev and their G2 forms).  A coordinate >= q is copied as it is, for points_check_dev to find.
+int coords_to_mont(zkc_ctx* ctx, const void* d_in, void* d_out, size_t ncoord);
 // the device bytes one call needs beside d_pts and d_out
 inline size_t ecntt_work_bytes(uint32_t logn, bool g2) { return ((size_t)1 << logn) * (g2 ? sizeof(G2XYZZ) : sizeof(G1XYZZ)) * 2; }
 

@@ -115,10 +115,7 @@ int lagrange_entry(zkc_ctx* ctx, const void* d_points, uint32_t logn, int mont, 
     DevBuf conv, tw; int rc;
     const void* src = d_points;
     if (!mont) {
-        if ((rc = conv.alloc(ctx, (size_t)n * PT))) return rc;
-        const size_t ncoord = (size_t)n * (PT / 32);
-        hipLaunchKernelGGL(zkc_ecntt_to_mont, dim3((unsigned)((ncoord + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_points, conv.as<uint32_t>(), ncoord);
-        ZKC_HIP_CHECK(ctx, hipGetLastError());
+        if ((rc = conv.alloc(ctx, (size_t)n * PT)) || (rc = coords_to_mont(ctx, d_points, conv.p, (size_t)n * (PT / 32)))) return rc;
         src = conv.p;
     }
     uint32_t bad = 0;
@@ -131,6 +128,13 @@ int lagrange_entry(zkc_ctx* ctx, const void* d_points, uint32_t logn, int mont, 
 }  // namespace
 
 namespace zkc {
+
+int coords_to_mont(zkc_ctx* ctx, const void* d_in, void* d_out, size_t ncoord) {
+    if (!ncoord) return ZKC_OK;
+    hipLaunchKernelGGL(zkc_ecntt_to_mont, dim3((unsigned)((ncoord + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_in, (uint32_t*)d_out, ncoord);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    return ZKC_OK;
+}
 
 int ecntt_twiddles(zkc_ctx* ctx, uint32_t logn, Fr** d_tw) {
     if (logn < 1 || logn > ECNTT_MAX_LOGN) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "ecntt_twiddles: bad size");

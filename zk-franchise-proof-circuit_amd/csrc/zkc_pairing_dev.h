@@ -17,6 +17,7 @@ int miller_membership_begin(zkc_ctx* ctx, const G2Affine* h_Q, uint32_t N);
 void miller_join(zkc_ctx* ctx);
 int miller_product_dev(zkc_ctx* ctx, const G1XYZZ* d_P, uint32_t N, pairing::Fq12* product, int* bad, std::vector<pairing::Fq12>* tops = nullptr);
 int miller_membership_each(zkc_ctx* ctx, uint32_t N, int32_t* h_flag);
+int g2_membership_first_bad(zkc_ctx* ctx, const G2Affine* d_Q, uint32_t N, uint32_t* bad);      // the membership kernel over the caller's device points: the smallest index outside G2
 int miller_sum_trees(zkc_ctx* ctx, const G1XYZZ* d_C, uint32_t N, std::vector<G1XYZZ>& h);
 int miller_round_levels(zkc_ctx* ctx, const G1XYZZ* d_P, uint32_t N, uint32_t c);
 int miller_nodes_fetch(zkc_ctx* ctx, uint32_t n, const uint32_t (*node)[2], size_t count, pairing::Fq12* out);

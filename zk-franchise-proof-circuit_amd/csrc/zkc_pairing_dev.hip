@@ -231,6 +231,21 @@ int miller_membership_each(zkc_ctx* ctx, uint32_t N, int32_t* h_flag) {
         (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return dev_fail(ctx, e, "miller_membership_each");
     return ZKC_OK;
 }
+// the same kernel over points of the caller's (zkc_ptau_verify.hip: section 3 of a powers-of-tau file): *bad = the smallest index of a point of d_Q (N points on the
+// device, Montgomery form, all zero = infinity, which passes) that is off the twist or outside G2, 0xffffffff when there is none.  Has synchronised on return.
+int g2_membership_first_bad(zkc_ctx* ctx, const G2Affine* d_Q, uint32_t N, uint32_t* bad) {
+    *bad = 0xffffffffu;
+    if (!N) return ZKC_OK;
+    DevBuf flag; int rc;
+    if ((rc = flag.alloc(ctx, (size_t)N * sizeof(int32_t)))) return rc;
+    hipLaunchKernelGGL(zkc_g2_membership_each, dim3((N + 63) / 64), dim3(64), 0, ctx->stream, d_Q, N, miller_consts(), flag.as<int32_t>());
+    std::vector<int32_t> h(N);
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpyAsync(h.data(), flag.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return dev_fail(ctx, e, "g2_membership_first_bad");
+    for (uint32_t i = 0; i < N; i++) if (h[i]) { *bad = i; break; }
+    return ZKC_OK;
+}
 // the sum trees over the singletons d_C[i] = rho_i C_i, one per round of pairs and of the shape of that round's product tree, every level kept: the tree of round c starts
 // at h[c * TreeShape(min(N, chunk)).nodes], its level k at TreeShape(n_c).off[k]
 int miller_sum_trees(zkc_ctx* ctx, const G1XYZZ* d_C, uint32_t N, std::vector<G1XYZZ>& h) {

@@ -1,5 +1,5 @@
 // zkc_point_ops.h -- G1 and G2 behind one interface for the kernels that work on the points of a file (zkc_phase2.hip: one scalar times many points; zkc_setup_ptau.hip:
-// a sparse matrix times a vector of points; zkc_ecntt.hip: a transform over points): the check of such a point, an accumulator in radix 2^29, set from / added to by an
+// a sparse matrix times a vector of points; zkc_ecntt.hip: a transform over points; zkc_ptau_verify.hip: two weighted sums over consecutive points): the check of such a point, an accumulator in radix 2^29, set from / added to by an
 // affine point in Montgomery words, the complete additions of two such accumulators, and the trait by which host code that is generic in the field picks the group
 // (GroupOf).  The merge kernel of the MSM's bucket reduction (zkc_msm_merge29, zkc_msm.hip) is instantiated with the same two structs, for the complete addition and the
 // way in and out of the accumulator (from_xyzz, add, is_inf, set_inf, leave).  The operations are device only and the header needs hipcc: a plain C++ host program (tests/host/*.cc) cannot include it.  Product code.
@@ -16,6 +16,8 @@
 //   add_point, opposite   G1: setup, the K rows with alpha = -beta.  G1, G2: repeats `pm`, `pmp`, `k-k`, `half` (zkc_ptau_acc)
 //   G::add, equal         G1, G2: repeats `red_eq` at the first reduction step, `red_eq2` at the second, `red3_eq` at the third (zkc_ptau_red)
 //   G::add, opposite      G1, G2: repeats `red_op` (zkc_ptau_red)
+// zkc_wsum (zkc_ptau_verify.hip) reaches all three in both groups, and in G2 on twist points outside G2, in tests/test_gpu_ptau_verify.py: the sets `same` (equal), `alternating`
+// (opposite, then set again from infinity) and `infinities`, and the files with tau = 1, tau = r - 1 and tau on the domain; its partial sums meet G::add's cases in zkc_ptau_red there.
 // The double-and-add users of add_point (zkc_ptau_scale, the load kernel of zkc_ecntt.hip) meet no equal or opposite operand for a scalar below r, so no test takes the
 // `false` return there; zkc_p2_scale_g1 walks signed digits and meets it for the scalar r - 2 alone (zkc_phase2.hip).
 #pragma once

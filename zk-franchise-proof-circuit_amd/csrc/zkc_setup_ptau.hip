@@ -37,6 +37,7 @@
 #include "zkc_f29_g1.h"
 #include "zkc_f29_g2.h"
 #include "zkc_point_ops.h"
+#include "zkc_point_red.h"
 #include "zkc_pairing.h"
 #include "zkc_file_points.h"
 #include "zkc_jds.h"
@@ -51,7 +52,7 @@ using namespace zkc;
 namespace {
 
 constexpr uint32_t SEG = 32;                     // terms per lane of the accumulation
-constexpr uint32_t RED = 32;                     // partial sums per lane of a reduction step
+// RED, the partial sums per lane of a reduction step: POINT_RED (zkc_point_red.h)
 constexpr uint32_t T_NEG = 0x80000000u, T_IDX = 0x7fffffffu;
 
 // ================================================================ device ================================================================
@@ -104,19 +105,7 @@ zkc_ptau_acc(const uint32_t* __restrict__ pts, uint32_t npts, const uint32_t* __
     part[s] = o;
 }
 
-// ---- reduce: out[j] = sum of in[job_start[j] .. job_start[j + 1]) (at most RED of them; none: infinity), complete additions ----
-template <class G> __global__ void __launch_bounds__(64)
-zkc_ptau_red(const XYZZ<typename G::F>* __restrict__ in, const uint32_t* __restrict__ job_start, uint32_t njobs, XYZZ<typename G::F>* __restrict__ out) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= njobs) return;
-    const uint32_t a = job_start[j]; uint32_t b = job_start[j + 1];
-    if (b - a > RED) b = a + RED;
-    if (a == b) { out[j] = XYZZ<typename G::F>::inf(); return; }
-    if (b - a == 1) { out[j] = in[a]; return; }
-    typename G::Acc acc = G::from_xyzz(in[a]);
-    for (uint32_t i = a + 1; i < b; i++) { const typename G::Acc o = G::from_xyzz(in[i]); typename G::Acc r; G::add(r, acc, o); acc = r; }
-    out[j] = G::is_inf(acc) ? XYZZ<typename G::F>::inf() : G::leave(acc);
-}
+// ---- reduce: zkc_ptau_red, shared with zkc_ptau_verify.hip (zkc_point_red.h) ----
 
 // ================================================================ host ================================================================
 
@@ -180,21 +169,11 @@ bool make_plan(Builder& B, Plan& P, std::string& why) {
     return true;
 }
 
-// the reduction steps of a plan: step i sums, per job j, the partial sums [start[j], start[j + 1]) of step i - 1's output; the last step has one job per sorted row
-std::vector<std::vector<uint32_t>> reduction_steps(const Plan& P) {
-    std::vector<std::vector<uint32_t>> steps;
+// the reduction steps of a plan (reduction_steps, zkc_point_red.h): the partial sums of the row at sorted position p are its segments
+std::vector<uint32_t> row_counts(const Plan& P) {
     std::vector<uint32_t> cnt(P.nrows);
     for (uint32_t p = 0; p < P.nrows; p++) cnt[p] = P.rowseg[p + 1] - P.rowseg[p];
-    for (;;) {
-        const uint32_t maxc = P.nrows ? *std::max_element(cnt.begin(), cnt.end()) : 0;
-        std::vector<uint32_t> start; start.push_back(0);
-        if (maxc <= RED) { for (uint32_t p = 0; p < P.nrows; p++) start.push_back(start.back() + cnt[p]); steps.push_back(std::move(start)); return steps; }
-        for (uint32_t p = 0; p < P.nrows; p++) {
-            for (uint32_t c = 0; c < cnt[p]; c += RED) start.push_back(start.back() + std::min(RED, cnt[p] - c));
-            cnt[p] = (cnt[p] + RED - 1) / RED;
-        }
-        steps.push_back(std::move(start));
-    }
+    return cnt;
 }
 
 // ---- stage 3 on host threads (zkc_curve.h), over the same plan ----
@@ -259,24 +238,13 @@ int run_dev(zkc_ctx* ctx, const Plan& P, const std::vector<Affine<F>>& base, std
         if ((rc = fixed_affine<F>(ctx, prod.as<XYZZ<F>>(), nj, (uint8_t*)pts.p + (size_t)P.nbase * PT, true))) return rc;      // synchronises
     }
     const clk::time_point t2 = clk::now();
-    DevBuf cur, nxt;
+    DevBuf cur;
     if ((rc = cur.alloc(ctx, (size_t)P.nseg * sizeof(XYZZ<F>)))) return rc;
     if (P.nseg) {
         hipLaunchKernelGGL(zkc_ptau_acc<G>, dim3((P.nseg + 63) / 64), dim3(64), 0, ctx->stream, pts.as<uint32_t>(), npts, terms.as<uint32_t>(), seg.as<uint32_t>(), P.nseg, cur.as<XYZZ<F>>());
         ZKC_HIP_CHECK(ctx, hipGetLastError());
     }
-    for (const std::vector<uint32_t>& start : reduction_steps(P)) {
-        const uint32_t njobs = (uint32_t)start.size() - 1;
-        DevBuf st;
-        if ((rc = st.alloc(ctx, start.size() * 4)) || (rc = nxt.alloc(ctx, (size_t)njobs * sizeof(XYZZ<F>)))) return rc;
-        ZKC_HIP_CHECK(ctx, hipMemcpyAsync(st.p, start.data(), start.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (njobs) {
-            hipLaunchKernelGGL(zkc_ptau_red<G>, dim3((njobs + 63) / 64), dim3(64), 0, ctx->stream, cur.as<XYZZ<F>>(), st.as<uint32_t>(), njobs, nxt.as<XYZZ<F>>());
-            ZKC_HIP_CHECK(ctx, hipGetLastError());
-        }
-        ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));                                                  // `start` and `st` end with this turn of the loop
-        (void)hipFree(cur.p); cur.p = nxt.release();
-    }
+    if ((rc = point_reduce<F>(ctx, cur, row_counts(P)))) return rc;
     // cur: one sum per sorted row
     DevBuf aff;
     if ((rc = aff.alloc(ctx, (size_t)P.nrows * PT)) || (rc = fixed_affine<F>(ctx, cur.as<XYZZ<F>>(), P.nrows, aff.p, true))) return rc;

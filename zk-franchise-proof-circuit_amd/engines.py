@@ -58,6 +58,24 @@ def g2_lagrange(ctx, d_points_ptr, logn, d_out_ptr, mont=False):
     ctx._check(ctx._lib.zkc_g2_lagrange_dev(ctx._h, d_points_ptr, logn, 1 if mont else 0, d_out_ptr))
 
 
+def _wsum_pair(fn, width, ctx, d_points_ptr, n, d_weights16_ptr, mont):
+    lo, hi = ctypes.create_string_buffer(width), ctypes.create_string_buffer(width)
+    ctx._check(fn(ctx._h, d_points_ptr, n, 1 if mont else 0, d_weights16_ptr, lo, hi))
+    return lo.raw, hi.raw
+
+
+def g1_wsum_pair(ctx, d_points_ptr, n, d_weights16_ptr, mont=False):
+    """(sum_(i<n-1) w_i P_i, sum_(i<n-1) w_i P_(i+1)) for n >= 2 affine G1 points on the device (64 B, all zero = infinity) and n - 1 weights of 16 little-endian bytes
+    on the device: the pair of sums a powers-of-tau section is checked with (include/zkcensus_ptau_verify.h).  mont: the points' coordinates are in Montgomery form, as a
+    .ptau stores them.  Returns two 64-byte points in standard form (all zero = infinity).  A point off the curve raises (ZKC_ERR_FORMAT, the smallest index in the text)."""
+    return _wsum_pair(ctx._lib.zkc_g1_wsum_pair_dev, 64, ctx, d_points_ptr, n, d_weights16_ptr, mont)
+
+
+def g2_wsum_pair(ctx, d_points_ptr, n, d_weights16_ptr, mont=False):
+    """The same in G2: points 128 B (x.c0 | x.c1 | y.c0 | y.c1), anywhere on the twist."""
+    return _wsum_pair(ctx._lib.zkc_g2_wsum_pair_dev, 128, ctx, d_points_ptr, n, d_weights16_ptr, mont)
+
+
 def fixed_mul_window():
     """The window width w of the fixed-base tables (256 / w windows of 2^w - 1 rows)."""
     from . import _native

@@ -1,7 +1,8 @@
 """Key generation.  Test-only keys: r1cs.build() -> .r1cs -> zkc_setup_from_r1cs[_dev] -> .zkey + verification_key.json, the stand-in for `make compile`
 (circuit/circuit-compiler.sh:80-136) whose outputs are missing blobs; their toxic waste comes from a seed.  Keys nobody holds the waste of: from_ptau(), `snarkjs
 groth16 setup` from a public prepared powers-of-tau file (include/zkcensus_ptau.h), to be followed by phase2.contribute; prepare_ptau() and check_prepared() are
-`snarkjs powersoftau prepare phase2` and the check of a prepared file against its own monomial sections (include/zkcensus_ptau_prepare.h)."""
+`snarkjs powersoftau prepare phase2` and the check of a prepared file against its own monomial sections (include/zkcensus_ptau_prepare.h); verify_ptau() checks that
+the monomial sections themselves are the powers of one tau, the point checks of `snarkjs powersoftau verify` (include/zkcensus_ptau_verify.h)."""
 import ctypes
 import hashlib
 import os
@@ -56,10 +57,16 @@ def ensure_test_artifacts(nLevels=160, seed=DEFAULT_SEED, directory=None, force=
     return r, z, v
 
 
-def from_ptau(r1cs_path, ptau_path, zkey_path, vkey=None, ctx=None):
+def from_ptau(r1cs_path, ptau_path, zkey_path, vkey=None, ctx=None, verify=False):
     """`snarkjs groth16 setup r1cs ptau zkey`: the initial key (gamma = delta = 1, no contributions) of the circuit from a PREPARED powers-of-tau file, and unless `vkey`
     is None its verification_key.json.  With a Context the sums over the file's points run on its GPU, without one on host threads; the bytes are the same.  Raises
-    ZkcError with the refusal's text for a file that does not parse, does not fit the circuit, holds a point off its curve or fails a sanity check; nothing is written then."""
+    ZkcError with the refusal's text for a file that does not parse, does not fit the circuit, holds a point off its curve or fails a sanity check; nothing is written then.
+    verify=True: the whole file is checked first -- verify_ptau (its monomial sections are the powers of one tau), then check_prepared (its Lagrange sections are their
+    transforms) -- and a file that fails either raises ZkcError (ZKC_ERR_FORMAT) with that check's reason.  The key's bytes do not depend on `verify`."""
+    if verify:
+        for res in (verify_ptau(ptau_path, ctx=ctx), check_prepared(ptau_path, ctx=ctx)):
+            if not res[0]:
+                raise _native.ZkcError(5, res[-1])
     err = ctypes.create_string_buffer(512)
     lib = _native.load() if ctx is None else ctx._lib
     rc = lib.zkc_setup_from_ptau(None if ctx is None else ctx._h, os.fsencode(r1cs_path), os.fsencode(ptau_path), os.fsencode(zkey_path),
@@ -98,6 +105,44 @@ def check_prepared(ptau, ctx=None):
     if rc < 0:
         raise _native.ZkcError(-rc, err.value.decode())
     return rc == 1, sec.value, idx.value, err.value.decode()
+
+
+PTAU_CHECKS = ('', 'POINT', 'G2_SUBGROUP', 'GENERATORS', 'TAU_G1_G2', 'TAU_G1', 'TAU_G2', 'ALPHA_TAU_G1', 'BETA_TAU_G1', 'BETA_G1_G2')      # ZKC_PTAU_CHECK_*, by id
+
+
+def verify_ptau(ptau, ctx=None, seed=None):
+    """Are sections 2 .. 6 of a powers-of-tau file (prepared or not) tau^i G1, tau^i G2, alpha tau^i G1, beta tau^i G1 and beta G2 for ONE tau, alpha and beta?  The point
+    checks of `snarkjs powersoftau verify` (include/zkcensus_ptau_verify.h says which, and in what order); with check_prepared on top, all of it but the contribution
+    transcript.  -> (ok, check, section, index, reason): the first failing check as its ZKC_PTAU_CHECK_* id (0 when ok; PTAU_CHECKS[id] is its name), and the point to blame where there is one.
+    With a Context the weighted sums run on its GPU, without one on host threads; verdict and sums are the same.  seed: 32 bytes make the weights reproducible (tests);
+    None draws them from the OS, which is what a verifier wants.  Raises ZkcError for a file that does not parse."""
+    err = ctypes.create_string_buffer(512)
+    chk, sec, idx = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_ptau_verify(None if ctx is None else ctx._h, os.fsencode(ptau), None if seed is None else bytes(seed), ctypes.byref(chk), ctypes.byref(sec), ctypes.byref(idx), err, 512)
+    if rc < 0:
+        raise _native.ZkcError(-rc, err.value.decode())
+    return rc == 1, chk.value, sec.value, idx.value, err.value.decode()
+
+
+def debug_verify_ptau(ptau, weights16, ctx=None, chunk_terms=0):
+    """Test hook (zkc_debug_ptau_verify): verify_ptau with the caller's weights (2N - 2 of 16 little-endian bytes) and chunk size (0: the default).
+    -> (verify_ptau's tuple, the eight sums R1 R2 | S1 S2 | A pair | B pair as 640 bytes in standard form, all zero where a sum is infinity or was not reached)."""
+    err = ctypes.create_string_buffer(512); sums = ctypes.create_string_buffer(640)
+    chk, sec, idx = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    lib = _native.load() if ctx is None else ctx._lib
+    w = bytes(weights16)
+    rc = lib.zkc_debug_ptau_verify(None if ctx is None else ctx._h, os.fsencode(ptau), w, len(w) // 16, chunk_terms, sums, ctypes.byref(chk), ctypes.byref(sec), ctypes.byref(idx), err, 512)
+    if rc < 0:
+        raise _native.ZkcError(-rc, err.value.decode())
+    return (rc == 1, chk.value, sec.value, idx.value, err.value.decode()), sums.raw
+
+
+def ptau_verify_stats():
+    """Milliseconds of the calling thread's last verify_ptau, by stage."""
+    ms = (ctypes.c_double * 6)()
+    _native.load().zkc_ptau_verify_stats(ms)
+    return dict(zip(['read', 'upload_check', 'g2_membership', 'sums_g1', 'sums_g2', 'pairings'], list(ms)))
 
 
 def ptau_prepare_stats():
