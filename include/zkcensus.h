@@ -93,6 +93,7 @@ int zkc_witness_dev(zkc_ctx* ctx, int nLevels, const void* d_inputs, int B, void
  * circuit/circuit-compiler.sh:112-131), builds the CSR of section 4 and uploads + pre-shifts the MSM bases. ---- */
 int  zkc_zkey_load(zkc_ctx* ctx, const void* zkey_bytes, size_t len, zkc_zkey** out);
 void zkc_zkey_free(zkc_zkey* zk);
+int  zkc_zkey_call_streams(const zkc_zkey* zk, int* streams);               /* distinct HIP streams the key's latest batch call was enqueued on: a census key's call of several passes runs each pass on its lane's one stream (4 lanes + the witness stream = 5; ZKC_LANE_STREAMS) */
 int  zkc_zkey_info(const zkc_zkey* zk, uint32_t* nVars, uint32_t* nPublic, uint32_t* domainSize);
 int  zkc_zkey_pass_info(const zkc_zkey* zk, int* pass_size, int* lanes);      /* proofs per pipeline pass (a batch call of B voters is cut into ceil(B / pass_size) equal passes) and pipeline lanes the passes rotate over */
 int  zkc_zkey_header_info(const void* zkey_bytes, size_t len, uint32_t* nVars, uint32_t* nPublic, uint32_t* domainSize);   /* from the file image alone: host only, nothing is loaded */

@@ -85,6 +85,12 @@ class ProvingKey:
         self._lib.zkc_zkey_pass_info(h, ctypes.byref(ps), ctypes.byref(ln))
         self.pass_size, self.lanes = ps.value, ln.value          # a batch call of B voters runs as ceil(B / pass_size) equal passes over `lanes` pipeline lanes
 
+    def call_streams(self):
+        """Distinct HIP streams the latest batch call of this key was enqueued on (zkc_zkey_call_streams): the stream plan it took."""
+        n = ctypes.c_int()
+        self.ctx._check(self._lib.zkc_zkey_call_streams(self._h, ctypes.byref(n)))
+        return n.value
+
     def close(self):
         if getattr(self, '_h', None):
             if getattr(self.ctx, '_h', None):          # the context frees its keys when it closes first

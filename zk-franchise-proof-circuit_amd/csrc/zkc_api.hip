@@ -139,6 +139,9 @@ static void conv_consts(std::vector<Fr>& out, const unsigned long long (&src)[N]
 // stream waits; on four queues the batch path lost 5 % (3104 -> 3267 proofs/s with 8, same box) and the proving service's lanes ran one after another instead of side by
 // side (profiles/r05_service_hw_queues.txt).  The library does not set the variable: the queue count is the host's choice, and hosts that share a GPU
 // with other processes keep it low.
+// ... so the batch path asks for few queues instead: a call whose passes rotate over the lanes runs every stage of a pass on the lane's ONE stream (plan::lane_roles,
+// zkc_pass_plan.h) -- five busy streams with two waits per pass between them instead of thirteen with nine.  On four queues that is +3.7 % over the three-stream lanes
+// (profiles/lane_streams_ab.json; ZKC_LANE_STREAMS=3 is the old plan).  The proving service's lanes (lane named by the caller) keep their plan.
 
 extern "C" int zkc_ctx_create(int device, zkc_ctx** out) {
     if (!out) return zkc_fail(nullptr, ZKC_ERR_BAD_ARG, "out == NULL");

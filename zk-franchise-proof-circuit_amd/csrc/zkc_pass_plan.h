@@ -78,6 +78,7 @@ struct Switches {
     uint32_t vw_big = 0, vw_small = 0, vw_g2 = 0; size_t deep_wires = 16000;                         // ZKC_VW_BIG, ZKC_VW_SMALL, ZKC_VW_G2, ZKC_DEEP_WIRES
     bool matvec_inline = false, g2_acc_hold = false, g2_acc_early = false, reduce_stream = false;   // ZKC_MATVEC_INLINE, ZKC_G2_ACC_HOLD, ZKC_G2_ACC_EARLY, ZKC_REDUCE_STREAM
     bool serial_streams = false;                                                                    // ZKC_SERIAL_STREAMS, as the key was loaded
+    int lane_streams = 0;                                                                           // ZKC_LANE_STREAMS, as the key was loaded (lane_roles)
 };
 struct PassShape {
     uint32_t vws, vwb, vw_g2;                        // buckets per reduction wave: witness sections, H, the G2 jobs
@@ -152,6 +153,8 @@ inline StreamOrder stream_order(int nb, bool one_lane, int pass, int npasses, in
     // not held (round 3), and the twelve-proof passes of a 2^20-domain key run 140 proofs/s held against 136 early (their bucketing phase is 9 ms long: room for the G2 accumulation).
     // [r5] ... and with the passes of a call rotating over four lanes the hold is right again for full passes: the G2 accumulation of lane k then lands beside lane k's own
     // bucketing instead of beside another lane's transforms (alternating on one box: 3380 / 3386 proofs/s held, 3363 / 3363 started with the pass: +0.6 %)
+    // ... which is what a rotating call gets without an event now that its G2 MSM is enqueued on the lane's st behind the transforms (lane_roles): there the flag is read only
+    // under ZKC_LANE_STREAMS=2 / 3, where the G2 side has its own stream again
     o.g2_acc_with_sort = s.g2_acc_hold || ((nb < 32 || !one_lane) && !s.g2_acc_early);
     // (measured, alternating on one box: 3102 / 3089 / 3083 proofs/s with the reduction on its own stream, 3074 / 3087 / 3097 without -- nothing: the pass is bound by the
     // sum of its kernels' VALU work, and where the reduction's waves run does not change that sum.  Off unless ZKC_REDUCE_STREAM=1.)
@@ -162,6 +165,38 @@ inline StreamOrder stream_order(int nb, bool one_lane, int pass, int npasses, in
     // call follows it, so a stream of its own buys nothing and costs a hardware queue (a service of four lanes keeps 8 streams busy instead of 12)
     o.blind_on_st = (tree || lane0 >= 0) && npasses == 1;
     return o;
+}
+
+// ---- which of a lane's roles share a stream in this pass ----
+// A lane has up to four streams (zkc_lane): st, st2, fin, red.  Each role of a pass names the one that carries it; two roles with the same answer need no event between them,
+// and prove_batch_begin enqueues none.
+enum LaneStream { ON_ST = 0, ON_ST2 = 1, ON_FIN = 2, ON_RED = 3 };
+struct LaneRoles {
+    int g1;                    // buildABC, transforms, G1 MSM: always ON_ST
+    int g2;                    // G2 MSM (and piB of a small pass)
+    int blind;                 // blinding and the copy of the proofs
+    int red;                   // G1 bucket reduction
+    int streams;               // how many streams of the lane the pass touches
+};
+// lanes: how many lanes the passes of this call rotate over (1: the call stays on one lane -- a key with one lane, a call of one pass, a lane named by the caller).
+// The second and third stream of a lane overlap a pass with ITSELF: the G2 side beside the G1 side, the blinding beside the next pass.  That was the single-lane pipeline of
+// rounds 2-4 and it still is the plan of a call that stays on one lane, whatever the switch says.  A call whose passes rotate over several lanes finds the same overlap BETWEEN
+// lanes -- a lane works ~20 ms of the ~75 ms between two of its passes -- and every further stream is a further share of the process' hardware queues, every hop between two
+// streams of a lane a barrier packet that another lane's stream may have to queue behind (zkc_api.hip, "Hardware queues").  So such a call runs every stage of a pass on the
+// lane's st, in the order they are enqueued today: transforms, G2 MSM, G1 MSM, blinding, copy.  ZKC_LANE_STREAMS: 1 that plan, 2 the G2 side on st2 again, 3 the plan of
+// rounds 2-5 (st, st2, fin) for a host that gives the process a hardware queue per stream.  Measured on four queues: DESIGN.md section 3, "Lanes, hardware queues".
+// The reduction stream (ZKC_REDUCE_STREAM=1, stream_order) is an A/B switch of its own and stays one under every plan.
+inline LaneRoles lane_roles(int nb, bool one_lane, int pass, int npasses, int lane0, bool tree, int lanes, const Switches& s) {
+    const StreamOrder o = stream_order(nb, one_lane, pass, npasses, lane0, tree, s);
+    const bool rotates = !one_lane && lanes > 1;
+    const int want = !rotates ? 3 : (s.lane_streams >= 1 && s.lane_streams <= 3) ? s.lane_streams : 1;
+    LaneRoles r;
+    r.g1 = ON_ST;
+    r.g2 = want >= 2 ? ON_ST2 : ON_ST;
+    r.blind = (o.blind_on_st || want <= 2) ? ON_ST : ON_FIN;
+    r.red = o.red_split ? ON_RED : ON_ST;
+    r.streams = 1 + (r.g2 != ON_ST) + (r.blind != ON_ST) + (r.red != ON_ST);
+    return r;
 }
 
 }}  // namespace zkc::plan

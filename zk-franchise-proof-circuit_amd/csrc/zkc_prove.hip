@@ -113,6 +113,12 @@ static int lane_init(zkc_ctx* ctx, int l) {
 // stream, so that the per-category HIP-event brackets of zkc_profile_* are ISOLATED kernel times; the pipeline's overlap is gone, the proofs are the same bytes) -- ctx->stream
 struct LaneSt { hipStream_t st, st2, fin, red; };
 static LaneSt lane_st(const zkc_zkey* zk, const zkc_lane& L) { hipStream_t c = zk->ctx->stream; return zk->serial_streams ? LaneSt{c, c, c, c} : LaneSt{L.st, L.st2, L.fin, L.red}; }
+// ... and which of them carries each role of ONE pass (plan::lane_roles answers by name; the logic is there): G1 side, G2 side, blinding and copy, bucket reduction
+struct PassSt { hipStream_t st, st2, bl, red; };
+static PassSt pass_st(const LaneSt& s, const plan::LaneRoles& r) { const hipStream_t by[4] = {s.st, s.st2, s.fin, s.red}; return PassSt{by[r.g1], by[r.g2], by[r.blind], by[r.red] ? by[r.red] : by[r.g1]}; }
+// stream `s` waits for event `e`, last recorded on stream `on` -- unless that is `s` itself (the stream's own order already says so) or nothing recorded it yet: no barrier
+// packet for a wait that cannot hold anything back
+static hipError_t wait_unless_same(hipStream_t s, hipEvent_t e, hipStream_t on) { return (!on || on == s) ? hipSuccess : hipStreamWaitEvent(s, e, 0); }
 // Grows lane l of the key's context until it holds `inflight` proofs of this key per pass (grow only, never below what another key of the context asked for).  The caller holds
 // the context lock.  Footprint per proof in flight at nLevels = 160: abc + NTT scratch 2 x 12 MiB, p 4 MiB, MSM entries 59 MB, bucket / segment arrays and partial sums ~60 MB.
 static int lane_ensure(zkc_zkey* zk, int l, int inflight) {
@@ -304,8 +310,13 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     // a hardware queue of its own (GPU_MAX_HW_QUEUES, zkc_api.hip) and the lanes made only when a call reaches them, the overlap that rounds 1-4 could not find is there:
     // alternating on one box, (1 lane, 96) 3243 / 3235 proofs/s, (4, 96) 3291, (4, 64) 3314 / 3308 (+2.2 %), (4, 48) 3251, (3, 64) 3179, (2, 96) 3146 / 3155.  A lone proof
     // still touches lane 0 only (0.6 GB); a 1 024-voter call all four (37 GB; ZKC_LANES=1 ZKC_INFLIGHT=96: 14 GB and the old shape).
+    // ... that was with 24 hardware queues.  On the runtime's four -- what the library gets now that it leaves the count alone -- the three streams per lane cost more than
+    // their overlap brought: (4 lanes, 3 streams, 64) ran BEHIND (1 lane, 96).  A rotating call now keeps each pass on its lane's one stream (plan::lane_roles,
+    // ZKC_LANE_STREAMS): alternating on one box at four queues, (4, 3, 64) 3398 / 3387, (4, 2, 64) 3399 / 3403, (1 lane, 96) 3438 / 3437, (4, 1, 64) 3504 / 3522 proofs/s
+    // (profiles/lane_streams_ab.json).
     { const auto e_l = sw::given<sw::ZKC_LANES>(); zk->nlanes = opt_lanes > 0 ? std::min(opt_lanes, (int)MAX_LANES) : e_l ? (int)*e_l : zk->nLevels >= 0 ? (int)MAX_LANES : 1; }
     zk->serial_streams = sw::on<sw::ZKC_SERIAL_STREAMS>();          // (lane_st)
+    zk->lane_streams = (int)sw::value<sw::ZKC_LANE_STREAMS>(0);     // (plan::lane_roles; 0: the plan's own default)
     // the lanes are the context's: lane 0 is made (or found) now with room for a lone caller, the others when a call first lands on them
     if ((rc = lanes_ensure(zk, 1, 0, 1))) return bail(rc);
     {   // fixed-base tables for the blinding step (delta1, alpha1, beta1 in G1; delta2 in G2)
@@ -338,6 +349,14 @@ int zkc::prove_reserve(zkc_zkey* zk, int inflight) {
 extern "C" int zkc_zkey_pass_info(const zkc_zkey* zk, int* pass_size, int* lanes) {
     if (!zk) return ZKC_ERR_BAD_ARG;
     if (pass_size) *pass_size = zk->max_inflight; if (lanes) *lanes = zk->nlanes;
+    return ZKC_OK;
+}
+// the stream plan the key's latest batch call took: the distinct streams its witness chunks and its passes were enqueued on.  A census key's call of several passes: its
+// lanes' G1 streams and the context's stream for the witness chunks (4 + 1); with ZKC_LANE_STREAMS=2 / 3 two / three streams per lane (8 + 1, 12 + 1)
+extern "C" int zkc_zkey_call_streams(const zkc_zkey* zk, int* streams) {
+    if (!zk || !streams) return ZKC_ERR_BAD_ARG;
+    ZKC_LOCK(zk->ctx);
+    *streams = zk->last_call_streams;
     return ZKC_OK;
 }
 extern "C" int zkc_zkey_info(const zkc_zkey* zk, uint32_t* nVars, uint32_t* nPublic, uint32_t* domainSize) {
@@ -532,14 +551,18 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
     const bool trace_host = sw::on<sw::ZKC_TRACE_HOST>();
     auto now_ms = [] { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; };
     const double t_begin = now_ms(); double tr[6] = {0};
-    int pass = 0, done_on_st_lane = -1;
+    int pass = 0;
+    hipStream_t done_on[MAX_LANES] = {};                           // per lane: the stream that carries the blinding and copies of the call's passes on it
+    hipStream_t touched[1 + 4 * MAX_LANES] = {st0}; int ntouched = 1;      // (zkc_zkey_call_streams)
+    auto touch = [&](hipStream_t s) { for (int i = 0; i < ntouched; i++) if (touched[i] == s) return; touched[ntouched++] = s; };
     const bool one_lane = lane0 >= 0 || zk->nlanes == 1;
+    const int lanes = lane0 >= 0 ? 1 : std::min(zk->nlanes, npasses);      // the lanes this call's passes rotate over
     // what the decisions of a pass (zkc_pass_plan.h) read of the key and of the switches
     const plan::KeyShape KS{zk->c_sec, zk->c_h, zk->c_deep, nv, np, n, zk->offA, zk->offB1, zk->offC, zk->offA_deep, zk->offB1_deep, zk->offC_deep, zk->d_g2_29_lone != nullptr, zk->d_fb4 != nullptr};
     plan::Switches SW;
     SW.vw_big = (uint32_t)sw::value<sw::ZKC_VW_BIG>(0); SW.vw_small = (uint32_t)sw::value<sw::ZKC_VW_SMALL>(0); SW.vw_g2 = (uint32_t)sw::value<sw::ZKC_VW_G2>(0);
     SW.deep_wires = (size_t)sw::value<sw::ZKC_DEEP_WIRES>(16000); SW.matvec_inline = sw::on<sw::ZKC_MATVEC_INLINE>(); SW.g2_acc_hold = sw::on<sw::ZKC_G2_ACC_HOLD>();
-    SW.g2_acc_early = sw::on<sw::ZKC_G2_ACC_EARLY>(); SW.reduce_stream = sw::on<sw::ZKC_REDUCE_STREAM>(); SW.serial_streams = zk->serial_streams;
+    SW.g2_acc_early = sw::on<sw::ZKC_G2_ACC_EARLY>(); SW.reduce_stream = sw::on<sw::ZKC_REDUCE_STREAM>(); SW.serial_streams = zk->serial_streams; SW.lane_streams = zk->lane_streams;
     std::vector<plan::TopSeed> seeds;
     for (int p0 = 0; p0 < B; p0 += per_pass, pass++) {
         const int nb = std::min(per_pass, B - p0);
@@ -549,8 +572,6 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         const bool early = CS.early_n > 0;
         if (!early) ZKC_HIP_CHECK(ctx, zkc_wait_event(CS.ev_chunk[pass]));              // host: this chunk's fold flags have arrived
         tr[1] = now_ms();
-        ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(LS.st, CS.ev_chunk[pass], 0)); ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(LS.st2, CS.ev_chunk[pass], 0));
-        hipStream_t st = LS.st, st2 = LS.st2, fin = LS.fin;
         const uint32_t* w0 = (const uint32_t*)d_wtns + (size_t)p0 * nv * 8;
         // constant folding is per proof: voter q keeps the census levels below its own leaf depth dcq[q] (sik: dsq[q]) in its MSMs; the levels
         // above are the template's and come back as a constant in the blinding kernel.  One foreign witness (n2bOld block differs) unfolds the pass.
@@ -574,11 +595,17 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
             for (int q = 0; q < nb; q++) vms[q] = nf;
         }
         const bool listed = fold || (nofold_lists && vms[0].d != nullptr);                      // the pass' jobs run over wire lists (vms) instead of whole sections
-        if (LN.npass >= 2) { ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_fin[slot], 0)); ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st2, LN.ev_fin[slot], 0)); }   // slot still read by the blinding two passes back?
-        LN.npass++;
         // windows, tables and job counts of the pass, and where its stages go (zkc_pass_plan.h)
         const plan::PassShape PS = plan::pass_shape(KS, nb, listed ? vms : (const zkc_zkey::Fold::VMap*)nullptr, plan::LaneCaps{LN.w1.max_entries, LN.w1.max_buckets, LN.w1.max_jobs, LN.w2.max_entries}, SW);
         const plan::StreamOrder SO = plan::stream_order(nb, one_lane, pass, npasses, lane0, PS.tree, SW);
+        // the streams of the pass by role.  Roles that share a stream are ordered by it: every wait below that would name the waiting stream's own event is left out
+        // (wait_unless_same), and an event that only such waits would read is not recorded
+        const PassSt PT = pass_st(LS, plan::lane_roles(nb, one_lane, pass, npasses, lane0, PS.tree, lanes, SW));
+        const hipStream_t st = PT.st, st2 = PT.st2, bl = PT.bl, fin = LS.fin;
+        touch(st); touch(st2); touch(bl); touch(PT.red);
+        ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, CS.ev_chunk[pass], 0)); if (st2 != st) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st2, CS.ev_chunk[pass], 0));
+        if (LN.npass >= 2) { ZKC_HIP_CHECK(ctx, wait_unless_same(st, LN.ev_fin[slot], LN.fin_on[slot])); if (st2 != st) ZKC_HIP_CHECK(ctx, wait_unless_same(st2, LN.ev_fin[slot], LN.fin_on[slot])); }   // slot still read by the blinding two passes back?
+        LN.npass++;
         const bool tree = PS.tree, mv_done = SO.mv_done;
         if (mv_done) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_mv, 0));
         // (tried for passes of a few proofs while their G2 side was the longer chain: G2 enqueued first and its accumulation not held for the transforms -- its 1024 fat waves
@@ -590,7 +617,7 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         zkc_zkey::Fold::AbcRows ar; const bool abc_fold = fold && !mv_done && !zk->fold.abc_cls.empty() && zk->fold.d_abc_tmpl != nullptr;
         if (abc_fold) { int Dc = 0, Ds = 0; for (int q = 0; q < nb; q++) { Dc = std::max(Dc, (int)dcq[q]); Ds = std::max(Ds, (int)dsq[q]); } if ((rc = abc_rows(zk, Dc, Ds, &ar))) return rc; }
         if ((rc = h_evals_dev(zk, LN, st, w0, nb, !mv_done, abc_fold ? &ar : nullptr))) return rc;
-        ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_ntt, st));
+        if (st2 != st || SO.mv_prefetch) ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_ntt, st));      // read by the G2 stream's held accumulation and by the buildABC prefetch
         tr[2] = now_ms();
         static thread_local MsmJobList j1, j2;     // 6 KB each: kept off the stack frame of a C-ABI entry point
         j1.clear(PS.vws, PS.vwb, MSM_MAX_VW_G1); j2.clear(PS.vw_g2, 1024, MSM_MAX_VW_PER_JOB);
@@ -623,27 +650,35 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         // until the G1 stream has finished its short kernels (they were seen to stall next to the G2 chain's low-occupancy kernels); the G2
         // kernels then starve behind the 13 ms G1 accumulation instead and spill into the next pass -- measured equal within noise.
         const bool g2_early = !sw::on<sw::ZKC_G2_LATE>();
-        // the G2 side of the pass on st2: its MSM (the accumulation held behind acc_after, if given), piB of a small pass right behind it
+        // the G2 side of the pass on st2: its MSM (the accumulation held behind acc_after, if given), piB of a small pass right behind it.  A rotating call's st2 is the
+        // lane's st (plan::lane_roles): the G2 MSM then simply follows the transforms there, and the blinding behind it needs no ev_msm2
+        // The lane's G2 work space (LN.w2) is ONE, and the G2 side moves between the lane's st and st2 with the plan: a rotating call's pass may be followed on this lane by
+        // a one-pass call's (the other call slot, or another key of the context), or the other way round.  Where the stream differs from the one that carried the lane's
+        // previous G2 side, it first waits for the event recorded behind that one (g2_done); on the same stream, every pass of a call and every steady state, nothing is enqueued
         auto g2_side = [&](hipEvent_t acc_after) -> int {
+            if (LN.g2_done) ZKC_HIP_CHECK(ctx, wait_unless_same(st2, LN.g2_done, LN.g2_on));
             if ((rc = msm_pass_g2(zk, LN.w2, j2, slot, false, st2, acc_after))) return rc;
             if (tree && (rc = finalize_tree_g2_launch(ctx, st2, fa, nb))) return rc;
-            ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm2, st2));
+            if (st2 != bl) ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm2, st2));
+            LN.g2_on = st2; LN.g2_done = st2 != bl ? LN.ev_msm2 : LN.ev_fin[slot];      // (st2 == bl: the blinding follows on this stream and ev_fin[slot] is recorded behind it, below)
             return ZKC_OK;
         };
-        if (g2_early && (rc = g2_side(SO.g2_acc_with_sort ? LN.ev_ntt : nullptr))) return rc;
+        if (g2_early && (rc = g2_side(SO.g2_acc_with_sort && st2 != st ? LN.ev_ntt : nullptr))) return rc;
         tr[3] = now_ms();
         // [r4] the work space of the G1 pass (segment lists, partial sums, job and window lists) is the previous pass' until its bucket reduction is through -- which, for a
         // full pass, runs on the lane's reduction stream beside THIS pass' buildABC and transforms (a no-op wait when the reduction ran on this stream)
-        ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_red, 0));
-        if ((rc = msm_pass_g1(zk, LN.w1, j1, slot, false, st, LN.ev_sorted, LN.ev_acc, (SO.red_split && LS.red) ? LS.red : nullptr, LN.ev_red))) return rc;
+        ZKC_HIP_CHECK(ctx, wait_unless_same(st, LN.ev_red, LN.red_on));
+        const bool want_sorted = SO.mv_prefetch || (!g2_early && st2 != st);           // ev_sorted has a reader: the buildABC prefetch, or a late G2 side on a stream of its own
+        if ((rc = msm_pass_g1(zk, LN.w1, j1, slot, false, st, want_sorted ? LN.ev_sorted : nullptr, PT.red != st ? LN.ev_acc : nullptr, PT.red != st ? PT.red : nullptr, LN.ev_red))) return rc;
+        LN.red_on = PT.red;
         tr[4] = now_ms();
         if (!g2_early) {
-            ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st2, LN.ev_sorted, 0));
+            if (st2 != st) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st2, LN.ev_sorted, 0));
             if ((rc = g2_side(nullptr))) return rc;
         }
         if (want_publics)       // wires 1..nPublic of every witness, one strided copy
             ZKC_HIP_CHECK(ctx, hipMemcpy2DAsync(h_pub + 32ull * np * p0, 32ull * np, w0 + 8, 32ull * nv, 32ull * np, nb, hipMemcpyDeviceToHost, st));
-        ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm, st));
+        if (bl != st) ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_msm, st));
         if (SO.mv_prefetch && p0 + per_pass < B) {                                  // buildABC of the next pass, beside this pass' accumulation
             const int p1 = p0 + per_pass, nb1 = std::min(per_pass, B - p1);
             ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, sw::on<sw::ZKC_MV_PREFETCH_AT_NTT>() ? LN.ev_ntt : LN.ev_sorted, 0));         // this pass' NTT and joinABC are through (d_abc is free), its accumulation is next (waiting on ev_ntt instead, i.e. starting beside the bucketing, is 1 % slower: 3113 / 3093 against 3143 / 3137 proofs/s on one box)
@@ -651,27 +686,31 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
             if ((rc = h_matvec_dev(zk, LN, (const uint32_t*)d_wtns + (size_t)p1 * nv * 8, nb1, fin))) return rc;
             ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_mv, fin));
         }
-        // a7 on the second stream: overlaps the next pass (a one-pass call that is small or stays on its lane: on the G1 stream itself, plan::stream_order)
-        hipStream_t bl = SO.blind_on_st ? st : fin;
-        if (bl == fin) { ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, LN.ev_msm, 0)); ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(fin, LN.ev_red, 0)); }      // ev_msm: the G1 stream up to the copy of the public signals; ev_red: the G1 results
+        // a7 on the blinding stream: overlaps the next pass (a one-pass call that is small or stays on its lane, and every pass of a rotating call: on the G1 stream
+        // itself, plan::stream_order and plan::lane_roles)
+        if (bl != st) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm, 0));      // ev_msm: the G1 stream up to the copy of the public signals
+        ZKC_HIP_CHECK(ctx, wait_unless_same(bl, LN.ev_red, LN.red_on));               // ev_red: the G1 results
         // [r4] ... but the blinding scratch (LN.d_fin) is the lane's, and the pass before this one -- the last pass of the PREVIOUS call, begun on the other call slot -- blinds on
         // `fin`: without this wait its lane-per-product kernels and this call's tree kernels could write the scratch at the same time (a wrong proof for one of the two callers,
         // seen once in tests/test_gpu_service.py::test_queue_spills_over_further_device_entries under a load of mixed batch sizes).  That pass' blinding is long over when
         // this call's MSMs are through, so the wait costs nothing.
-        else { if (LN.npass >= 2) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_fin[slot ^ 1], 0)); if (SO.red_split) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(st, LN.ev_red, 0)); }
-        if (!tree) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm2, 0));      // a small pass' piB is written on the G2 stream: piA and piC need not wait for it ...
+        // (the wait is left out where that blinding ran on this pass' own blinding stream: every pass of a rotating call after the lane's first)
+        if (LN.npass >= 2) ZKC_HIP_CHECK(ctx, wait_unless_same(bl, LN.ev_fin[slot ^ 1], LN.fin_on[slot ^ 1]));
+        if (!tree && st2 != bl) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm2, 0));      // a small pass' piB is written on the G2 stream: piA and piC need not wait for it ...
         if ((rc = finalize_launch(ctx, bl, fa, nb))) return rc;
-        if (tree) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm2, 0));        // ... only the copy of the finished proof does
+        if (tree && st2 != bl) ZKC_HIP_CHECK(ctx, hipStreamWaitEvent(bl, LN.ev_msm2, 0));        // ... only the copy of the finished proof does
         if (tree) { ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_xyzz + 512ull * p0, CS.d_xyzz + 512 * (size_t)p0, 512ull * nb, hipMemcpyDeviceToHost, bl)); for (int q = 0; q < nb; q++) CS.as_xyzz[p0 + q] = 1; }
         else ZKC_HIP_CHECK(ctx, hipMemcpyAsync(CS.h_out + 256ull * p0, CS.d_proofs + 256 * (size_t)p0, 256ull * nb, hipMemcpyDeviceToHost, bl));
-        ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_fin[slot], bl));
-        if (bl == st) done_on_st_lane = li;
+        ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_fin[slot], bl)); LN.fin_on[slot] = bl;
+        done_on[li] = bl;
         tr[5] = now_ms();
         if (trace_host) fprintf(stderr, "[zkc host] pass %2d: start %8.2f | chunk wait %6.2f | h_evals %6.2f | g2 pass %6.2f | g1 pass %6.2f | blinding %6.2f ms\n", pass, tr[0] - t_begin,
                                 tr[1] - tr[0], tr[2] - tr[1], tr[3] - tr[2], tr[4] - tr[3], tr[5] - tr[4]);
     }
-    // every lane's blinding stream already waits for its G1 and G2 streams (ev_msm, ev_msm2) and carries the last copies: one event per lane closes the call
-    for (int l = 0; l < zk->nlanes; l++) if (CS.lanes_used >> l & 1) { const LaneSt ls = lane_st(zk, ctx->lanes[l]); ZKC_HIP_CHECK(ctx, hipEventRecord(CS.ev_done[l], done_on_st_lane == l ? ls.st : ls.fin)); }      // only the lanes this call ran on: another lane's streams carry another call
+    // every lane's blinding stream (done_on: the lane's fin, or its st where the plan put the blinding there) already waits for its G1 and G2 streams (ev_msm, ev_msm2) or
+    // is that stream, and carries the last copies: one event per lane closes the call
+    for (int l = 0; l < zk->nlanes; l++) if (CS.lanes_used >> l & 1) ZKC_HIP_CHECK(ctx, hipEventRecord(CS.ev_done[l], done_on[l]));      // only the lanes this call ran on: another lane's streams carry another call
+    zk->last_call_streams = ntouched;
     CS.B = B; CS.pending = true;
     return ZKC_OK;
 }

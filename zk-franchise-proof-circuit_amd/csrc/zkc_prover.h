@@ -191,6 +191,8 @@ struct zkc_lane {
     zkc::MsmWork w1, w2;                                                  // G1 and G2 pipelines
     size_t cap_abc = 0, cap_p = 0, cap_fin = 0, cap_bs = 0, bytes = 0; bool made = false;      // capacities (elements of d_abc / d_t, words of d_p, bytes of d_fin, words of d_bs), HBM held (hipMemGetInfo delta), events and streams created
     hipEvent_t ev_msm = nullptr, ev_msm2 = nullptr, ev_sorted = nullptr, ev_ntt = nullptr, ev_mv = nullptr, ev_acc = nullptr, ev_fin[2] = {nullptr, nullptr}; int npass = 0;      // ev_acc: the G1 accumulation of the lane's latest pass is through      // ev_ntt: buildABC/NTT/joinABC of the pass are through      // ev_fin[slot]: blinding of the pass that used result slot `slot`
+    hipStream_t g2_on = nullptr; hipEvent_t g2_done = nullptr;           // the stream that carried the G2 side of the lane's latest pass, and the event recorded behind it there (ev_msm2, or that pass' ev_fin where the blinding followed on the same stream): the G2 work space w2 is that pass' until it fires
+    hipStream_t fin_on[2] = {nullptr, nullptr}, red_on = nullptr;         // the stream ev_fin[slot] / ev_red was last recorded on (nullptr: never): a pass that runs on that very stream enqueues no wait for it (plan::lane_roles)
 };
 
 struct zkc_zkey {
@@ -222,6 +224,8 @@ struct zkc_zkey {
     size_t bytes_tables = 0;                                                // HBM held by the key's constant tables (hipMemGetInfo delta around the load; the lanes' work space is the context's)
     uint8_t fingerprint[32] = {0};                                          // parse::zkey_fingerprint of the image: the per-call identity of the resident-key caches
     int nlanes = 1; bool serial_streams = false;          // lanes of the context this key's passes may use (zkc_ctx::lanes); serial_streams: every stage on ctx->stream instead of the lane's streams (ZKC_SERIAL_STREAMS, measurement only)
+    int lane_streams = 0;                                 // ZKC_LANE_STREAMS at key load (0: not given): which of a lane's streams a pass of a rotating call uses (plan::lane_roles)
+    int last_call_streams = 0;                            // distinct streams the latest batch call's witness chunks and passes were enqueued on (zkc_zkey_call_streams)
     zkc::G1Affine *d_tblDelta1 = nullptr, *d_tblAlpha1 = nullptr, *d_tblBeta1 = nullptr; zkc::G2Affine* d_tblDelta2 = nullptr;
     uint32_t *d_depths = nullptr, *h_depths = nullptr; size_t depths_cap = 0;                     // zkc_input_depths: device [2 B], pinned [2 B] (read back inside begin, under the context lock)
     zkc::G1XYZZ* d_fb4 = nullptr; zkc::G2XYZZ* d_fb4g2 = nullptr; int fb4_bases = 0;   // 4-bit fixed-base tables of the small-pass blinding (FinalizeArgs::fb4)

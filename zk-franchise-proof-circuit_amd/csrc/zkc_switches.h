@@ -34,6 +34,7 @@ constexpr long long ANY = LLONG_MIN;      // no bound on this side of a clamp
     X(ZKC_DEVICE,               TEXT,        ANY, ANY,   LIVE,    "service creation: the GPUs of the default proving service: \"2\", \"0,1,2,3\", \"all\"; unset: every visible device") \
     X(ZKC_INFLIGHT,             NUMBER,      1,   128,   LIVE,    "key load: proofs per pipeline pass (census key 64, any other 96, fewer for a large circuit); at most MSM_MAX_JOBS / 4") \
     X(ZKC_LANES,                NUMBER,      1,   4,     LIVE,    "key load: pipeline lanes the passes of a batch call rotate over (census key MAX_LANES = 4, any other 1)")      \
+    X(ZKC_LANE_STREAMS,         NUMBER,      1,   3,     LIVE,    "key load: streams of a lane that a pass of a call rotating over several lanes uses: 1 all on the G1 stream (default), 2 the G2 MSM on its own, 3 the blinding too") \
     X(ZKC_DEEP_TABLES,          NUMBER,      ANY, ANY,   LIVE,    "key load: 0 leaves out the second section tables that passes of deep voters take, 2 builds them for a census key of any size (default 1)") \
     X(ZKC_G2_LONE_TABLE,        OFF_IF_ZERO, ANY, ANY,   LIVE,    "key load: =0 skips the 8-bit-window G2 table of the lone-proof path")                                          \
     X(ZKC_BLIND_TREE,           OFF_IF_ZERO, ANY, ANY,   LIVE,    "key load: =0 gives a key whose passes of one or two proofs take the general blinding kernels")                 \
