@@ -298,6 +298,10 @@ void zkc_msm_g1_free(zkc_msm* m);
 int zkc_debug_stage(zkc_zkey* zk, const void* d_wtns, int stage, void* host_out);
 unsigned long long zkc_debug_early_retries(void);      /* calls of given witnesses that were laid out from their sibling wires, refused by the fold check and proved again from their fold flags (process-wide) */
 int zkc_msm_debug(zkc_zkey* zk, int which, const void* d_scalars, uint32_t count, void* host_out);
+/* zkc_debug_c_rows: what a pass that leaves out the transform pair of C reads of its (census) key.  what 0: the points -H'_j, j in [first, first + count), 64 B each in
+ *                  zkc_msm_debug's form (the tables are made if no pass has made them); what 1: the template's A_w | B_w | C_w in zkc_debug_stage 0's form; what 2: four
+ *                  uint64 -- vectors the key's passes sent through the transform pair, passes without C's pair, folded passes with it, 1 once the tables exist. */
+int zkc_debug_c_rows(zkc_zkey* zk, int what, uint32_t first, uint32_t count, void* host_out);
 int zkc_debug_pairing_dev(zkc_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint8_t* weights, int N, uint8_t product_out[384], uint8_t* folded_out,
                           int32_t* member_out, int* bad_out, const uint32_t* nodes, size_t count, uint8_t* node_out);
 

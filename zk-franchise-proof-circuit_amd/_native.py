@@ -50,6 +50,7 @@ def load():
     L.zkc_debug_stage.argtypes = [vp, vp, ctypes.c_int, ctypes.c_char_p]
     L.zkc_debug_early_retries.argtypes = []; L.zkc_debug_early_retries.restype = ctypes.c_ulonglong
     L.zkc_msm_debug.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint32, ctypes.c_char_p]
+    L.zkc_debug_c_rows.argtypes = [vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p]
     L.zkc_debug_pairing_dev.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, i32p, ctypes.POINTER(ctypes.c_int),
                                         ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_char_p]
     ulp = ctypes.POINTER(ctypes.c_ulong)

@@ -4,6 +4,8 @@
 #include "zkc_prover.h"
 #include "zkc_host_util.h"
 #include "zkc_kernels.h"
+#include "zkc_fixedbase_dev.h"
+#include "zkc_ecntt.h"
 #include <ctime>
 #include <cstdio>
 #include <algorithm>
@@ -325,14 +327,54 @@ int zkc::abc_rows(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::AbcRows* out) {
     zkc_zkey::Fold::AbcRows m; m.nrows = (uint32_t)v.rows.size(); m.nlong = v.nlong; m.offC = m.nrows; m.nC = (uint32_t)v.crows.size(); m.offW = m.offC + m.nC; m.nW = (uint32_t)v.wires.size();
     std::vector<uint32_t> all(v.rows); all.insert(all.end(), v.crows.begin(), v.crows.end()); all.insert(all.end(), v.wires.begin(), v.wires.end());
     if (int rc = list_upload(ctx, all, ctx->stream, &m.d)) return rc;
+    // [c rows] a key with the wide H table: the list an H job takes over these C rows when the pass leaves out C's transform pair
+    if (zk->h_rows == 2 * zk->n) { if (int rc = list_upload(ctx, plan::h_vmap(zk->n, v.crows.data(), m.nC), ctx->stream, &m.d_hv)) { (void)hipFree(m.d); return rc; } }
     if (sw::on<sw::ZKC_TRACE_HOST>()) fprintf(stderr, "[zkc host] abc rows at depths (%d, %d): %u of %zu A/B rows listed (%u long), %u C rows, %u wires\n", Dc, Ds, m.nrows, f.abc_cls.size(), m.nlong, m.nC, m.nW);
     f.abc_rows[{Dc, Ds}] = m; *out = m;
     return ZKC_OK;
 }
+// [c rows] what a pass that leaves out the transform pair of C needs of its key, once per key at the first such pass (DESIGN.md "Constant folding"):
+//   c_hat = pair(C_T)   the template's C through the very kernels a pass runs (ntt_pair_run), kept in Montgomery form: joinABC's third operand for every proof
+//   -H'                 H'_j = sum_i M_ij H_i with M = F diag(g^i / n) F~ the matrix of the pair, so that sum_i pair(dC)_i H_i = sum_j dC_j H'_j.  M's factors are symmetric:
+//                       H' = F~ diag F H over the key's H points.  With E = ecntt (inverse transform, natural order, 1 / n included): (F H)_k = n E(H)_(-k) and F~ S = n E(S), so
+//                       -H' = E(S), S_k = (-n g^k) E(H)_(-k mod n): two point transforms and one product per point in between (g1_scale_each), then window 0 of the second
+//                       half of the H table, pre-shifted for the H windows like the first half.
+// Synchronous on ctx->stream under the context lock the caller holds.  Passes in flight on the lanes read the first half of the H table only.
+int zkc::c_rows_prepare(zkc_zkey* zk) {
+    auto& f = zk->fold; zkc_ctx* ctx = zk->ctx;
+    if (f.c_rows_ready) return ZKC_OK;
+    const uint32_t n = zk->n, logn = zk->logn; int rc;
+    if (!f.d_abc_tmpl || zk->h_rows != 2 * n || logn < 12 || logn > 27) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "c_rows_prepare: the key has no template abc or no wide H table");
+    timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
+    DevBuf chat, t, s, xy, sc, wi;
+    if ((rc = chat.alloc(ctx, (size_t)n * sizeof(Fr)))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(chat.p, f.d_abc_tmpl + 2 * (size_t)n, (size_t)n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = ntt_pair_run(ctx, ctx->stream, chat.as<Fr>(), zk->d_tw_inv29, zk->d_tw_fwd29, zk->d_coset_br, (int)logn, 1))) return rc;
+    // scalar of point p = -k mod n is -n g^k; entry k of the product takes point and scalar (n - k) mod n
+    std::vector<uint32_t> h_sc(8 * (size_t)n), h_wi(n);
+    { const Fr g = fr_root_of_unity((int)logn + 1); Fr c = Fr::zero() - fp_from_u32<FrParams>(n);
+      for (uint32_t k = 0; k < n; k++) { const uint32_t p = (n - k) & (n - 1); fp_to_std<FrParams>(h_sc.data() + 8 * (size_t)p, c); h_wi[k] = p; c = c * g; } }
+    G1Affine* const H0 = zk->d_g1 + zk->offH;
+    if ((rc = t.alloc(ctx, (size_t)n * sizeof(G1Affine))) || (rc = s.alloc(ctx, (size_t)n * sizeof(G1Affine))) || (rc = xy.alloc(ctx, (size_t)n * sizeof(G1XYZZ))) ||
+        (rc = sc.alloc(ctx, h_sc.size() * 4)) || (rc = wi.alloc(ctx, h_wi.size() * 4))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(sc.p, h_sc.data(), h_sc.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(wi.p, h_wi.data(), h_wi.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ecntt<Fq>(ctx, H0, logn, zk->d_tw_inv, logn, t.p, true, nullptr))) return rc;                              // E(H); synchronises
+    if ((rc = g1_scale_each(ctx, t.as<G1Affine>(), sc.as<uint32_t>(), wi.as<uint32_t>(), n, xy.as<G1XYZZ>()))) return rc;
+    if ((rc = fixed_affine<Fq>(ctx, xy.as<G1XYZZ>(), n, s.p, true))) return rc;                                          // S; synchronises
+    if ((rc = ecntt<Fq>(ctx, s.p, logn, zk->d_tw_inv, logn, H0 + n, true, nullptr))) return rc;                          // -H' into window 0 of the second half
+    if ((rc = msm_precompute_g1(ctx, n, H0 + n, zk->c_h, 2 * (size_t)n))) return rc;
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    f.d_c_hat = (Fr*)chat.release(); f.c_rows_ready = true;
+    if (sw::on<sw::ZKC_TRACE_HOST>()) { timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1);
+        fprintf(stderr, "[zkc host] c rows: transformed template C and -H' (%u points, %d windows) in %.1f ms\n", n, msm_nw(zk->c_h), (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) * 1e-6); }
+    return ZKC_OK;
+}
 // everything above that lives as long as the key (zkc_zkey_free; d_fb4 / d_fb4g2 are in the key's own list there)
 void zkc::fold_free(zkc_zkey* zk) {
+    if (zk->fold.d_c_hat) (void)hipFree(zk->fold.d_c_hat);
     for (auto& kv : zk->fold.vmaps) if (kv.second.d) (void)hipFree(kv.second.d);
-    for (auto& kv : zk->fold.abc_rows) if (kv.second.d) (void)hipFree(kv.second.d);
+    for (auto& kv : zk->fold.abc_rows) { if (kv.second.d) (void)hipFree(kv.second.d); if (kv.second.d_hv) (void)hipFree(kv.second.d_hv); }
     if (zk->fold.d_abc_tmpl) (void)hipFree(zk->fold.d_abc_tmpl);
     { auto& tp = zk->fold.top; for (void* q : {(void*)tp.d_copy[0], (void*)tp.d_copy[1], (void*)tp.d_valid, (void*)tp.d_A, (void*)tp.d_B1, (void*)tp.d_C, (void*)tp.d_B2}) if (q) (void)hipFree(q); }
     for (void* q : {(void*)zk->fold.d_foldA, (void*)zk->fold.d_foldB1, (void*)zk->fold.d_foldC, (void*)zk->fold.d_foldB2}) if (q) (void)hipFree(q);

@@ -30,11 +30,13 @@ __device__ __forceinline__ Fr mv_term(const Fr* __restrict__ val, const Fr* __re
 // ---- zkc_ntt.hip (launched from zkc_prove.hip) ----
 extern "C" __global__ void zkc_wtns_mont(const Fr* wtns_std, size_t wtns_stride, Fr* wm, size_t wm_stride, uint32_t nv);
 extern "C" __global__ void zkc_wtns_mont_list(const Fr* wtns_std, size_t wtns_stride, Fr* wm, size_t wm_stride, const uint32_t* list, uint32_t nlist);
-extern "C" __global__ void zkc_abc_fill(const uint4* tmpl, uint4* abc, uint32_t per);
+extern "C" __global__ void zkc_abc_fill(const uint4* tmpl, uint4* abc, uint32_t per, uint32_t stride);
 extern "C" __global__ void zkc_matvec_jds(const uint32_t* perm, const uint32_t* rowlen, const uint32_t* jdptr, const uint32_t* col, const Fr* val, const Fr* wtns_std,
                                           size_t wtns_stride, Fr* abc, int n, uint32_t nlong, const Fr* wm_all, size_t wm_stride, const uint32_t* list, uint32_t nrows);
 extern "C" __global__ void zkc_pointwise_mul(Fr* abc, int n, const uint32_t* list, uint32_t count);
 extern "C" __global__ void zkc_join_abc(const Fr* abc, uint32_t* p_std, int n);
+extern "C" __global__ void zkc_join_abc_ct(const Fr* abc, const Fr* c_hat, uint32_t* p_std, int n);
+extern "C" __global__ void zkc_c_rows_delta(const Fr* abc, const Fr* c_tmpl, uint32_t* p_std, int n, const uint32_t* list, uint32_t count);
 
 // ---- zkc_fold.hip: a call's witnesses against the template and the top-of-tree table, depths off the inputs (launched from zkc_prove.hip) ----
 struct TopCheckArgs;      // zkc_prover.h, which both files include

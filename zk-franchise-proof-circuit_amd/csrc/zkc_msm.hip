@@ -490,16 +490,17 @@ zkc_msm_shift_bases(const Affine<F>* __restrict__ prev, Affine<F>* __restrict__ 
     next[i] = xyzz_to_affine(p);
 }
 template <class F>
-static int precompute(zkc_ctx* ctx, uint32_t count, Affine<F>* d_table, int c) {
+static int precompute(zkc_ctx* ctx, uint32_t count, Affine<F>* d_table, int c, size_t stride = 0) {
+    if (!stride) stride = count;
     for (int w = 1; w < msm_nw(c); w++) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_msm_shift_bases<F>), dim3((count + 127) / 128), dim3(128), 0, ctx->stream,
-                           d_table + (size_t)(w - 1) * count, d_table + (size_t)w * count, count, c);
+                           d_table + (size_t)(w - 1) * stride, d_table + (size_t)w * stride, count, c);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("zkc_msm_shift_bases: ") + hipGetErrorString(e));
     }
     return ZKC_OK;
 }
-int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c) { return precompute<Fq>(ctx, count, d_table, c); }
+int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c, size_t window_stride) { return precompute<Fq>(ctx, count, d_table, c, window_stride); }
 int msm_precompute_g2(zkc_ctx* ctx, uint32_t count, G2Affine* d_table, int c) { return precompute<Fq2>(ctx, count, d_table, c); }
 int msm_g2_rows29(zkc_ctx* ctx, const G2Affine* d_points, size_t n, const char* what, uint32_t** out) {
     DevBuf rows; int rc;
@@ -577,6 +578,11 @@ static int fold_group_sums(zkc_ctx* ctx, const Affine<F>* tbl, const uint32_t* d
 }
 int fold_group_sums_g1(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, int32_t sh, const uint32_t* gs, uint32_t ng, G1XYZZ* o, uint32_t pt_mod, hipStream_t st) {
     return fold_group_sums<Fq>(ctx, tbl, s, w, nw, sh, gs, ng, o, pt_mod, st);
+}
+int g1_scale_each(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, G1XYZZ* d_out) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(zkc_fold_mul<Fq>), dim3((nw + 63) / 64), dim3(64), 0, ctx->stream, tbl, d_scalars, d_wires, nw, 0, d_out, 0u);
+    ZKC_HIP_CHECK(ctx, hipGetLastError());
+    return ZKC_OK;
 }
 // the batch verifier's form: scratch and sums in buffers of the caller's (the context's verifier work space), the sums left on the device for the Miller kernels and copied to h_out
 int fold_group_sums_g1_ws(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* s, const uint32_t* w, uint32_t nw, const uint32_t* gs, uint32_t ng, G1XYZZ* d_tmp, G1XYZZ* d_out, G1XYZZ* h_out) {
@@ -674,7 +680,8 @@ static int msm_pass(zkc_zkey* zk, MsmWork& w, const Affine<F>* table, const MsmJ
     uint64_t alg_bytes = 0; uint32_t maxcount = 0;
     uint64_t streamed_bytes = 0;
     for (int j = 0; j < nj; j++) {
-        alg_bytes += (uint64_t)jl.job[j].tbl_count * (sizeof(Affine<F>) + 32);     // the whole section, folded or not
+        // the whole section, folded or not ([c rows] a job without a list runs over a whole section: its count -- the first half of a wide H table)
+        alg_bytes += (uint64_t)(jl.job[j].vmap ? jl.job[j].tbl_count : std::min(jl.job[j].tbl_count, jl.job[j].count)) * (sizeof(Affine<F>) + 32);
         streamed_bytes += (uint64_t)jl.job[j].count * (sizeof(Affine<F>) + 32);     // (scalar, base) pairs that actually enter the MSM
         maxcount = std::max(maxcount, jl.job[j].count);
     }

@@ -53,8 +53,8 @@ zkc_wtns_mont_list(const Fr* __restrict__ wtns_std, size_t wtns_stride, Fr* __re
 }
 // [abc fold] every proof's [3][n] block := the key's template abc (per = uint4 per block); the listed rows are then computed over it
 extern "C" __global__ void __launch_bounds__(256)
-zkc_abc_fill(const uint4* __restrict__ tmpl, uint4* __restrict__ abc, uint32_t per) {
-    uint4* __restrict__ dst = abc + (size_t)blockIdx.y * per;
+zkc_abc_fill(const uint4* __restrict__ tmpl, uint4* __restrict__ abc, uint32_t per, uint32_t stride) {      // [c rows] per < stride: the A and B thirds only
+    uint4* __restrict__ dst = abc + (size_t)blockIdx.y * stride;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < per; i += gridDim.x * blockDim.x) dst[i] = tmpl[i];
 }
 // [abc fold] list != nullptr: the kernel walks the `nrows` sorted positions list[0 .. nrows) instead of all 2 n (ascending, so the first `nlong` of them are long rows and
@@ -99,12 +99,7 @@ zkc_pointwise_mul(Fr* __restrict__ abc, int n, const uint32_t* __restrict__ list
 // 32 x value (their R' form), (a b + (D - c) 2^261) / 2^261 is one fused product (zkc_f29.h), and a second reduction of the nine limbs alone
 // divides by R' once more, which is the way out of Montgomery form; 243 mads per element instead of two out-of-line products.
 struct JoinDom { static constexpr L9 D27 = f29_dominator<FrParams>(1u << 29, 1u << 27); };
-extern "C" __global__ void __launch_bounds__(256)
-zkc_join_abc(const Fr* __restrict__ abc, uint32_t* __restrict__ p_std, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fr* a = abc + (size_t)blockIdx.y * 3 * n;
-    const Fr av = ld_fr(a + i), bv = ld_fr(a + n + i), cv = ld_fr(a + 2 * (size_t)n + i);
+__device__ __forceinline__ void join_abc_one(const Fr av, const Fr bv, const Fr cv, uint32_t* __restrict__ out_std) {
     uint32_t A[9], B[9], C[9], T[9];
     f29_from_fp_shl5(A, av.v); f29_from_fp_shl5(B, bv.v); f29_from_fp_shl5(C, cv.v);
 #pragma unroll
@@ -118,8 +113,37 @@ zkc_join_abc(const Fr* __restrict__ abc, uint32_t* __restrict__ p_std, int n) {
     r.v[0] = f29_word<0>(T); r.v[1] = f29_word<32>(T); r.v[2] = f29_word<64>(T); r.v[3] = f29_word<96>(T);
     r.v[4] = f29_word<128>(T); r.v[5] = f29_word<160>(T); r.v[6] = f29_word<192>(T); r.v[7] = f29_word<224>(T);
     fp_reduce_once<FrParams>(r.v);
-    uint4* d = reinterpret_cast<uint4*>(p_std + 8 * ((size_t)blockIdx.y * n + i));
+    uint4* d = reinterpret_cast<uint4*>(out_std);
     d[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]); d[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+}
+extern "C" __global__ void __launch_bounds__(256)
+zkc_join_abc(const Fr* __restrict__ abc, uint32_t* __restrict__ p_std, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fr* a = abc + (size_t)blockIdx.y * 3 * n;
+    join_abc_one(ld_fr(a + i), ld_fr(a + n + i), ld_fr(a + 2 * (size_t)n + i), p_std + 8 * ((size_t)blockIdx.y * n + i));
+}
+// [c rows] the same with the key's transformed template C (c_hat, one vector for every proof of the pass) as the third operand; a proof's H scalars are 2 n apart: its second
+// half holds the differences zkc_c_rows_delta wrote
+extern "C" __global__ void __launch_bounds__(256)
+zkc_join_abc_ct(const Fr* __restrict__ abc, const Fr* __restrict__ c_hat, uint32_t* __restrict__ p_std, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fr* a = abc + (size_t)blockIdx.y * 3 * n;
+    join_abc_one(ld_fr(a + i), ld_fr(a + n + i), ld_fr(c_hat + i), p_std + 8 * ((size_t)blockIdx.y * 2 * n + i));
+}
+// [c rows] for the `count` constraints of `list`: a b - c_T on the domain (a, b: the proof's rows after buildABC, before the transforms; c_T: the template's C row), out of
+// Montgomery form, to entry n + i of the proof's H scalars.  Entries off the list are never read (plan::h_vmap)
+extern "C" __global__ void __launch_bounds__(256)
+zkc_c_rows_delta(const Fr* __restrict__ abc, const Fr* __restrict__ c_tmpl, uint32_t* __restrict__ p_std, int n, const uint32_t* __restrict__ list, uint32_t count) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const uint32_t i = list[e];
+    const Fr* a = abc + (size_t)blockIdx.y * 3 * n;
+    const Fr dv = ld_fr(a + i) * ld_fr(a + n + i) - ld_fr(c_tmpl + i);
+    uint32_t s[8]; fp_to_std<FrParams>(s, dv);
+    uint4* d = reinterpret_cast<uint4*>(p_std + 8 * ((size_t)blockIdx.y * 2 * n + n + i));
+    d[0] = make_uint4(s[0], s[1], s[2], s[3]); d[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
 
 // ---- one NTT pass: stages s0+1 .. s0+b of a DIT transform of size 2^logn ----
@@ -191,11 +215,14 @@ __device__ __forceinline__ void ntt_r4(uint32_t* p0, uint32_t* p1, uint32_t* p2,
 #pragma unroll
     for (int i = 0; i < 9; i++) { p0[i] = a[i]; p1[i] = b[i]; p2[i] = c[i]; p3[i] = d[i]; }
 }
+// [c rows] the vector a block works on: blockIdx.y of the batch, or -- ab_only, a pass that transforms the A and B thirds of its proofs' [3][n] blocks and leaves C alone
+// (ntt_pair_run) -- vector y + y / 2: 0, 1, 3, 4, 6, 7 ...  Wave-uniform, scalar arithmetic
+__device__ __forceinline__ size_t ntt_vec(int ab_only) { return ab_only ? (size_t)blockIdx.y + (blockIdx.y >> 1) : (size_t)blockIdx.y; }
 extern "C" __global__ void __launch_bounds__(256)
 zkc_ntt_pass(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, const Fr* __restrict__ scale,      // src_all == dst_all when ntt_pair_run calls it in place: no __restrict__ on the data pointers
-             int logn, int s0, int b, int first) {
-    const Fr* src = src_all + ((size_t)blockIdx.y << logn);      // blockIdx.y = vector of the batch
-    Fr* dst = dst_all + ((size_t)blockIdx.y << logn);
+             int logn, int s0, int b, int first, int ab_only) {
+    const Fr* src = src_all + (ntt_vec(ab_only) << logn);      // blockIdx.y = vector of the batch
+    Fr* dst = dst_all + (ntt_vec(ab_only) << logn);
     extern __shared__ uint32_t tile[];                                      // 9 words per element (odd stride: conflict-free)
     const int mid_n = 1 << b;
     const int lo_bits = s0;
@@ -319,12 +346,12 @@ __device__ __forceinline__ void ntt_nr_stages(uint32_t* tile, Slot slot, int b, 
     }
 }
 template <int RADIX>
-__device__ __forceinline__ void ntt_nr_head_body(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, int logn, int q0, int b) {      // src_all == dst_all: in place
+__device__ __forceinline__ void ntt_nr_head_body(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, int logn, int q0, int b, int ab_only) {      // src_all == dst_all: in place
     // NR stages q0 .. q0+b-1.  tile: mid = the b position bits below the top q0 (stride 2^sh, sh = logn-q0-b), lo_t = NTT_TILE >> b neighbouring positions starting
     // at lo0; the top q0 bits (`prefix`) are fixed per block.  q0 = 0: the first kernel of a transform (stage 0 is twiddle-free, operands as large as 32 p).
     // [r4] domains above 2^18 run two of these in a row (q0 = 0, then q0 = b of the first): the mid kernel always takes the last nine NR stages.
-    const Fr* src = src_all + ((size_t)blockIdx.y << logn);
-    Fr* dst = dst_all + ((size_t)blockIdx.y << logn);
+    const Fr* src = src_all + (ntt_vec(ab_only) << logn);
+    Fr* dst = dst_all + (ntt_vec(ab_only) << logn);
     extern __shared__ uint32_t tile[];
     const int mid_n = 1 << b, sh = logn - q0 - b, lo_t = NTT_TILE >> b, elems = mid_n * lo_t;
     const int bpp = (1 << sh) / lo_t;                                    // blocks per prefix
@@ -349,13 +376,13 @@ __device__ __forceinline__ void ntt_nr_head_body(const Fr* src_all, Fr* dst_all,
     }
 }
 extern "C" __global__ void __launch_bounds__(256)
-zkc_ntt_nr_head(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, int logn, int q0, int b) { ntt_nr_head_body<1>(src_all, dst_all, tw29, logn, q0, b); }
+zkc_ntt_nr_head(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, int logn, int q0, int b, int ab_only) { ntt_nr_head_body<1>(src_all, dst_all, tw29, logn, q0, b, ab_only); }
 extern "C" __global__ void __launch_bounds__(256)
-zkc_ntt_nr_head_r4(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, int logn, int q0, int b) { ntt_nr_head_body<4>(src_all, dst_all, tw29, logn, q0, b); }
+zkc_ntt_nr_head_r4(const Fr* src_all, Fr* dst_all, const uint32_t* __restrict__ tw29, int logn, int q0, int b, int ab_only) { ntt_nr_head_body<4>(src_all, dst_all, tw29, logn, q0, b, ab_only); }
 // NR stages logn-9 .. logn-1 of the inverse, the scale, RN stages 1 .. 9 of the forward transform: NTT_TILE consecutive positions = two blocks of 512
 extern "C" __global__ void __launch_bounds__(256)
-zkc_ntt_mid(Fr* __restrict__ data_all, const uint32_t* __restrict__ tw_inv29, const uint32_t* __restrict__ tw_fwd29, const Fr* __restrict__ scale_br, int logn) {
-    Fr* __restrict__ data = data_all + ((size_t)blockIdx.y << logn);
+zkc_ntt_mid(Fr* __restrict__ data_all, const uint32_t* __restrict__ tw_inv29, const uint32_t* __restrict__ tw_fwd29, const Fr* __restrict__ scale_br, int logn, int ab_only) {
+    Fr* __restrict__ data = data_all + (ntt_vec(ab_only) << logn);
     extern __shared__ uint32_t tile[];
     constexpr int B = 9, MID = 1 << B, NSUB = NTT_TILE / MID;
     const size_t base = (size_t)blockIdx.x * NTT_TILE;
@@ -421,10 +448,12 @@ int ntt_bitrev_table(zkc_ctx* ctx, const Fr* d_src, Fr** out, int logn) {
     return ZKC_OK;
 }
 // the prover's transform pair on `nvec` contiguous vectors: data <- NTT(scale x iNTT(data)), in place (tmp is not needed); 12 <= logn <= 27.
+// [c rows] ab_only: the nvec vectors are the first two of every three (the A and B thirds of nvec / 2 proofs' [3][n] blocks); no block is launched for the third.
 // Up to 2^18: head (NR 0 .. logn-10) -> mid -> tail (RN 10 .. logn), three HBM round trips.  [r4] Above (BASELINE configs[4]: a 2^20 domain, the ceiling of the reference's
 // powers of tau, circuit/circuit-compiler.sh:57) the logn-9 head stages and the logn-9 tail stages no longer fit one tile of 1024 elements with whole cache lines per row,
 // so each side is two kernels: five round trips, still in place and still without a single permuted access (the stand-alone ntt_run needs six, two of them bit-reversed gathers).
-int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv29, const uint32_t* tw_fwd29, const Fr* scale_br, int logn, int nvec) {
+int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv29, const uint32_t* tw_fwd29, const Fr* scale_br, int logn, int nvec, bool ab_only) {
+    const int ab = ab_only ? 1 : 0;
     if (logn < 12 || logn > 27) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "ntt_pair_run: 12 <= logn <= 27");
     const int bh = logn - 9;                                     // head: NR stages 0 .. logn-10, tail: RN stages 10 .. logn (bh stages each)
     const int b1 = bh <= 9 ? bh : (bh + 1) / 2, b2 = bh - b1;    // one kernel each side up to 2^18, two above
@@ -435,11 +464,11 @@ int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv2
     // too: 137 instead of 145 instructions per element and stage, but 162-168 VGPRs (three waves per SIMD instead of four) -- 2856 / 2845 against 2997 / 2990 proofs/s, -5 %; removed.
     const int radix = (int)sw::value<sw::ZKC_NTT_RADIX>(4);
     auto head = radix >= 4 ? zkc_ntt_nr_head_r4 : zkc_ntt_nr_head;
-    hipLaunchKernelGGL(head, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_inv29, logn, 0, b1);
-    if (b2) hipLaunchKernelGGL(head, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_inv29, logn, b1, b2);
-    hipLaunchKernelGGL(zkc_ntt_mid, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, data, tw_inv29, tw_fwd29, scale_br, logn);
-    hipLaunchKernelGGL(zkc_ntt_pass, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_fwd29, (const Fr*)nullptr, logn, 9, b1, 0);
-    if (b2) hipLaunchKernelGGL(zkc_ntt_pass, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_fwd29, (const Fr*)nullptr, logn, 9 + b1, b2, 0);
+    hipLaunchKernelGGL(head, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_inv29, logn, 0, b1, ab);
+    if (b2) hipLaunchKernelGGL(head, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_inv29, logn, b1, b2, ab);
+    hipLaunchKernelGGL(zkc_ntt_mid, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, data, tw_inv29, tw_fwd29, scale_br, logn, ab);
+    hipLaunchKernelGGL(zkc_ntt_pass, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_fwd29, (const Fr*)nullptr, logn, 9, b1, 0, ab);
+    if (b2) hipLaunchKernelGGL(zkc_ntt_pass, dim3(blocks, nvec), dim3(256), (size_t)NTT_TILE * 36, st, (const Fr*)data, data, tw_fwd29, (const Fr*)nullptr, logn, 9 + b1, b2, 0, ab);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("ntt_pair_run: ") + hipGetErrorString(e));
     return ZKC_OK;
@@ -482,7 +511,7 @@ int ntt_run(zkc_ctx* ctx, hipStream_t st, const Fr* src, Fr* dst, const uint32_t
         const int nblocks = (1 << logn) / ((1 << b) * lo_t);
         const bool last = s0 + b == logn;
         hipLaunchKernelGGL(zkc_ntt_pass, dim3(nblocks, nvec), dim3(256), (size_t)(1 << b) * lo_t * 36, st,
-                           first ? src : dst, dst, tw29, last ? scale : nullptr, logn, s0, b, first ? 1 : 0);
+                           first ? src : dst, dst, tw29, last ? scale : nullptr, logn, s0, b, first ? 1 : 0, 0);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return zkc_fail(ctx, ZKC_ERR_HIP, std::string("zkc_ntt_pass: ") + hipGetErrorString(e));
         s0 += b; first = false;

@@ -128,6 +128,44 @@ template <class Lists> inline ProofViews proof_views(const KeyShape& k, const Pa
     return {{w, nullptr, nv, p.oA, nv, 0}, {w, nullptr, nv, p.oB1, nv, 0}, {w + 8ull * (np + 1), nullptr, nc, p.oC, nc, 0}};
 }
 
+// ---- [c rows] the transform pair of C left out of a folded pass (DESIGN.md "Constant folding", ZKC_C_ROWS) ----
+// C on the domain is the key's template except on the constraints the pass lists (zkc_abc_rows.h: VoterRows::crows), and the pair is linear: the pass joins A'B' with the
+// template's transformed C, kept per key, and the listed differences enter the H job as k more (scalar, base) pairs against the second half of the H table (-H').  That
+// trades a third of the pass' transform work for k nw_H additions per proof, so it pays while k nw_H <= beta n log2 n.  Everything else keeps the pair of three vectors:
+// a pass that is not folded or whose buildABC is not (the prefetched one of a one-lane call, ZKC_ABC_FOLD=0), a pass laid out early, the tree-shaped pass of one or two
+// proofs, a key without the wide H table, a lane whose work space does not hold the further entries or the second half of the H scalars.
+// The answer reads the pass' depths (through k) and its lane, never the state of the top-of-tree table: section_entries is counted over the lists that fold no top.
+struct CRowsIn {
+    int mode;                        // ZKC_C_ROWS as the key was loaded: 0 never, 2 wherever legal, else the rule
+    uint32_t beta_milli;             // beta in thousandths
+    bool wide_table;                 // the key's H table has 2 n rows per window
+    bool abc_folded, early;          // buildABC of this pass runs over the voter rows only; the pass was laid out before its witnesses existed
+    uint32_t k;                      // constraints whose C the pass forms
+    int logn;
+    size_t section_entries;          // (scalar, window) entries of the pass' A, B1 and C jobs, at most: over the lists that fold no top, at the key's 12-bit windows
+    size_t cap_p_words;              // words of the lane's H-scalar buffer
+};
+inline bool c_rows_rule(uint32_t k, int nw_h, uint32_t n, int logn, uint32_t beta_milli) { return (uint64_t)k * (uint64_t)nw_h * 1000u <= (uint64_t)beta_milli * n * (uint64_t)logn; }
+// what costs nothing to ask: a pass that fails this never takes the path, and its caller need not count section_entries for it
+inline bool c_rows_candidate(const KeyShape& key, const PassShape& p, int nb, const CRowsIn& in) {
+    if (in.mode == 0 || !in.wide_table || !in.abc_folded || in.early || p.tree || nb <= 2) return false;
+    return in.mode == 2 || c_rows_rule(in.k, msm_nw(key.c_h), key.n, in.logn, in.beta_milli);
+}
+inline bool c_rows(const KeyShape& key, const PassShape& p, int nb, const LaneCaps& cap, const CRowsIn& in) {
+    if (!c_rows_candidate(key, p, nb, in)) return false;
+    const int nw_h = msm_nw(key.c_h);
+    if (in.section_entries + (size_t)nb * nw_h * ((size_t)key.n + in.k) > cap.w1_entries) return false;
+    if ((size_t)nb * 16 * key.n > in.cap_p_words) return false;
+    return true;
+}
+// the H job's list on that path: the identity over [0, n), then n + j for the listed constraints j (ascending): scalar and table row of entry i are both h_vmap[i]
+inline std::vector<uint32_t> h_vmap(uint32_t n, const uint32_t* crows, uint32_t k) {
+    std::vector<uint32_t> v((size_t)n + k);
+    for (uint32_t i = 0; i < n; i++) v[i] = i;
+    for (uint32_t i = 0; i < k; i++) v[(size_t)n + i] = n + crows[i];
+    return v;
+}
+
 // ---- on which stream, and behind what, the stages of a pass go ----
 struct StreamOrder {
     bool mv_prefetch;          // buildABC of the next pass is issued on the blinding stream beside this pass' accumulation (a call that stays on one lane)

@@ -24,17 +24,19 @@ using namespace zkc;
 // the pair runs in place, the two-transform form writes it afterwards) when it is large enough for nVars elements per proof
 // [abc fold] d_abc / d_wm: where the products and the wires' Montgomery forms go (a lane's d_abc and d_t; the key's template buffers once, abc_template).  al != nullptr (a folded
 // pass, abc_rows): every proof's block is first the key's template abc, then the SAME three kernels run over the voter rows of the pass' depths and the wires those read
-void zkc::matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al) {
+// [c rows] c_rows (a folded pass that leaves out the transform pair of C): the template's A and B thirds only, and no C is formed -- zkc_c_rows_delta (h_evals_dev) reads the
+// A and B rows of the listed constraints instead
+void zkc::matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al, bool c_rows) {
     const uint32_t n = zk->n, nv = zk->nVars;
     const bool units = zk->n_unit_coeffs > 0 && nv <= 3 * (size_t)n && sw::on<sw::ZKC_MATVEC_UNITS>();
     const Fr* wm = units ? (const Fr*)d_wm : (const Fr*)nullptr;
     if (al) {
-        const uint32_t per = 6 * n;                                                  // uint4 per [3][n] block
-        hipLaunchKernelGGL(zkc_abc_fill, dim3((per + 1023) / 1024, nb), dim3(256), 0, mv, (const uint4*)zk->fold.d_abc_tmpl, (uint4*)d_abc, per);
+        const uint32_t stride = 6 * n, per = c_rows ? 4 * n : stride;                // uint4 per [3][n] block, and how many of them are copied
+        hipLaunchKernelGGL(zkc_abc_fill, dim3((per + 1023) / 1024, nb), dim3(256), 0, mv, (const uint4*)zk->fold.d_abc_tmpl, (uint4*)d_abc, per, stride);
         if (units && al->nW) hipLaunchKernelGGL(zkc_wtns_mont_list, dim3((al->nW + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)d_wtns0, (size_t)nv, d_wm, 3 * (size_t)n, al->d + al->offW, al->nW);
         if (al->nrows) hipLaunchKernelGGL(zkc_matvec_jds, dim3((al->nrows + 63 * al->nlong + 255) / 256, nb), dim3(256), 0, mv, zk->d_perm, zk->d_rowlen, zk->d_jdptr, zk->d_col, zk->d_val,
                                           (const Fr*)d_wtns0, (size_t)nv, d_abc, (int)n, al->nlong, wm, 3 * (size_t)n, (const uint32_t*)al->d, al->nrows);
-        if (al->nC) hipLaunchKernelGGL(zkc_pointwise_mul, dim3((al->nC + 255) / 256, nb), dim3(256), 0, mv, d_abc, (int)n, (const uint32_t*)(al->d + al->offC), al->nC);
+        if (al->nC && !c_rows) hipLaunchKernelGGL(zkc_pointwise_mul, dim3((al->nC + 255) / 256, nb), dim3(256), 0, mv, d_abc, (int)n, (const uint32_t*)(al->d + al->offC), al->nC);
         return;
     }
     if (units) hipLaunchKernelGGL(zkc_wtns_mont, dim3((nv + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)d_wtns0, (size_t)nv, d_wm, 3 * (size_t)n, nv);
@@ -75,7 +77,8 @@ static LaneNeed lane_need(const zkc_zkey* zk, int inflight) {
     const uint32_t n = zk->n, nv = zk->nVars; const int NWS = msm_nw(zk->c_sec), NWB = msm_nw(zk->c_h);
     const size_t per_proof_entries = (size_t)NWS * 3 * nv + (size_t)NWB * n;
     const size_t per_proof_buckets = 3 * (size_t)msm_half(std::max(zk->c_sec, zk->c_deep)) + msm_half(zk->c_h);      // (a deep pass has fewer entries and more buckets)
-    LaneNeed nd; nd.abc = 3 * (size_t)n * inflight; nd.p = 8 * (size_t)n * inflight; nd.fin = finalize_scratch_bytes(inflight); nd.bs = 2 * 2 * 8 * (size_t)nv;
+    LaneNeed nd; nd.abc = 3 * (size_t)n * inflight; nd.fin = finalize_scratch_bytes(inflight); nd.bs = 2 * 2 * 8 * (size_t)nv;
+    nd.p = (zk->h_rows == 2 * n ? 16 : 8) * (size_t)n * inflight;      // ([c rows] a key with the wide H table: 2 n scalars per H job)
     nd.e1 = per_proof_entries * inflight; nd.b1 = per_proof_buckets * inflight; nd.j1 = 4 * inflight;
     nd.e2 = (size_t)NWS * nv * inflight; nd.b2 = (size_t)msm_half(std::max(zk->c_sec, zk->c_deep)) * inflight; nd.j2 = inflight;
     return nd;
@@ -269,16 +272,22 @@ int zkc::zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int op
     zk->c_h = std::max(zk->c_h, std::max(zk->c_sec, zk->c_deep));
     const int NWB = msm_nw(zk->c_h);
     zk->offA = 0; zk->offB1 = NWS * nv; zk->offC = 2 * NWS * nv; zk->offH = 2 * NWS * nv + NWS * nc;
+    // [c rows] a census key whose buildABC folds keeps 2 n rows per window of the H table, [H_w | -H'_w]: the second half is what the C rows of a pass that leaves out C's
+    // transform pair are summed against (c_rows_prepare fills it at the first such pass; +64 B x n x windows: 126 MB at nLevels = 160).  ZKC_C_ROWS=0: the narrow table
+    zk->c_rows_mode = (int)sw::value<sw::ZKC_C_ROWS>(1); zk->c_rows_beta = (uint32_t)sw::value<sw::ZKC_C_ROWS_BETA>(120);
+    // ... for domains whose doubled table leaves the H job's entry word as it is: nw x 2 n rows below 2^23, the 8 + 8 bit split of the bucketing (MsmJobList::finish) -- up
+    // to n = 2^18 at 15 windows.  A larger domain keeps the narrow table and the old path
+    zk->h_rows = (zk->c_rows_mode != 0 && !zk->fold.abc_cls.empty() && zk->logn >= 12 && (uint64_t)NWB * 2 * n < (1ull << 23) && !sw::on<sw::ZKC_NTT_SEPARATE>()) ? 2 * n : n;
     const int NWD = zk->c_deep ? msm_nw(zk->c_deep) : 0;
-    zk->offA_deep = zk->offH + NWB * n; zk->offB1_deep = zk->offA_deep + NWD * nv; zk->offC_deep = zk->offB1_deep + NWD * nv;
-    const size_t g1_points = (size_t)NWS * (2 * (size_t)nv + nc) + (size_t)NWB * n + (size_t)NWD * (2 * (size_t)nv + nc);
+    zk->offA_deep = zk->offH + NWB * zk->h_rows; zk->offB1_deep = zk->offA_deep + NWD * nv; zk->offC_deep = zk->offB1_deep + NWD * nv;
+    const size_t g1_points = (size_t)NWS * (2 * (size_t)nv + nc) + (size_t)NWB * zk->h_rows + (size_t)NWD * (2 * (size_t)nv + nc);
     if (g1_points >= (1ull << 31)) return bail(zkc_fail(ctx, ZKC_ERR_FORMAT, "zkey too large for 31-bit point indices"));
     if ((rc = dmalloc(ctx, &zk->d_g1, g1_points)) || (rc = dmalloc(ctx, &zk->d_g2, (size_t)NWS * nv))) return bail(rc);
     ZKC_UP(zk->d_g1 + zk->offA, sec[5], 64ull * nv); ZKC_UP(zk->d_g1 + zk->offB1, sec[6], 64ull * nv);
     ZKC_UP(zk->d_g1 + zk->offC, sec[8], 64ull * nc); ZKC_UP(zk->d_g1 + zk->offH, sec[9], 64ull * n);
     ZKC_UP(zk->d_g2, sec[7], 128ull * nv);
     if ((rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offA, zk->c_sec)) || (rc = msm_precompute_g1(ctx, nv, zk->d_g1 + zk->offB1, zk->c_sec)) ||
-        (rc = msm_precompute_g1(ctx, nc, zk->d_g1 + zk->offC, zk->c_sec)) || (rc = msm_precompute_g1(ctx, n, zk->d_g1 + zk->offH, zk->c_h)) ||
+        (rc = msm_precompute_g1(ctx, nc, zk->d_g1 + zk->offC, zk->c_sec)) || (rc = msm_precompute_g1(ctx, n, zk->d_g1 + zk->offH, zk->c_h, zk->h_rows)) ||
         (rc = msm_precompute_g2(ctx, nv, zk->d_g2, zk->c_sec))) return bail(rc);
     if ((rc = dmalloc(ctx, &zk->d_g2_29, G2ROW_WORDS * (size_t)NWS * nv)) || (rc = msm_g2_table29(ctx, zk->d_g2, zk->d_g2_29, (size_t)NWS * nv))) return bail(rc);
     if (zk->c_deep) {   // the sections again for c_deep-bit windows (at nLevels = 160: 15 bits, 17 x 64 B per wire and G1 section, 17 x 240 B for G2: 0.6 GB beside the 0.8 GB of the 12-bit tables)
@@ -367,27 +376,38 @@ extern "C" int zkc_zkey_info(const zkc_zkey* zk, uint32_t* nVars, uint32_t* nPub
 
 // stages a2..a4 for `nb` proofs: leaves (A'B' - C') on the odd coset in d_p[q] (standard form), q < nb
 // buildABC (a2) for `nb` proofs on stream `mv`: A_w, B_w by the jagged-diagonal mat-vec, C_w = A_w o B_w (al: over the voter rows of a folded pass only, matvec_launch)
-static int h_matvec_dev(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr) {
+static int h_matvec_dev(zkc_zkey* zk, zkc_lane& L, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr, bool c_rows = false) {
     zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n, nv = zk->nVars;
     zkc_prof_scope _ps(ctx, ZKC_PROF_MATVEC, (uint64_t)nb * ((uint64_t)zk->nCoeffs * 68 + 3ull * n * 32), mv);
-    matvec_launch(zk, L.d_abc, L.d_t, d_wtns0, nb, mv, al);
+    matvec_launch(zk, L.d_abc, L.d_t, d_wtns0, nb, mv, al, c_rows);
+    // [c rows] the differences a b - c_T of the listed constraints, while A and B still are on the domain: the second half of each proof's H scalars
+    if (c_rows && al->nC) hipLaunchKernelGGL(zkc_c_rows_delta, dim3((al->nC + 255) / 256, nb), dim3(256), 0, mv, (const Fr*)L.d_abc, (const Fr*)(zk->fold.d_abc_tmpl + 2 * (size_t)n), L.d_p, (int)n,
+                                             (const uint32_t*)(al->d + al->offC), al->nC);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     return ZKC_OK;
 }
 // stages a2..a4 for `nb` proofs: leaves (A'B' - C') on the odd coset in d_p[q] (standard form), q < nb.  with_matvec = false: buildABC has been
 // run already (on another stream; L.st has been made to wait for it)
-static int h_evals_dev(zkc_zkey* zk, zkc_lane& L, hipStream_t st, const uint32_t* d_wtns0, int nb, bool with_matvec = true, const zkc_zkey::Fold::AbcRows* al = nullptr) {
+// [c rows] c_rows (needs with_matvec and al): the pair runs over the A and B vectors only, joinABC takes the key's transformed template C, and d_p[q] is 2 n scalars: the
+// evaluations, then the differences of the listed C rows (h_matvec_dev)
+static int h_evals_dev(zkc_zkey* zk, zkc_lane& L, hipStream_t st, const uint32_t* d_wtns0, int nb, bool with_matvec = true, const zkc_zkey::Fold::AbcRows* al = nullptr, bool c_rows = false) {
     zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n;
-    if (with_matvec) { int rc0 = h_matvec_dev(zk, L, d_wtns0, nb, st, al); if (rc0) return rc0; }
+    if (c_rows && !(with_matvec && al && zk->fold.c_rows_ready)) return zkc_fail(ctx, ZKC_ERR_GENERIC, "h_evals_dev: a pass without C's transform pair needs its row lists and the key's tables (internal error)");
+    if (with_matvec) { int rc0 = h_matvec_dev(zk, L, d_wtns0, nb, st, al, c_rows); if (rc0) return rc0; }
+    const int nvec = c_rows ? 2 * nb : 3 * nb;      // the grid's second dimension in the transform kernels: what the key's counter adds up (zkc_debug_c_rows)
     zkc_prof_scope _pn(ctx, ZKC_PROF_NTT, (uint64_t)nb * (6ull * 2 * n * 32 + 4ull * n * 32), st);   // 6 transforms r+w, joinABC
     int rc;
     if (!sw::on<sw::ZKC_NTT_SEPARATE>() && zk->logn >= 12 && zk->logn <= 27) {      // (the switch is diagnostics: the round-1 path, two full transforms, four HBM round trips)
-        if ((rc = ntt_pair_run(ctx, st, L.d_abc, zk->d_tw_inv29, zk->d_tw_fwd29, zk->d_coset_br, (int)zk->logn, 3 * nb))) return rc;
+        if ((rc = ntt_pair_run(ctx, st, L.d_abc, zk->d_tw_inv29, zk->d_tw_fwd29, zk->d_coset_br, (int)zk->logn, nvec, c_rows))) return rc;
+        zk->fold.ntt_vectors += (uint64_t)nvec;
     } else {
-        if ((rc = ntt_run(ctx, st, L.d_abc, L.d_t, zk->d_tw_inv29, zk->d_coset, (int)zk->logn, 3 * nb))) return rc;
-        if ((rc = ntt_run(ctx, st, L.d_t, L.d_abc, zk->d_tw_fwd29, nullptr, (int)zk->logn, 3 * nb))) return rc;
+        if (c_rows) return zkc_fail(ctx, ZKC_ERR_GENERIC, "h_evals_dev: the two-transform form has no A / B only pass (internal error)");
+        if ((rc = ntt_run(ctx, st, L.d_abc, L.d_t, zk->d_tw_inv29, zk->d_coset, (int)zk->logn, nvec))) return rc;
+        if ((rc = ntt_run(ctx, st, L.d_t, L.d_abc, zk->d_tw_fwd29, nullptr, (int)zk->logn, nvec))) return rc;
+        zk->fold.ntt_vectors += (uint64_t)nvec;
     }
-    hipLaunchKernelGGL(zkc_join_abc, dim3((n + 255) / 256, nb), dim3(256), 0, st, L.d_abc, L.d_p, (int)n);
+    if (c_rows) hipLaunchKernelGGL(zkc_join_abc_ct, dim3((n + 255) / 256, nb), dim3(256), 0, st, (const Fr*)L.d_abc, (const Fr*)zk->fold.d_c_hat, L.d_p, (int)n);
+    else hipLaunchKernelGGL(zkc_join_abc, dim3((n + 255) / 256, nb), dim3(256), 0, st, L.d_abc, L.d_p, (int)n);
     ZKC_HIP_CHECK(ctx, hipGetLastError());
     return ZKC_OK;
 }
@@ -422,11 +442,34 @@ extern "C" int zkc_msm_debug(zkc_zkey* zk, int which, const void* d_scalars, uin
     if (count != full) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_msm_debug: count must equal the section size");
     static thread_local MsmJobList jl; jl.clear(256, 1024, which == 2 ? (uint32_t)MSM_MAX_VW_PER_JOB : (uint32_t)MSM_MAX_VW_G1);
     const uint32_t offs[5] = {zk->offA, zk->offB1, 0, zk->offC, zk->offH};
-    jl.add((const uint32_t*)d_scalars, nullptr, count, offs[which], full, 0, which == 4 ? zk->c_h : zk->c_sec);
+    jl.add((const uint32_t*)d_scalars, nullptr, count, offs[which], which == 4 ? zk->h_rows : full, 0, which == 4 ? zk->c_h : zk->c_sec);
     int rc = which == 2 ? msm_pass_g2(zk, L0.w2, jl, 0, true, st_l0) : msm_pass_g1(zk, L0.w1, jl, 0, true, st_l0); if (rc) return rc;
     ZKC_HIP_CHECK(ctx, hipStreamSynchronize(st_l0));
     if (which == 2) wr_g2_std((uint8_t*)host_out, xyzz_to_affine(*(G2XYZZ*)L0.w2.h_results));
     else wr_g1_std((uint8_t*)host_out, xyzz_to_affine(*(G1XYZZ*)L0.w1.h_results));
+    return ZKC_OK;
+}
+
+// [c rows] test and measurement access to what a pass without C's transform pair reads of its key (include/zkcensus.h):
+//   what 0: the points -H'_j, j in [first, first + count), as the H table holds them, in the 64-byte standard form zkc_msm_debug writes; makes the tables if no pass has yet
+//   what 1: the template's abc block, 3 x domainSize x 32 B in Montgomery form (what zkc_debug_stage 0 gives for a witness)
+//   what 2: four uint64: vectors the key's passes sent through the transform pair, passes without C's pair, folded passes with it, 1 if the tables are made
+extern "C" int zkc_debug_c_rows(zkc_zkey* zk, int what, uint32_t first, uint32_t count, void* host_out) {
+    if (!zk || !host_out || what < 0 || what > 2) return ZKC_ERR_BAD_ARG;
+    zkc_ctx* ctx = zk->ctx; const uint32_t n = zk->n;
+    ZKC_LOCK(ctx);
+    if (what == 2) { const uint64_t v[4] = {zk->fold.ntt_vectors, zk->fold.c_rows_passes, zk->fold.old_passes, zk->fold.c_rows_ready ? 1u : 0u}; memcpy(host_out, v, sizeof v); return ZKC_OK; }
+    if (zk->nLevels < 0 || zk->fold.abc_cls.empty()) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_debug_c_rows: not a census key whose buildABC folds");
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device)); ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    int rc; if ((rc = fold_prepare(zk))) return rc;
+    uint32_t* tmpl = zkc_get_template(ctx, zk->nLevels); if (!tmpl) return ZKC_ERR_HIP;
+    if ((rc = abc_template(zk, tmpl))) return rc;
+    if (what == 1) { ZKC_HIP_CHECK(ctx, hipMemcpy(host_out, zk->fold.d_abc_tmpl, 96ull * n, hipMemcpyDeviceToHost)); return ZKC_OK; }
+    if (zk->h_rows != 2 * n || first >= n || count > n - first) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, "zkc_debug_c_rows: no wide H table on this key, or points outside it");
+    if ((rc = c_rows_prepare(zk))) return rc;
+    std::vector<G1Affine> pts(count);
+    ZKC_HIP_CHECK(ctx, hipMemcpy(pts.data(), zk->d_g1 + zk->offH + n + first, (size_t)count * sizeof(G1Affine), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < count; i++) wr_g1_std((uint8_t*)host_out + 64 * (size_t)i, pts[i]);
     return ZKC_OK;
 }
 
@@ -616,14 +659,31 @@ int zkc::prove_batch_begin(zkc_zkey* zk, int cs, const void* d_wtns, uint32_t nW
         // (below) is enqueued before its pass' depths are on the host and computes every row as before.
         zkc_zkey::Fold::AbcRows ar; const bool abc_fold = fold && !mv_done && !zk->fold.abc_cls.empty() && zk->fold.d_abc_tmpl != nullptr;
         if (abc_fold) { int Dc = 0, Ds = 0; for (int q = 0; q < nb; q++) { Dc = std::max(Dc, (int)dcq[q]); Ds = std::max(Ds, (int)dsq[q]); } if ((rc = abc_rows(zk, Dc, Ds, &ar))) return rc; }
-        if ((rc = h_evals_dev(zk, LN, st, w0, nb, !mv_done, abc_fold ? &ar : nullptr))) return rc;
+        // [c rows] ... and such a pass may leave out the transform pair of C (plan::c_rows): its listed C rows join the H job below.  The section entries the lane must still
+        // hold are counted -- only for a pass that is otherwise eligible -- over the lists that fold no top and at the 12-bit windows (an upper bound of what the pass' own
+        // lists and windows give), so the answer reads the pass' depths and its lane and never the state of the top-of-tree table
+        bool c_rows = false; uint32_t* d_hv = nullptr;
+        if (abc_fold && zk->c_rows_mode != 0 && zk->h_rows == 2 * n) {
+            plan::CRowsIn ci{zk->c_rows_mode, zk->c_rows_beta, true, true, early, ar.nC, (int)zk->logn, 0, LN.cap_p};
+            if (plan::c_rows_candidate(KS, PS, nb, ci)) {
+                for (int q = 0; q < nb; q++) { zkc_zkey::Fold::VMap v0; if ((rc = fold_vmap(zk, 0, dcq[q], 0, dsq[q], &v0))) return rc; ci.section_entries += (size_t)msm_nw(KS.c_sec) * ((size_t)v0.nA + v0.nB + v0.nC); }
+                c_rows = plan::c_rows(KS, PS, nb, plan::LaneCaps{LN.w1.max_entries, LN.w1.max_buckets, LN.w1.max_jobs, LN.w2.max_entries}, ci);
+            }
+            if (c_rows) { d_hv = ar.d_hv; if ((rc = c_rows_prepare(zk))) return rc; }
+        }
+        if (fold) (c_rows ? zk->fold.c_rows_passes : zk->fold.old_passes)++;
+        if ((rc = h_evals_dev(zk, LN, st, w0, nb, !mv_done, abc_fold ? &ar : nullptr, c_rows))) return rc;
         if (st2 != st || SO.mv_prefetch) ZKC_HIP_CHECK(ctx, hipEventRecord(LN.ev_ntt, st));      // read by the G2 stream's held accumulation and by the buildABC prefetch
         tr[2] = now_ms();
         static thread_local MsmJobList j1, j2;     // 6 KB each: kept off the stack frame of a C-ABI entry point
         j1.clear(PS.vws, PS.vwb, MSM_MAX_VW_G1); j2.clear(PS.vw_g2, 1024, MSM_MAX_VW_PER_JOB);
         // job order of the G1 pass: the nb H jobs first (the 16-bit bucket sort wants the jobs with the larger bucket count in front), then
         // A, B1, C per proof.  zkc_finalize reads results[q] = H_q and results[nb + 3 q + {0, 1, 2}] = A_q, B1_q, C_q.
-        for (int q = 0; q < nb; q++) j1.add(LN.d_p + 8 * (size_t)n * q, nullptr, n, zk->offH, n, 0, zk->c_h);
+        // ([c rows] a pass without C's transform pair: 2 n scalars per proof, the evaluations and then the listed differences, against [H | -H'] through the pass' list)
+        for (int q = 0; q < nb; q++) {
+            if (c_rows) j1.add(LN.d_p + 16 * (size_t)n * q, d_hv, n + ar.nC, zk->offH, zk->h_rows, 0, zk->c_h);
+            else j1.add(LN.d_p + 8 * (size_t)n * q, nullptr, n, zk->offH, zk->h_rows, 0, zk->c_h);
+        }
         // per proof: A, B1, C over its views (its wire lists, or the whole sections); in a small pass (tree) the same A and B1 again over the blinded scalars
         auto add = [](MsmJobList& jl, const uint32_t* scalars, const plan::SectionView& v, int c) { jl.add(scalars, v.vmap, v.count, v.tbl_off, v.tbl_count, v.pt_shift, c); };
         BlindArgs ba{}; ba.rs = CS.d_rs + 64 * (size_t)p0; ba.nv = nv;

@@ -213,6 +213,9 @@ struct zkc_zkey {
     uint32_t* d_g2_29 = nullptr;                                            // the G2 table again in radix 2^29 (G2ROW_WORDS per point: x, y, -y; zkc_f29_g2.h), read by the accumulation
     uint32_t* d_g2_29_lone = nullptr;                                       // the same bases pre-shifted for MSM_C_G2_LONE (32 windows), radix 2^29 only; nullptr: not built (ZKC_G2_LONE_TABLE=0)
     uint32_t offA = 0, offB1 = 0, offC = 0, offH = 0;                       // table offsets inside d_g1 (points)
+    // [c rows] rows per window of the H table: n, or 2 n for a census key that may leave the transform pair of C out of a pass -- [H_w | -H'_w], the second half filled at the
+    // first pass that takes that path (c_rows_prepare).  A job over the first n points never sees the second half.  c_rows_mode / c_rows_beta: ZKC_C_ROWS / ZKC_C_ROWS_BETA at key load
+    uint32_t h_rows = 0; int c_rows_mode = 1; uint32_t c_rows_beta = 120;
     // [r4] a census key of 2^16 wires and more keeps its witness sections a second time, pre-shifted for c_deep = 17-bit windows: a pass whose voters sit deep in the trees (or
     // whose witnesses do not fold at all) has 50-80 k wires per section instead of 8-11 k, and 15 additions per scalar into 65536 buckets then beat 22 into 2048.  0: not built
     int c_deep = 0; uint32_t offA_deep = 0, offB1_deep = 0, offC_deep = 0; uint32_t* d_g2_29_deep = nullptr;
@@ -261,8 +264,13 @@ struct zkc_zkey {
         // made by buildABC's own kernels, and per pair of pass depths one allocation [voter rows as sorted positions | constraints whose C is formed | wires those rows read]
         std::vector<zkc::abc::RowClass> abc_cls; std::vector<uint32_t> abc_rowptr, abc_col, abc_perm;
         zkc::Fr* d_abc_tmpl = nullptr;
-        struct AbcRows { uint32_t* d = nullptr; uint32_t nrows = 0, nlong = 0, offC = 0, nC = 0, offW = 0, nW = 0; };
+        struct AbcRows { uint32_t* d = nullptr; uint32_t nrows = 0, nlong = 0, offC = 0, nC = 0, offW = 0, nW = 0;
+                         uint32_t* d_hv = nullptr; };      // [c rows] a key with the wide H table: the H job's list over these C rows (plan::h_vmap), n + nC entries
         std::map<std::pair<int, int>, AbcRows> abc_rows;
+        // [c rows] the template's C after the transform pair (Montgomery form, n elements), made with -H' at the first pass that leaves C's pair out; per pair of pass depths
+        // what the passes of this key ran: vectors through the transform pair, passes on the new path, folded passes on the old one
+        zkc::Fr* d_c_hat = nullptr; bool c_rows_ready = false;
+        uint64_t ntt_vectors = 0, c_rows_passes = 0, old_passes = 0;
         // [top fold] the levels between the root and depth K of a tree are the same bits for every voter below one depth-K node: a direct-mapped table of such subtrees
         // per tree, each slot written ONCE (by the first witness that lands on it while it is empty, top_seed) and kept for the life of the key.  K = 0: off
         struct Top {
@@ -290,7 +298,7 @@ int msm_g2_window_table29(zkc_ctx* ctx, const G2Affine* d_bases, uint32_t count,
 // n affine G2 points (device) -> a fresh table of their rows; the stream is synchronised, so the caller may drop the points
 int msm_g2_rows29(zkc_ctx* ctx, const G2Affine* d_points, size_t n, const char* what, uint32_t** out);
 // [r2] the prover's pair iNTT -> x scale -> NTT in three HBM round trips without bit reversal (zkc_ntt.hip); scale_br = scale table in bit-reversed order
-int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv29, const uint32_t* tw_fwd29, const Fr* scale_br, int logn, int nvec);
+int ntt_pair_run(zkc_ctx* ctx, hipStream_t st, Fr* data, const uint32_t* tw_inv29, const uint32_t* tw_fwd29, const Fr* scale_br, int logn, int nvec, bool ab_only = false);
 int ntt_bitrev_table(zkc_ctx* ctx, const Fr* d_src, Fr** out, int logn);      // twiddles in the 12-word radix-2^29 form ntt_run reads
 int msm_work_alloc(zkc_ctx* ctx, MsmWork& w, size_t max_entries, size_t max_buckets, int max_jobs, bool g2);
 void msm_work_free(MsmWork& w);
@@ -322,8 +330,12 @@ int nofold_vmap(zkc_zkey* zk, zkc_zkey::Fold::VMap* out);
 int top_seed(zkc_zkey* zk, const uint32_t* w0, const std::vector<plan::TopSeed>& seeds);
 int abc_template(zkc_zkey* zk, const uint32_t* tmpl);
 int abc_rows(zkc_zkey* zk, int Dc, int Ds, zkc_zkey::Fold::AbcRows* out);
+// [c rows] the key's transformed template C and the second half of its H table, once per key (synchronous, like abc_template, which it needs); the H job's list for the
+// C rows of a pass of depths (Dc, Ds) comes with its row lists (abc_rows: AbcRows::d_hv)
+int c_rows_prepare(zkc_zkey* zk);
 // zkc_prove.hip -- buildABC's kernels for nb proofs on stream mv (al: over the voter rows of a folded pass only); abc_template runs them over the template witness
-void matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr);
+// c_rows (with al): the C third is neither copied nor formed
+void matvec_launch(zkc_zkey* zk, Fr* d_abc, Fr* d_wm, const uint32_t* d_wtns0, int nb, hipStream_t mv, const zkc_zkey::Fold::AbcRows* al = nullptr, bool c_rows = false);
 // a batch call in two halves (zkc_prove.hip; the public zkc_[full]prove_batch_dev are begin + finish on slot 0): begin validates, enqueues every pass and returns
 // without waiting for the GPU; finish waits for that call and copies proofs / public signals out.  cs = call slot 0 / 1; a slot must be finished before it is
 // begun again; d_wtns (and d_inputs, d_status) stay the caller's until finish returns.  d_inputs == nullptr: the witnesses are given.
@@ -339,7 +351,9 @@ int prove_reserve(zkc_zkey* zk, int inflight);              // grow the key's wo
 int zkey_load_opts(zkc_ctx* ctx, const void* zkey_bytes, size_t len, int nlanes, int max_inflight, zkc_zkey** out);
 size_t zkey_device_bytes(const zkc_zkey* zk, size_t* tables, size_t* work);      // HBM now: the key's constant tables / the per-pass work space of its context's lanes (shared by every key of the context)
 size_t finalize_scratch_bytes(int nproofs);
-int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c);   // d_table[0..count) = base on entry
+int msm_precompute_g1(zkc_ctx* ctx, uint32_t count, G1Affine* d_table, int c, size_t window_stride = 0);   // d_table[0..count) = base on entry; window w at d_table + w * window_stride (0: count)
+// out[i] = scalars[wires[i]] * tbl[wires[i]] for i < nw (device, XYZZ), on ctx->stream, not waited for
+int g1_scale_each(zkc_ctx* ctx, const G1Affine* tbl, const uint32_t* d_scalars, const uint32_t* d_wires, uint32_t nw, G1XYZZ* d_out);
 int msm_precompute_g2(zkc_ctx* ctx, uint32_t count, G2Affine* d_table, int c);
 int msm_g2_table29(zkc_ctx* ctx, const G2Affine* d_table, uint32_t* d_out, size_t count);       // d_out: G2ROW_WORDS per point (zkc_f29_g2.h)
 // out[i] = scalar[wires[i]] * P[wires[i] - pt_shift] (window-0 table), then per-group sums: gsum[g] = sum out[gstart[g]..gstart[g+1])

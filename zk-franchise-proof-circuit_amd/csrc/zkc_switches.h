@@ -71,6 +71,8 @@ constexpr long long ANY = LLONG_MIN;      // no bound on this side of a clamp
     X(ZKC_MATVEC_UNITS,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: buildABC multiplies by its +-1 coefficients instead of adding the wire")                                   \
     X(ZKC_ABC_FOLD,             OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: buildABC of a folded pass computes every row instead of copying the voter-independent ones from the template") \
     X(ZKC_TOP_FOLD,             NUMBER,      0,   12,    LIVE,    "key load: census tree levels below the root whose MSM terms are summed once per subtree instead of per voter (8; 0: off)") \
+    X(ZKC_C_ROWS,               NUMBER,      0,   2,     LIVE,    "key load: a folded pass leaves out the transform pair of C and adds its voter rows of C to the H job: 0 never, 2 wherever it is legal, 1 or unset by the rule k nw_H <= beta n log2 n") \
+    X(ZKC_C_ROWS_BETA,          NUMBER,      0,   100000, LIVE,   "key load: beta of that rule in thousandths (120)")                                                             \
     X(ZKC_MATVEC_INLINE,        SET,        ANY, ANY,   PROCESS, "set (any value, 0 included): buildABC of the next pass is not prefetched on the blinding stream")              \
     X(ZKC_MV_PREFETCH_AT_NTT,   ON_IF_ONE,   ANY, ANY,   PROCESS, "=1: that prefetch starts beside the pass' bucketing instead of beside its accumulation")                       \
     X(ZKC_EARLY_LAYOUT,         OFF_IF_ZERO, ANY, ANY,   PROCESS, "=0: one-pass calls of more than two voters wait for their fold flags instead of reading the depths off the inputs") \
