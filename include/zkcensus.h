@@ -424,4 +424,5 @@ int zkc_setup_from_r1cs(const char* r1cs_path, uint64_t seed, const char* zkey_p
 #include "zkcensus_ptau.h" /* keys from a powers-of-tau file (snarkjs groth16 setup), and zkey verify against the circuit */
 #include "zkcensus_ptau_prepare.h" /* a powers-of-tau file prepared for phase 2 (snarkjs powersoftau prepare phase2), and a prepared file checked */
 #include "zkcensus_ptau_verify.h" /* a powers-of-tau file checked for being the powers of one tau (the point checks of snarkjs powersoftau verify) */
+#include "zkcensus_ptau_contribute.h" /* phase 1: a new powers-of-tau file, a contribution to one, and its chain of contributions checked (snarkjs powersoftau new / contribute / verify) */
 #endif

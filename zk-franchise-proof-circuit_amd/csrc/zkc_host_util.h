@@ -58,6 +58,17 @@ inline void unc_g2(uint8_t o[128], const G2Affine& a) {
     be_fq(o, a.x.c1); be_fq(o + 32, a.x.c0); be_fq(o + 64, a.y.c1); be_fq(o + 96, a.y.c0);
 }
 
+// a secret scalar (standard or Montgomery form): cleared on every way out of its scope, through a volatile pointer so that the stores are not dropped as dead.  wipe does
+// the same for any other storage that held something derived from a secret
+struct Secret {
+    uint32_t v[8] = {0};
+    ~Secret() { wipe(v, 32); }
+    operator uint32_t*() { return v; }
+    static void wipe(void* p, size_t n) { volatile uint8_t* q = (volatile uint8_t*)p; for (size_t i = 0; i < n; i++) q[i] = 0; }
+};
+struct SecretFr { Fr f = Fr::zero(); ~SecretFr() { Secret::wipe(&f, sizeof f); } };
+inline bool std_is_zero(const uint32_t k[8]) { uint32_t o = 0; for (int i = 0; i < 8; i++) o |= k[i]; return o == 0; }
+
 // a < b for two 256-bit integers of eight words, lowest first (standard form)
 inline bool std_less(const uint32_t a[8], const uint32_t b[8]) { for (int i = 7; i >= 0; i--) if (a[i] != b[i]) return a[i] < b[i]; return false; }
 

@@ -95,12 +95,7 @@ zkc_p2_mont_to_std(uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict_
 
 thread_local double g_p2_ms[9] = {0};
 
-// a secret scalar: cleared on every way out of its scope, through a volatile pointer so that the stores are not dropped as dead
-struct Secret {
-    uint32_t v[8] = {0};
-    ~Secret() { volatile uint32_t* q = v; for (int i = 0; i < 8; i++) q[i] = 0; }
-    operator uint32_t*() { return v; }
-};
+// Secret, a scalar cleared on every way out of its scope, and std_is_zero: zkc_host_util.h
 
 // k (standard form, 0 < k < 2^255) -> its non-adjacent form
 ScaleDigits recode_naf(const uint32_t k_in[8]) {
@@ -119,7 +114,6 @@ ScaleDigits recode_naf(const uint32_t k_in[8]) {
     return d;
 }
 
-bool std_is_zero(const uint32_t k[8]) { uint32_t o = 0; for (int i = 0; i < 8; i++) o |= k[i]; return o == 0; }
 
 // the body of zkc_g1_scale_dev: the lock is held and the device is set.  ms (may be NULL): [0] the scale kernel, [1] the conversion to affine
 int scale_dev(zkc_ctx* ctx, const void* d_points, uint32_t n, const uint32_t k[8], bool mont, void* d_out, double* ms) {

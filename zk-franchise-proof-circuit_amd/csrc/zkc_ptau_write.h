@@ -30,17 +30,27 @@ inline bool ptau_out_bytes(PtauOut& o, const void* src, size_t n, std::string& e
     while (n) { const ssize_t k = write(o.fd, s, n); if (k <= 0) { err = "ptau: cannot write " + o.path; return false; } s += k; n -= (size_t)k; }
     return true;
 }
-// the header and the input's sections
-inline bool ptau_out_begin(const Ptau& in, const char* out_path, PtauOut& o, std::string& err) {
+// the temporary file and the file header of nsec sections (zkc_ptau_prepare.hip through ptau_out_begin; zkc_scale_each.hip, whose outputs take no section as it lies)
+inline bool ptau_out_open(const char* out_path, uint32_t nsec, PtauOut& o, std::string& err) {
     if (!out_path) { err = "ptau: no output path"; return false; }
-    if (in.nsections > 0xffffffffu - 4) { err = "ptau: too many sections"; return false; }
     static std::atomic<unsigned> serial{0};                     // two threads of one process writing to one out_path get two names
     o.path = out_path; o.tmp = o.path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(serial.fetch_add(1));
     o.fd = open(o.tmp.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0644);
     if (o.fd < 0) { o.tmp.clear(); err = "ptau: cannot write " + o.path; return false; }
     uint8_t h[12]; memcpy(h, "ptau", 4);
-    const uint32_t ver = 1, nsec = in.nsections + 4; memcpy(h + 4, &ver, 4); memcpy(h + 8, &nsec, 4);
-    if (!ptau_out_bytes(o, h, 12, err)) return false;
+    const uint32_t ver = 1; memcpy(h + 4, &ver, 4); memcpy(h + 8, &nsec, 4);
+    return ptau_out_bytes(o, h, 12, err);
+}
+// the head of a section whose body follows in pieces (ptau_out_bytes)
+inline bool ptau_out_section_head(PtauOut& o, int id, uint64_t nbytes, std::string& err) {
+    uint8_t h[12]; const uint32_t i = (uint32_t)id; memcpy(h, &i, 4); memcpy(h + 4, &nbytes, 8);
+    return ptau_out_bytes(o, h, 12, err);
+}
+// the header and the input's sections
+inline bool ptau_out_begin(const Ptau& in, const char* out_path, PtauOut& o, std::string& err) {
+    if (!out_path) { err = "ptau: no output path"; return false; }
+    if (in.nsections > 0xffffffffu - 4) { err = "ptau: too many sections"; return false; }
+    if (!ptau_out_open(out_path, in.nsections + 4, o, err)) return false;
     std::vector<uint8_t> buf(1u << 20);
     for (uint64_t at = 12; at < in.end;) {                      // in.end <= the file's size: ptau_open has walked the table
         const size_t n = (size_t)std::min<uint64_t>(buf.size(), in.end - at);

@@ -3,7 +3,8 @@
 zkc_ntt_dev / zkc_g1_mul_batch_dev / zkc_msm_g1_*; used by SURVEY.md 8(d) config 5 (ii) (tools/stress.py) and its parity tests.
 g1_fixed_mul / g2_fixed_mul (include/zkcensus_setup.h) are the windowed fixed-base batch products the device key generator is built from; g1_scale
 (include/zkcensus_phase2.h) is the opposite shape, many points times one scalar, which a phase-2 contribution is made of; g1_lagrange / g2_lagrange
-(include/zkcensus_ptau_prepare.h) are the inverse transform over points that prepares a powers-of-tau file."""
+(include/zkcensus_ptau_prepare.h) are the inverse transform over points that prepares a powers-of-tau file; g1_scale_each / g2_scale_each
+(include/zkcensus_ptau_contribute.h) are many points each times its own scalar, which a powers-of-tau contribution is made of."""
 import ctypes
 
 R_MONT = 1 << 256
@@ -44,6 +45,31 @@ def g1_scale(ctx, d_points_ptr, n, k, d_out_ptr, mont=False):
     the text)."""
     kb = k.to_bytes(32, 'little') if isinstance(k, int) else bytes(k)
     ctx._check(ctx._lib.zkc_g1_scale_dev(ctx._h, d_points_ptr, n, kb, 1 if mont else 0, d_out_ptr))
+
+
+def g1_scale_each(ctx, d_points_ptr, n, d_scalars_ptr, d_out_ptr, mont=False):
+    """d_out[i] = k_i * d_points[i]: n affine points (64 B, all zero = infinity), each times its OWN scalar (n x 32 little-endian bytes on the device, standard form, below r;
+    0 gives infinity); include/zkcensus_ptau_contribute.h.  mont: the coordinates are in Montgomery form on both sides, as a .ptau stores them.  d_out may equal d_points.
+    A coordinate >= q, a point off the curve or a scalar >= r raises (ZKC_ERR_FORMAT, the smallest index in the text) and nothing is written."""
+    ctx._check(ctx._lib.zkc_g1_scale_each_dev(ctx._h, d_points_ptr, n, d_scalars_ptr, 1 if mont else 0, d_out_ptr))
+
+
+def g2_scale_each(ctx, d_points_ptr, n, d_scalars_ptr, d_out_ptr, mont=False):
+    """The same in G2: points 128 B (x.c0 | x.c1 | y.c0 | y.c1), anywhere on the twist."""
+    ctx._check(ctx._lib.zkc_g2_scale_each_dev(ctx._h, d_points_ptr, n, d_scalars_ptr, 1 if mont else 0, d_out_ptr))
+
+
+def debug_scale_each(ctx, g2, d_points_ptr, n, d_scalars_ptr, d_out_ptr, mont=False, form=0):
+    """Test hook (zkc_debug_scale_each_dev): g1_scale_each / g2_scale_each with the kernel form, 0 the shipped windowed form, 1 bit-serial double-and-add."""
+    ctx._check(ctx._lib.zkc_debug_scale_each_dev(ctx._h, 1 if g2 else 0, d_points_ptr, n, d_scalars_ptr, 1 if mont else 0, d_out_ptr, form))
+
+
+def scale_each_stats():
+    """Milliseconds of the calling thread's last g1_scale_each / g2_scale_each / debug_scale_each: the scale kernel (point checks included), the conversion to affine."""
+    from . import _native
+    ms = (ctypes.c_double * 2)()
+    _native.load().zkc_debug_scale_each_stats(ms)
+    return {'scale_kernel': ms[0], 'affine': ms[1]}
 
 
 def g1_lagrange(ctx, d_points_ptr, logn, d_out_ptr, mont=False):

@@ -2,7 +2,9 @@
 (circuit/circuit-compiler.sh:80-136) whose outputs are missing blobs; their toxic waste comes from a seed.  Keys nobody holds the waste of: from_ptau(), `snarkjs
 groth16 setup` from a public prepared powers-of-tau file (include/zkcensus_ptau.h), to be followed by phase2.contribute; prepare_ptau() and check_prepared() are
 `snarkjs powersoftau prepare phase2` and the check of a prepared file against its own monomial sections (include/zkcensus_ptau_prepare.h); verify_ptau() checks that
-the monomial sections themselves are the powers of one tau, the point checks of `snarkjs powersoftau verify` (include/zkcensus_ptau_verify.h)."""
+the monomial sections themselves are the powers of one tau, the point checks of `snarkjs powersoftau verify` (include/zkcensus_ptau_verify.h); new_ptau(),
+contribute_ptau(), ptau_contributions() and verify_ptau_contributions() are phase 1 itself, `snarkjs powersoftau new / contribute` and the transcript part of
+`powersoftau verify` (include/zkcensus_ptau_contribute.h)."""
 import ctypes
 import hashlib
 import os
@@ -150,3 +152,101 @@ def ptau_prepare_stats():
     ms = (ctypes.c_double * 6)()
     _native.load().zkc_ptau_prepare_stats(ms)
     return dict(zip(['read', 'upload_check', 'transforms_g1', 'transforms_g2', 'affine_download', 'write_or_compare'], list(ms)))
+
+
+def new_ptau(path, power):
+    """`snarkjs powersoftau new bn128 power path`: an unprepared file with tau = alpha = beta = 1 (every point its group's generator) and no contribution.  Host only."""
+    err = ctypes.create_string_buffer(512)
+    rc = _native.load().zkc_ptau_new(os.fsencode(path), power, err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    return path
+
+
+def _secrets96(secrets):
+    if secrets is None:
+        return None
+    b = b''.join(s.to_bytes(32, 'little') if isinstance(s, int) else bytes(s) for s in secrets)
+    if len(b) != 96:
+        raise ValueError('secrets: (tau, alpha, beta), three integers below r or three times 32 little-endian bytes')
+    return b
+
+
+def contribute_ptau(src, dst, ctx=None, secrets=None, name='', verify=False):
+    """`snarkjs powersoftau contribute src dst`: dst = src with every point of sections 2 .. 6 multiplied by its power of the secrets (tau', alpha', beta'; None draws them
+    from the OS and forgets them) and one more record in section 7 (include/zkcensus_ptau_contribute.h); returns the 64-byte contribution hash.  With a Context the products
+    run on its GPU, without one on host threads; the bytes are the same.  The output holds sections 1 .. 7 only: a prepared input loses its Lagrange sections.
+    verify=True runs verify_ptau on src first and raises ZkcError (ZKC_ERR_FORMAT) with its reason.  Raises ZkcError for a secret that is 0 or >= r, a file that does not
+    parse or a bad point (the section and the smallest index in the text); nothing is left at dst then."""
+    if verify:
+        res = verify_ptau(src, ctx=ctx)
+        if not res[0]:
+            raise _native.ZkcError(5, res[-1])
+    err = ctypes.create_string_buffer(512); h = ctypes.create_string_buffer(64)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_ptau_contribute(None if ctx is None else ctx._h, os.fsencode(src), os.fsencode(dst), _secrets96(secrets), name.encode() if name else None, h, err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    return h.raw
+
+
+def debug_contribute_ptau(src, dst, ctx=None, secrets=None, name='', chunk_points=0, form=0):
+    """Test hook (zkc_debug_ptau_contribute): contribute_ptau with the chunk size in points (0: the default) and the kernel form (0 shipped, 1 bit-serial)."""
+    err = ctypes.create_string_buffer(512); h = ctypes.create_string_buffer(64)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_debug_ptau_contribute(None if ctx is None else ctx._h, os.fsencode(src), os.fsencode(dst), _secrets96(secrets), name.encode() if name else None, chunk_points, form,
+                                       h, err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    return h.raw
+
+
+PTAU_RECORD_FIXED = 1288        # five points (448), three proofs of knowledge (3 x 256), transcript (64), type, paramsLen
+
+
+def ptau_contributions(path):
+    """The records of section 7 as this library writes them -> a list of dicts: the five points after the contribution (tauG1, tauG2, alphaG1, betaG1, betaG2), the three
+    proofs of knowledge (pok: tau, alpha, beta -> g1_s, g1_sx, g2_spx), transcript, type, name, and `raw`, the record's bytes.  Raises ZkcError (ZKC_ERR_FORMAT) for a
+    count that does not fit the section, a truncated record, an unknown tag or type, or trailing bytes."""
+    lib = _native.load()
+    err = ctypes.create_string_buffer(512); n = ctypes.c_uint32(0); need = ctypes.c_size_t(0)
+    rc = lib.zkc_ptau_contributions(os.fsencode(path), ctypes.byref(n), None, ctypes.byref(need), err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    buf = ctypes.create_string_buffer(max(need.value, 1))
+    rc = lib.zkc_ptau_contributions(os.fsencode(path), ctypes.byref(n), buf, ctypes.byref(need), err, 512)
+    if rc != 0:
+        raise _native.ZkcError(rc, err.value.decode())
+    raw, out, at = buf.raw[:need.value], [], 0
+    for _ in range(n.value):
+        r = raw[at:]
+        plen = int.from_bytes(r[1284:1288], 'little')
+        rec = {'tauG1': r[0:64], 'tauG2': r[64:192], 'alphaG1': r[192:256], 'betaG1': r[256:320], 'betaG2': r[320:448], 'pok': {}, 'transcript': r[1216:1280],
+               'type': int.from_bytes(r[1280:1284], 'little'), 'name': '', 'raw': r[:PTAU_RECORD_FIXED + plen]}
+        for i, key in enumerate(('tau', 'alpha', 'beta')):
+            q = r[448 + 256 * i:448 + 256 * (i + 1)]
+            rec['pok'][key] = {'g1_s': q[0:64], 'g1_sx': q[64:128], 'g2_spx': q[128:256]}
+        if plen:
+            rec['name'] = r[PTAU_RECORD_FIXED + 2:PTAU_RECORD_FIXED + 2 + r[PTAU_RECORD_FIXED + 1]].decode(errors='replace')
+        out.append(rec); at += PTAU_RECORD_FIXED + plen
+    return out
+
+
+def verify_ptau_contributions(prev, next, ctx=None, seed=None):
+    """The transcript part of `snarkjs powersoftau verify`, on top of verify_ptau: is `next` what `prev` becomes under the contributions its section 7 adds?  prev = None:
+    the chain starts at the generators (a new_ptau file of next's power).  -> (ok, n_new, reason): the number of records after prev's and, when not ok, the first failing
+    check by name (include/zkcensus_ptau_contribute.h lists them in order).  Raises ZkcError for a HIP failure."""
+    err = ctypes.create_string_buffer(768); n_new = ctypes.c_uint32(0)
+    lib = _native.load() if ctx is None else ctx._lib
+    rc = lib.zkc_ptau_verify_contributions(None if ctx is None else ctx._h, None if prev is None else os.fsencode(prev), os.fsencode(next), None if seed is None else bytes(seed),
+                                           ctypes.byref(n_new), err, 768)
+    if rc < 0:
+        raise _native.ZkcError(-rc, err.value.decode())
+    return rc == 1, n_new.value, err.value.decode()
+
+
+def ptau_contribute_stats():
+    """Milliseconds of the calling thread's last contribute_ptau, by stage."""
+    ms = (ctypes.c_double * 6)()
+    _native.load().zkc_ptau_contribute_stats(ms)
+    return dict(zip(['read', 'upload_scalars_check', 'scale_g1', 'scale_g2', 'affine_download', 'hashes_write'], list(ms)))
