@@ -63,7 +63,11 @@
  *                        double-and-add, the yardstick of tools/ptau_contribute_bench.py).
  * zkc_debug_scale_each_dev: zkc_g1_scale_each_dev (g2 = 0) / zkc_g2_scale_each_dev (g2 = 1) with the kernel form.
  * zkc_debug_scale_each_stats: milliseconds of the calling thread's last scale_each call: ms[0] the scale kernel (point checks included), ms[1] to affine.
- * zkc_debug_scale_each_work_bytes: the device work space one such call allocates beside its arguments. ---- */
+ * zkc_debug_scale_each_work_bytes: the device work space one such call allocates beside its arguments.
+ * zkc_debug_tau_scalars_dev: the scalars of a chunk of a contribution on their own: d_out[i] = mult * tau^(first + i) for i < n, 32 B little endian, standard form, by the
+ *                        power table and the kernel launch a contribution uses (zkc_tau_scalars).  tau32, mult32: 32 B little endian, standard form.  ZKC_ERR_BAD_ARG for a
+ *                        NULL pointer, n = 0, tau or mult outside [1, r), or first + n > 2^32: the table holds tau^(2^k) for k < 32.  The table and the work copy of the
+ *                        scalars are cleared on the stream before they are released. ---- */
 #ifndef ZKCENSUS_PTAU_CONTRIBUTE_H
 #define ZKCENSUS_PTAU_CONTRIBUTE_H
 #include "zkcensus.h"
@@ -86,6 +90,7 @@ int zkc_debug_ptau_contribute(zkc_ctx* ctx, const char* src_path, const char* ds
 int zkc_debug_scale_each_dev(zkc_ctx* ctx, int g2, const void* d_points, uint32_t n, const void* d_scalars32, int mont, void* d_out, int form);
 int zkc_debug_scale_each_stats(double ms[2]);
 uint64_t zkc_debug_scale_each_work_bytes(int g2, uint32_t n, int form);
+int zkc_debug_tau_scalars_dev(zkc_ctx* ctx, const uint8_t* tau32, const uint8_t* mult32, uint64_t first, uint32_t n, void* d_out);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,9 @@
 against the CPU oracle (oracle_lib.g1_mul, and its one-term G2 MSM): both groups, both coordinate forms, in place and out of place, and both kernel forms through the hook
 (0: the shipped windowed form, 1: bit-serial double-and-add).  Sizes around the wave; the scalars at which the signed 4-bit recoding carries through every window, where a
 digit is zero and an operand of the complete addition is infinity, and k = r - 2, the one scalar whose last addition meets equal operands; the field-edge points of
-tests/edge_points.py, which in G2 lie almost all outside the subgroup; one point under many scalars, many points under one scalar against zkc_g1_scale_dev; the refusals."""
+tests/edge_points.py, which in G2 lie almost all outside the subgroup; one point under many scalars, many points under one scalar against zkc_g1_scale_dev; the refusals.
+And n = 1000, sixteen workgroups with a partial last one, where the stride of the entry-major table and the lane split of the batched inversion are no longer those of
+one or two waves: a_i G under k_i against (a_i k_i mod r) G from the fixed-base engines, the scheme of tests/test_gpu_phase2_scale.py."""
 import functools, random
 import pytest
 import oracle_lib as ol
@@ -117,6 +119,32 @@ def test_edge_points(gpu, g2):
     cases = [(g2, True, False, 0), (g2, False, True, 0), (g2, True, True, 1)]
     check(gpu, g2, pts, [rng.randrange(1, R) for _ in pts], cases)
     check(gpu, g2, pts, [R - 2 if i % 2 else R - 1 for i in range(len(pts))], cases)
+
+
+@pytest.mark.parametrize('g2', [False, True])
+def test_a_thousand_points_against_the_fixed_base_engines(gpu, g2):
+    """P_i = a_i G from the fixed-base engine, k_i full-width: every lane must be (a_i k_i mod r) G from that engine, which shares no code with the kernel; 16 sampled
+    lanes and the special ones also against the oracle's product of the input point.  Infinity in and the scalars 0, 1, r - 2 sit at index 0, at index 999 and at both
+    edges of a wave."""
+    n, w = 1000, WIDTH[g2]
+    ctx, _ = gpu
+    rng = random.Random(4000 + g2)
+    a = [rng.randrange(1, R) for _ in range(n)]; ks = [rng.randrange(1, R) for _ in range(n)]
+    for i in (0, 64, 191, 999): a[i] = 0                                      # the all-zero point first, last, in the first and in the last lane of a wave
+    for i, k in ((1, 0), (2, 1), (3, R - 2), (63, R - 2), (127, 0), (128, 1), (192, R - 2), (960, 0), (996, R - 2), (997, 1), (998, 0), (999, R - 2)): ks[i] = k
+    special = [0, 1, 2, 3, 63, 64, 127, 128, 191, 192, 960, 996, 997, 998, 999]
+    raw = pl._points_gpu(ctx, w, a)
+    pts = [raw[w * i:w * i + w] for i in range(n)]
+    assert all(pts[i] == bytes(w) for i in (0, 64, 191, 999)) and pts[1] != bytes(w)
+    raw = pl._points_gpu(ctx, w, [x * k % R for x, k in zip(a, ks)])
+    want = [raw[w * i:w * i + w] for i in range(n)]
+    for i in sorted(set(random.Random(n).sample(range(n), 16) + special)):
+        assert want[i] == oracle(g2, pts[i], ks[i]), 'the expectation itself, lane %d' % i
+    runs = [(mont, in_place, 0, True) for mont in (False, True) for in_place in (False, True)] + [(True, False, 0, False)] + ([] if g2 else [(True, True, 1, True)])
+    for mont, in_place, form, hook in runs:
+        got = scale(gpu, g2, pts, ks, mont, in_place, form, hook=hook)
+        for i in range(n):
+            assert got[i] == want[i], 'g2 %d mont %d in place %d form %d hook %d: lane %d, k = %x' % (g2, mont, in_place, form, hook, i, ks[i])
 
 
 def test_many_points_under_one_scalar_against_the_one_scalar_engine(gpu):

@@ -4,7 +4,8 @@ a restatement in Python integers, and the addition chain of the scale kernel on 
 import ctypes, hashlib, os, shutil, struct, subprocess
 import pytest
 import oracle_lib as ol
-from g2_py import f2add, f2mul, f2sub, f2inv, g2_mul, g2_bytes, on_twist, in_g2, TWIST_H
+from g2_py import g2_bytes, on_twist, in_g2
+from g2_challenge import challenge_py
 from zkcensus_amd import _native, phase2
 
 ROOT = ol.ROOT
@@ -107,48 +108,7 @@ def test_section10_reader_under_asan_ubsan(tmp_path):
     assert r.returncode == 0 and 'phase2 reader: ok' in r.stdout, (r.stdout + r.stderr)[-3000:]
 
 
-# ---- the G2 challenge: the derivation of include/zkcensus_phase2.h / csrc/zkc_phase2.hip restated with hashlib and integers.  The square root here is the norm method
-# (sqrt of the norm in Fq, then of (a0 +- s) / 2), not the library's complex method: the choice between +-y is canonical, so the two must agree. ----
-def fq_sqrt(a):
-    s = pow(a, (Q + 1) // 4, Q)
-    return s if s * s % Q == a % Q else None
-
-
-def f2_sqrt(a):
-    a0, a1 = a
-    if a1 == 0:
-        s = fq_sqrt(a0)
-        if s is not None: return (s, 0)
-        s = fq_sqrt(-a0 % Q)
-        return (0, s)                                                               # (s u)^2 = -s^2 = a0
-    n = fq_sqrt((a0 * a0 + a1 * a1) % Q)
-    if n is None: return None
-    half = pow(2, -1, Q)
-    for t in ((a0 + n) * half % Q, (a0 - n) * half % Q):
-        y0 = fq_sqrt(t)
-        if y0 is not None and y0 != 0:
-            y = (y0, a1 * pow(2 * y0, -1, Q) % Q)
-            if f2mul(y, y) == (a0 % Q, a1 % Q): return y
-    return None
-
-
-def challenge_py(transcript):
-    b2 = f2mul((3, 0), f2inv((9, 1)))
-    ctr = 0
-    while True:
-        stream = b''.join(hashlib.sha256(transcript + struct.pack('<I', ctr) + bytes([j])).digest() for j in range(4))
-        ctr += 1
-        c0, c1 = (int.from_bytes(stream[32 * w:32 * w + 32], 'big') & ((1 << 254) - 1) for w in range(2))
-        if c0 >= Q or c1 >= Q: continue
-        x = (c0, c1)
-        y = f2_sqrt(f2add(f2mul(f2mul(x, x), x), b2))
-        if y is None: continue
-        ny = f2sub((0, 0), y)
-        small, large = sorted([y, ny], key=lambda v: (v[1], v[0]))
-        p = g2_mul((x, large if stream[127] & 1 else small), TWIST_H)
-        if p is not None: return p
-
-
+# ---- the G2 challenge against its restatement with hashlib and integers (tests/g2_challenge.py, which phase 1's record writer shares) ----
 @pytest.mark.parametrize('transcript', [bytes(64), bytes(range(64)), hashlib.blake2b(b'zkcensus phase 2', digest_size=64).digest()])
 def test_challenge_g2_against_the_python_restatement(transcript):
     out = ctypes.create_string_buffer(128)

@@ -13,7 +13,8 @@ from zkcensus_amd import _native, setup
 ROOT, R = ol.ROOT, ol.R
 SEED = bytes(range(11, 43))
 NEW_ENTRY_POINTS = sorted(['zkc_g1_scale_each_dev', 'zkc_g2_scale_each_dev', 'zkc_ptau_new', 'zkc_ptau_contribute', 'zkc_ptau_contributions', 'zkc_ptau_verify_contributions',
-                           'zkc_ptau_contribute_stats', 'zkc_debug_ptau_contribute', 'zkc_debug_scale_each_dev', 'zkc_debug_scale_each_stats', 'zkc_debug_scale_each_work_bytes'])
+                           'zkc_ptau_contribute_stats', 'zkc_debug_ptau_contribute', 'zkc_debug_scale_each_dev', 'zkc_debug_scale_each_stats', 'zkc_debug_scale_each_work_bytes',
+                           'zkc_debug_tau_scalars_dev'])
 BAD_ARG, FORMAT = 4, 5
 
 
@@ -145,6 +146,83 @@ def test_changed_chain_is_rejected_with_its_reason(chain, tmp_path, case):
     bad = write_sections(tmp_path / 'bad.ptau', secs, order)
     ok, _, why = setup.verify_ptau_contributions(None, bad, seed=SEED)
     assert not ok and all(w in why for w in words), why
+
+
+# ---- the record against its restatement in Python (tests/ptau_contrib_lib.py: hashlib, tests/g2_challenge.py, the oracle's products), in both directions ----
+def test_library_records_against_the_restatement(chain):
+    """what the library wrote, recomputed from the header's description alone: every stored transcript, every returned hash, g2_spx = x g2_sp with g2_sp hashed from
+    the transcript, g1_sx = x g1_s"""
+    f, hashes = chain
+    raws = [r['raw'] for r in setup.ptau_contributions(f[3])]
+    assert len(raws) == 3
+    for k, (raw, s) in enumerate(zip(raws, (S1, S2, S3))):
+        poks = pc.poks_of(raw)
+        tr = pc.transcript(3, raws[:k], poks)
+        assert raw[pc.OFF_TRANSCRIPT:pc.OFF_TRANSCRIPT + 64] == tr, k
+        assert hashes[k] == pc.contribution_hash(3, raws[:k + 1]), k
+        for i in range(3):
+            g1_s, g1_sx, g2_spx = (pc.from_mont(p) for p in poks[i])
+            assert g2_spx == ol.msm_g2(pc.challenge(tr, i), ol.le32(s[i])), (k, i)
+            assert g1_sx == ol.g1_mul(g1_s, s[i]), (k, i)
+        # the five points are the file's after that contribution
+        secs, _ = read_sections(f[k + 1])
+        assert pc.five_of(raw) == (bytes(secs[2][64:128]), bytes(secs[3][128:256]), bytes(secs[4][:64]), bytes(secs[5][:64]), bytes(secs[6]))
+
+
+@pytest.fixture(scope='module')
+def py_chain(tmp_path_factory):
+    """a chain of three written by tests/ptau_contrib_lib.py alone: the sections of its last file, the file, and the file after the first contribution"""
+    d = tmp_path_factory.mktemp('py_chain')
+    secs, recs = pc.make_chain(3, [S1, S2, S3])
+    first, recs1 = pc.make_chain(3, [S1])
+    assert recs1 == recs[:1]
+    return secs, recs, write_sections(d / 'py3.ptau', secs), write_sections(d / 'py1.ptau', first), first
+
+
+def test_restatement_records_against_the_library(py_chain, tmp_path):
+    secs, recs, last, first, _ = py_chain
+    assert setup.verify_ptau_contributions(None, last, seed=SEED) == (True, 3, '')
+    assert setup.verify_ptau_contributions(first, last, seed=SEED) == (True, 2, '')
+    got = setup.ptau_contributions(last)
+    assert [r['raw'] for r in got] == recs and [r['name'] for r in got] == ['py0', 'py1', 'py2']
+    # the library goes on from a file it did not write, and hashes the Python-made records as the restatement does
+    more = str(tmp_path / 'more.ptau')
+    h = setup.contribute_ptau(last, more, secrets=pc.S4, name='c3')
+    assert setup.verify_ptau_contributions(None, more, seed=SEED) == (True, 4, '')
+    assert setup.verify_ptau_contributions(last, more, seed=SEED) == (True, 1, '')
+    raws = [r['raw'] for r in setup.ptau_contributions(more)]
+    assert raws[:3] == recs and h == pc.contribution_hash(3, raws)
+
+
+# ---- one forgery per check ----
+FORGERIES = pc.forgeries(3, [S1, S2, S3])
+
+
+def test_forgery_table_names_every_check():
+    assert sorted(n.split()[0] for n in FORGERIES) == sorted(['3.1'] * 3 + ['3.3'] * 4 + ['3.4'] * 2 + ['3.5'] * 2 + ['4'] * 5 + ['3.2', '3'])
+
+
+@pytest.mark.parametrize('case', sorted(FORGERIES))
+def test_forged_chain_is_refused_by_its_own_check(py_chain, tmp_path, case):
+    """each forgery is applied to a chain that is accepted first, and the reason must be that of the check the forgery is for (its number is the case's first word),
+    which shows the forgery valid under the checks before it"""
+    secs, _, last, first, first_secs = py_chain
+    change_next, change_prev, words = FORGERIES[case]
+    prev = None
+    if change_prev:
+        assert setup.verify_ptau_contributions(first, last, seed=SEED) == (True, 2, '')
+        psecs = {i: bytearray(b) for i, b in first_secs.items()}
+        change_prev(psecs)
+        assert psecs != first_secs
+        prev = write_sections(tmp_path / 'prev.ptau', psecs)
+    else:
+        assert setup.verify_ptau_contributions(None, last, seed=SEED) == (True, 3, '')
+    nsecs = {i: bytearray(b) for i, b in secs.items()}
+    change_next(nsecs)
+    assert change_prev or nsecs != secs
+    bad = write_sections(tmp_path / 'bad.ptau', nsecs)
+    ok, _, why = setup.verify_ptau_contributions(prev, bad, seed=SEED)
+    assert not ok and all(w in why for w in words), (case, why)
 
 
 def test_prev_must_be_a_prefix_and_of_the_same_power(chain, tmp_path):

@@ -167,6 +167,7 @@ def load():
     L.zkc_debug_scale_each_dev.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint32, vp, ctypes.c_int, vp, ctypes.c_int]
     L.zkc_debug_scale_each_work_bytes.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_int]; L.zkc_debug_scale_each_work_bytes.restype = ctypes.c_uint64
     L.zkc_debug_scale_each_stats.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.zkc_debug_tau_scalars_dev.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, vp]
     L.zkc_ptau_new.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, sz]
     L.zkc_ptau_contribute.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, sz]
     L.zkc_debug_ptau_contribute.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, sz]

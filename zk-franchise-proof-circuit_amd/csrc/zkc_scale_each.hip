@@ -60,7 +60,8 @@ namespace {
 constexpr uint32_t CHUNK = 1u << 20;             // points per chunk of a section: 2.8 GB of G2 work space (128 B point, 32 B scalar, 2304 B table, 256 B sum per lane)
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr int WIN_ROWS = 8;                      // 1P .. 8P
-constexpr int POW_ROWS = 32;                     // tau'^(2^k), k < 32: exponents reach 2^29 - 2 at power 28
+constexpr int POW_ROWS = 32;                     // tau'^(2^k), k < 32: zkc_tau_scalars walks these 32 bits of first + lane and no more.  A contribution stays far below
+                                                 // 2^32 through the limit on the file's power (exponents reach 2^29 - 2 at power 28); the hook refuses first + n > 2^32
 constexpr int MULT_ROWS = 3;                     // then 1, alpha', beta': the multiplier of a section is a row of the same table, which is cleared with it
 
 // ================================================================ device ================================================================
@@ -275,6 +276,11 @@ struct Waste {
     Fr pw[POW_ROWS + MULT_ROWS];                 // tau'^(2^k), then 1, alpha', beta'
     ~Waste() { Secret::wipe(pw, sizeof pw); }
 };
+// the table zkc_tau_scalars reads, from the Montgomery forms of W: of a contribution, and of the hook zkc_debug_tau_scalars_dev (whose multiplier sits in alpha's row)
+void fill_power_table(Waste& W) {
+    W.pw[0] = W.m[0].f; for (int k = 1; k < POW_ROWS; k++) W.pw[k] = W.pw[k - 1] * W.pw[k - 1];
+    W.pw[POW_ROWS] = Fr::one(); W.pw[POW_ROWS + 1] = W.m[1].f; W.pw[POW_ROWS + 2] = W.m[2].f;
+}
 
 int fail(zkc_ctx* ctx, char* err, size_t errlen, int code, const std::string& m) { if (ctx) zkc_fail(ctx, code, m); return err_out(err, errlen, code, m); }
 
@@ -357,6 +363,13 @@ struct DevWaste {                                 // the device's copy of the po
     }
 };
 
+// d_ks[i] = (mult < 0 ? 1 : multiplier `mult` of the table) * tau'^(first + i), i < np, from the uploaded table d_pw, on the context's stream: the one launch of
+// zkc_tau_scalars, for a chunk of a contribution and for the hook.  first + np <= 2^32 is the caller's to keep.  false: the launch failed
+bool launch_tau_scalars(zkc_ctx* ctx, const void* d_pw, int mult, uint64_t first, uint32_t np, void* d_ks) {
+    hipLaunchKernelGGL(zkc_tau_scalars, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, (const Fr*)d_pw, (uint32_t)(POW_ROWS + (mult < 0 ? 0 : mult)), first, np, (uint32_t*)d_ks);
+    return hipGetLastError() == hipSuccess;
+}
+
 // section `sec` of the input times mult * tau'^i, appended to the output.  keep[j] (j < nkeep) = the new point of index keep_idx[j].  rc != 0: err is written
 template <class F>
 int section_pass(zkc_ctx* ctx, const parse::Ptau& pt, parse::PtauOut& o, int sec, const Waste& W, int mult /* -1: none, 1: alpha', 2: beta' */, bool tau_powers, uint32_t chunk, int form,
@@ -380,8 +393,7 @@ int section_pass(zkc_ctx* ctx, const parse::Ptau& pt, parse::PtauOut& o, int sec
         uint32_t bad = first_infinity<F>(buf.data(), np);
         if (ctx) {
             if (hipMemcpy(d_pts.p, buf.data(), (size_t)np * PT, hipMemcpyHostToDevice) != hipSuccess) return err_out(err, errlen, zkc_fail(ctx, ZKC_ERR_HIP, "zkc_ptau_contribute: upload"), zkc_last_error(ctx));
-            hipLaunchKernelGGL(zkc_tau_scalars, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, (const Fr*)dw.pw.p, (uint32_t)(POW_ROWS + (mult < 0 ? 0 : mult)), tau_powers ? c0 : 0ull, np, (uint32_t*)dw.ks.p);
-            if (hipGetLastError() != hipSuccess) return err_out(err, errlen, zkc_fail(ctx, ZKC_ERR_HIP, "zkc_ptau_contribute: scalar kernel"), zkc_last_error(ctx));
+            if (!launch_tau_scalars(ctx, dw.pw.p, mult, tau_powers ? c0 : 0ull, np, dw.ks.p)) return err_out(err, errlen, zkc_fail(ctx, ZKC_ERR_HIP, "zkc_ptau_contribute: scalar kernel"), zkc_last_error(ctx));
             g_con_ms[1] += ms_since(t0);
             double kms[2] = {0, 0}; uint32_t kbad = NONE;
             if ((rc = scale_each_dev<F>(ctx, d_pts.p, np, dw.ks.p, true, d_pts.p, form, &kbad, kms))) return err_out(err, errlen, rc, zkc_last_error(ctx));
@@ -426,8 +438,7 @@ int contribute(const char* fn, zkc_ctx* ctx, const char* src_path, const char* d
         if (std_is_zero(W.std[i]) || !fp_std_lt_p<FrParams>(W.std[i])) return fail(ctx, err, errlen, ZKC_ERR_BAD_ARG, std::string(fn) + ": tau', alpha' and beta' must be in [1, r)");
         W.m[i].f = fp_from_std<FrParams>(W.std[i].v);
     }
-    W.pw[0] = W.m[0].f; for (int k = 1; k < POW_ROWS; k++) W.pw[k] = W.pw[k - 1] * W.pw[k - 1];
-    W.pw[POW_ROWS] = Fr::one(); W.pw[POW_ROWS + 1] = W.m[1].f; W.pw[POW_ROWS + 2] = W.m[2].f;
+    fill_power_table(W);
     clk::time_point t0 = clk::now();
     Chain in; std::string why;
     if (!read_chain(src_path, in, why)) return fail(ctx, err, errlen, ZKC_ERR_FORMAT, std::string(fn) + ": " + why);
@@ -545,6 +556,31 @@ extern "C" int zkc_ptau_contribute(zkc_ctx* ctx, const char* src_path, const cha
 extern "C" int zkc_debug_ptau_contribute(zkc_ctx* ctx, const char* src_path, const char* dst_path, const uint8_t* secrets96, const char* name, uint32_t chunk_points, int form,
                                          uint8_t* hash64, char* err, size_t errlen) {
     return contribute("zkc_debug_ptau_contribute", ctx, src_path, dst_path, secrets96, name, chunk_points, form, hash64, err, errlen);
+}
+
+// the scalars of a chunk on their own: the table of fill_power_table with mult in alpha's row, the launch of launch_tau_scalars, a copy to the caller's buffer; the table
+// and the work copy of the scalars are cleared on the stream as a contribution's are (DevWaste)
+extern "C" int zkc_debug_tau_scalars_dev(zkc_ctx* ctx, const uint8_t* tau32, const uint8_t* mult32, uint64_t first, uint32_t n, void* d_out) {
+    const char* const fn = "zkc_debug_tau_scalars_dev";
+    if (!ctx || !tau32 || !mult32 || !d_out || n == 0) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, std::string(fn) + ": bad argument");
+    if (first > (1ull << 32) || first + n > (1ull << 32)) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, std::string(fn) + ": first + n exceeds 2^32, the exponents the power table serves");
+    Waste W;
+    memcpy(W.std[0].v, tau32, 32); memcpy(W.std[1].v, mult32, 32); W.std[2].v[0] = 1;
+    for (int i = 0; i < 3; i++) {
+        if (std_is_zero(W.std[i]) || !fp_std_lt_p<FrParams>(W.std[i])) return zkc_fail(ctx, ZKC_ERR_BAD_ARG, std::string(fn) + ": tau and mult must be in [1, r)");
+        W.m[i].f = fp_from_std<FrParams>(W.std[i].v);
+    }
+    fill_power_table(W);
+    ZKC_LOCK(ctx);
+    ZKC_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    DevWaste dw; int rc;
+    dw.ctx = ctx; dw.ks_bytes = (size_t)n * 32;
+    if ((rc = dw.pw.alloc(ctx, sizeof(Fr) * (POW_ROWS + MULT_ROWS))) || (rc = dw.ks.alloc(ctx, dw.ks_bytes))) return rc;
+    ZKC_HIP_CHECK(ctx, hipMemcpy(dw.pw.p, W.pw, sizeof(Fr) * (POW_ROWS + MULT_ROWS), hipMemcpyHostToDevice));
+    if (!launch_tau_scalars(ctx, dw.pw.p, 1, first, n, dw.ks.p)) return zkc_fail(ctx, ZKC_ERR_HIP, std::string(fn) + ": scalar kernel");
+    ZKC_HIP_CHECK(ctx, hipMemcpyAsync(d_out, dw.ks.p, dw.ks_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ZKC_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKC_OK;
 }
 
 extern "C" int zkc_ptau_contribute_stats(double ms[6]) {

@@ -64,6 +64,12 @@ def debug_scale_each(ctx, g2, d_points_ptr, n, d_scalars_ptr, d_out_ptr, mont=Fa
     ctx._check(ctx._lib.zkc_debug_scale_each_dev(ctx._h, 1 if g2 else 0, d_points_ptr, n, d_scalars_ptr, 1 if mont else 0, d_out_ptr, form))
 
 
+def debug_tau_scalars(ctx, tau, mult, first, n, d_out_ptr):
+    """Test hook (zkc_debug_tau_scalars_dev): d_out[i] = mult * tau^(first + i) mod r for i < n, 32 bytes little endian each, made by the power table and the kernel a
+    powers-of-tau contribution makes its scalars with.  tau, mult: integers in [1, r); first + n <= 2^32."""
+    ctx._check(ctx._lib.zkc_debug_tau_scalars_dev(ctx._h, tau.to_bytes(32, 'little'), mult.to_bytes(32, 'little'), first, n, d_out_ptr))
+
+
 def scale_each_stats():
     """Milliseconds of the calling thread's last g1_scale_each / g2_scale_each / debug_scale_each: the scale kernel (point checks included), the conversion to affine."""
     from . import _native
